@@ -8,9 +8,14 @@ covariance assembly (+noise) -> blocked Cholesky -> two triangular solves -> log
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --steps K --warmup W          (no launcher: bench.py starts its N ranks itself, see launch_ranks)
 
-N = 1: the fused single-GPU evaluation (fvgp_hip_loglik).  The line also carries, measured outside the timed
-region, the other BASELINE.json configurations that fit one GPU ("configs") and the CPU restatement of the
-reference path timed on this host ("cpu_baseline").
+N = 1: the fused single-GPU evaluation (fvgp_hip_loglik).  A plain run sets up, warms up, times the K steps and prints
+the line (roofline and stage figures come from events inside the timed steps).  `--full` adds, measured outside the
+timed region, the other BASELINE.json configurations that fit one GPU ("configs"), the CPU restatement of the
+reference path timed on this host ("cpu_baseline") and the headline's agreement with it ("headline_parity").
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (float64): loglik, logdet,
+quad, alpha (KVinvY, n values), factor_diag (the n diagonal entries of L) and factor_lower_sample (2^20 entries of
+the lower triangle of L at fixed, seeded positions) -- two builds run with the same arguments can be compared output
+for output.
 
 N > 1: ONE evaluation at a time, K+V row-sharded over the N ranks (block-cyclic 128-row blocks, RCCL all-gather of
 the panel factors over xGMI: fvgp_amd/dist.py) -- the partitioning the north star names; "scaling": "strong".
@@ -63,34 +68,67 @@ def _host_ram_gb():
         return 0.0
 
 
+# one oracle evaluation in a child process of its own (no GPU): the host's LAPACK can die on the full size (scipy's
+# OpenBLAS potrf segfaults from N ~ 32k when it runs on 8 or 16 threads), and that must not take the bench with it
+_ORACLE_CHILD = r"""
+import json, sys, time
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from bench import synth
+from oracle import fvgp_oracle as orc
+n, d, theta = int(sys.argv[2]), int(sys.argv[3]), np.array(json.loads(sys.argv[4]))
+x, y = synth(n, d)
+t0 = time.perf_counter()
+ll, st = orc.log_likelihood_once(x, y, np.full(n, 0.01), theta, "rbf_ard")
+print(json.dumps({"wall": time.perf_counter() - t0, "loglik": float(ll), "stages": st}))
+"""
+
+
+class OracleRunFailed(RuntimeError):
+    pass
+
+
 def cpu_baseline(n_full, d, sample_n):
     """The oracle timed on this host.  If the host has the memory (>= 100 GB: K, K+V and the factor of N = n_full)
     and a short probe says the full size finishes in a few minutes, the FULL size is run once and reported as
-    measured; otherwise a bounded sample is run and scaled with the stage exponents (assembly, addKV, solve: N^2;
-    potrf: N^3), labelled as such."""
-    from oracle import fvgp_oracle as orc
+    measured; otherwise, or when that run dies or overruns, a bounded sample is run and scaled with the stage
+    exponents (assembly, addKV, solve: N^2; potrf: N^3), labelled as such."""
+    import subprocess
     threads = _blas_threads()
     theta = np.array([1.0] + [0.3] * d)
 
     last = {}
 
-    def run(n):
-        x, y = synth(n, d)
-        t0 = time.perf_counter()
-        ll, st = orc.log_likelihood_once(x, y, np.full(n, 0.01), theta, "rbf_ard")
-        last.update(n=n, loglik=float(ll))          # kept: the HIP path is checked against it (headline_parity)
-        return time.perf_counter() - t0, st
+    def run(n, timeout=None):
+        try:
+            res = subprocess.run([sys.executable, "-c", _ORACLE_CHILD, ROOT, str(n), str(d), json.dumps(theta.tolist())],
+                                 capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+        except subprocess.TimeoutExpired:
+            raise OracleRunFailed(f"the oracle at N={n} did not finish within {timeout:.0f} s") from None
+        if res.returncode != 0:
+            how = f"signal {-res.returncode}" if res.returncode < 0 else f"exit status {res.returncode}"
+            tail = " | ".join(res.stderr.strip().splitlines()[-3:])
+            raise OracleRunFailed((f"the oracle at N={n} died ({how})" + (f": {tail}" if tail else ""))[:400])
+        rec = json.loads(res.stdout.strip().splitlines()[-1])
+        last.update(n=n, loglik=rec["loglik"])      # kept: the HIP path is checked against it (headline_parity)
+        return rec["wall"], rec["stages"]
 
     def scaled(st, r):
         return (st["kmat"] + st["addKV"] + st["solve_logdet"]) * r ** 2 + st["potrf"] * r ** 3
 
     ram = _host_ram_gb()
+    full_error = None
     if sample_n <= 0:
         probe_n = 12000
         _, st = run(probe_n)
         est = scaled(st, n_full / probe_n)
         if ram >= 100.0 and est <= 300.0:
-            wall, st = run(n_full)
+            try:
+                wall, st = run(n_full, timeout=min(360.0, 60.0 + 2.0 * est))
+            except OracleRunFailed as e:
+                full_error = str(e)
+                _progress(f"CPU leg: {full_error}; the sample is scaled instead")
+        if full_error is None and ram >= 100.0 and est <= 300.0:
             return {"value": 1.0 / wall, "unit": "evals/s", "cores": threads, "kind": "port",
                     "sample": (f"oracle (numpy/scipy restatement) on the FULL workload N={n_full}, d={d}, one evaluation: kmat "
                                f"{st['kmat']:.1f}s addKV {st['addKV']:.1f}s potrf {st['potrf']:.1f}s solve+logdet "
@@ -101,13 +139,16 @@ def cpu_baseline(n_full, d, sample_n):
         sample_n = 18000
     wall, st = run(sample_n)
     est = scaled(st, n_full / sample_n)
-    return {"value": 1.0 / est, "unit": "evals/s", "cores": threads, "kind": "port",
-            "sample": (f"oracle (numpy/scipy restatement) on N={sample_n}, d={d}: kmat {st['kmat']:.2f}s addKV "
-                       f"{st['addKV']:.2f}s potrf {st['potrf']:.2f}s solve+logdet {st['solve_logdet']:.2f}s "
-                       f"(wall {wall:.1f}s, BLAS threads {threads}, host cpus {os.cpu_count()}, RAM {ram:.0f} GB); scaled to "
-                       f"N={n_full} with N^2 (assembly, addKV, solve) and N^3 (potrf) -> {est:.0f}s per evaluation"),
-            "measured_seconds_at_sample": wall, "extrapolated": True, "oracle_n": last["n"], "oracle_loglik": last["loglik"],
-            "oracle_theta": theta.tolist()}
+    out = {"value": 1.0 / est, "unit": "evals/s", "cores": threads, "kind": "port",
+           "sample": (f"oracle (numpy/scipy restatement) on N={sample_n}, d={d}: kmat {st['kmat']:.2f}s addKV "
+                      f"{st['addKV']:.2f}s potrf {st['potrf']:.2f}s solve+logdet {st['solve_logdet']:.2f}s "
+                      f"(wall {wall:.1f}s, BLAS threads {threads}, host cpus {os.cpu_count()}, RAM {ram:.0f} GB); scaled to "
+                      f"N={n_full} with N^2 (assembly, addKV, solve) and N^3 (potrf) -> {est:.0f}s per evaluation"),
+           "measured_seconds_at_sample": wall, "extrapolated": True, "oracle_n": last["n"], "oracle_loglik": last["loglik"],
+           "oracle_theta": theta.tolist()}
+    if full_error is not None:
+        out["full_size_error"] = full_error
+    return out
 
 
 def cpu_small_sizes(small):
@@ -335,6 +376,28 @@ def config_records():
 
 
 # ------------------------------------------------------------------------------------------------
+DUMP_FACTOR_SAMPLE = 1 << 20        # lower-triangle entries of L that --dump-outputs writes (8 MB)
+
+
+def dump_outputs(out_dir, KV, alpha, n, ll, logdet, quad):
+    """--dump-outputs: what the last timed step handed its caller (fvgp_hip_loglik: the three scalars, KVinvY in alpha, the
+    factor L in the lower triangle of the row-major KV), as float64 .npy files; L is sampled at positions drawn from a fixed
+    seed, so that runs with the same arguments write the same entries"""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(20240502)
+    i, j = rng.integers(0, n, DUMP_FACTOR_SAMPLE), rng.integers(0, n, DUMP_FACTOR_SAMPLE)
+    ld = KV.stride(0)
+    flat = KV.view(-1)
+    pos = torch.as_tensor(np.maximum(i, j) * ld + np.minimum(i, j), device=KV.device)
+    diag = torch.arange(n, device=KV.device) * (ld + 1)
+    arrays = {"loglik": np.array([ll]), "logdet": np.array([logdet]), "quad": np.array([quad]),
+              "alpha": alpha[:n, 0].cpu().numpy(), "factor_diag": flat[diag].cpu().numpy(),
+              "factor_lower_sample": flat[pos].cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def single_gpu_eval(H, _lib, x, y, thetas):
     """fused single-GPU evaluations of the given thetas on this rank (replica leg / cross-check); returns (values, seconds)"""
     import torch
@@ -650,14 +713,21 @@ def main():
                          "tests); auto = the whole timed region through the backend's own (rccl for nccl, torch for gloo) AND through "
                          "ipc, both recorded in the line, the faster one its headline")
     ap.add_argument("--sharded-timeout", type=float, default=600.0)
-    ap.add_argument("--cpu-sample-n", type=int, default=0, help="0 = the full workload if the host can hold it, else N=18000 scaled")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the timed steps also measure the C2 / C3 / C4 / C5 records, the CPU leg and the headline's "
+                         "agreement with the oracle (a plain run does only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: write what the last timed step computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-sample-n", type=int, default=0, help="with --full: 0 = the full workload if the host can hold it, else N=18000 scaled")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU leg")
     ap.add_argument("--inject-sharded-failure", action="store_true", help=argparse.SUPPRESS)   # tests: the sharded run raises on every rank
     ap.add_argument("--inject-ipc-hang", action="store_true", help=argparse.SUPPRESS)          # tests: the direct-pull candidate never returns
-    ap.add_argument("--no-configs", action="store_true", help="skip the C2 / C3 / C5 records measured after the timed region")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the C2 / C3 / C5 records measured after the timed region")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or args.mode == "sharded"):
+        ap.error("--dump-outputs writes the single-GPU evaluation's outputs: --gpus 1 without --mode sharded")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC: RCCL across processes needs it on this driver
     if args.gpus < 1:
@@ -755,9 +825,11 @@ def main():
         elapsed = float(tt.item())
     H.set_option("profile", 0)
     _progress(f"timed region done: {1e3 * elapsed / args.steps:.1f} ms per step")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, KV, alpha, n, ll, logdet, quad)
     # outside the timed region: one evaluation at the theta the CPU leg's oracle runs, on the same resident buffers (headline_parity)
     hip_theta0 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         hip_theta0, _, _, info0 = H.loglik(0, xd, theta0, vd, ymd, KV, alpha)
         if info0 != 0:
             hip_theta0 = float("nan")
@@ -813,7 +885,7 @@ def main():
     del KV, alpha
     H.close()
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_configs and n == 50000:
             try:
                 out["configs"] = config_records()

@@ -252,3 +252,54 @@ def test_config4_size_n100000_two_drivers_agree():
     np.testing.assert_allclose(ll2, ll, rtol=1e-11)
     del gp
     torch.cuda.empty_cache()
+
+
+def _bench(args, tmp_path, timeout):
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + args, capture_output=True, text=True,
+                         env=env, timeout=timeout, cwd=str(tmp_path))
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py --gpus 1` run: the headline only (no side records), --steps timed steps, ms_per_step; --dump-outputs
+    writes the last step's outputs, the same ones for the same arguments (the inputs are seeded)."""
+    n = 3000
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"dump{k}"
+        line = _bench(["--steps", "3", "--warmup", "1", "--npoints", str(n), "--dump-outputs", str(d)], tmp_path, 300)
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "f64"
+        assert line["metric"] == "log_marginal_likelihood_evals_per_sec" and line["unit"] == "evals/s" and line["higher_is_better"]
+        assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] - 1e3) <= 1e-6 * 1e3
+        assert not {"configs", "cpu_baseline", "headline_parity"} & set(line)
+        files = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert set(files) == {"loglik", "logdet", "quad", "alpha", "factor_diag", "factor_lower_sample"}
+        assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert files["loglik"][0] == line["loglik_last"] and files["alpha"].shape == (n,) and files["factor_diag"].shape == (n,)
+        assert np.all(files["factor_diag"] > 0)
+        np.testing.assert_allclose(files["logdet"][0], 2.0 * np.sum(np.log(files["factor_diag"])), rtol=1e-12)
+        outs.append(files)
+    for name in outs[0]:
+        np.testing.assert_array_equal(outs[0][name], outs[1][name], err_msg=name)
+    # the last timed step is theta_0 (1 + 0.02 (warmup + steps - 1)): the same value the oracle gives
+    from oracle import fvgp_oracle as orc
+    x, y = synth(n, 3)
+    ref, _ = orc.log_likelihood_once(x, y, np.full(n, 0.01), np.array([1.0, 0.3, 0.3, 0.3]) * 1.06, "rbf_ard")
+    assert abs(outs[0]["loglik"][0] - ref) <= 1e-10 * abs(ref)
+
+
+def test_bench_full_run_keeps_the_cpu_leg_and_the_parity_check(tmp_path):
+    """`--full` adds what a plain run leaves out: the CPU leg (the oracle on this host) and the headline's agreement with it."""
+    line = _bench(["--steps", "2", "--warmup", "1", "--npoints", "3000", "--full"], tmp_path, 600)
+    assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["oracle_n"] > 0
+    assert line["headline_parity"]["ok"] and line["headline_parity"]["rel_diff"] <= 1e-10
