@@ -31,7 +31,9 @@ SYMBOLS = [
     "fvgp_hip_grad_trace_cols", "fvgp_hip_comm_unique_id", "fvgp_hip_comm_init", "fvgp_hip_comm_init_callbacks", "fvgp_hip_comm_destroy", "fvgp_hip_ipc_window", "fvgp_hip_comm_init_ipc", "fvgp_hip_all_reduce",
     "fvgp_hip_all_gather", "fvgp_hip_comm_profile", "fvgp_hip_dist_workspace", "fvgp_hip_loglik_dist", "fvgp_hip_dist_scratch", "fvgp_hip_solve_dist",
     "fvgp_hip_posterior_dist", "fvgp_hip_grad_dist", "fvgp_hip_loglik_rows", "fvgp_hip_get_profile_ex", "fvgp_hip_comm_info", "fvgp_hip_comm_check", "fvgp_hip_posterior_prepare",
+    "fvgp_hip_loglik_batch", "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes",
 ]
+BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
 
 
 # ---- row-sharded entry points: structures of include/fvgp_hip.h ---------------------------------------------------
@@ -146,6 +148,13 @@ def loglik_dim(n, ncol=1):
     return pad128(n) if pad128(n) - n >= ncol else pad128(n + ncol)
 
 
+def loglik_batch_dim(n, ncol=1):
+    """rows = columns of one problem's square in the batched scratch (fvgp_hip_loglik_batch_dim): loglik_dim(n, ncol), 0 past
+    BATCH_MAX_DIM"""
+    d = loglik_dim(n, ncol)
+    return d if d <= BATCH_MAX_DIM else 0
+
+
 def lib():
     """Load (once) and return the ctypes library with argtypes set."""
     global _lib
@@ -195,6 +204,11 @@ def lib():
     L.fvgp_hip_loglik.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_i, c_p, c_l, c_p, P_d, P_i]
     L.fvgp_hip_loglik_rows.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_i, c_p, c_l, c_l, c_p, P_d, P_i]
     L.fvgp_hip_get_profile_ex.argtypes = [c_p, P_d]
+    L.fvgp_hip_loglik_batch.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, P_d, P_i]
+    L.fvgp_hip_loglik_batch_dim.argtypes = [c_l, c_i]
+    L.fvgp_hip_loglik_batch_dim.restype = c_l
+    L.fvgp_hip_loglik_batch_workspace_bytes.argtypes = [c_l, c_i, c_l]
+    L.fvgp_hip_loglik_batch_workspace_bytes.restype = c_l
     L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
     L.fvgp_hip_grad_trace.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, P_d]
     L.fvgp_hip_posterior.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_p, c_l,
@@ -223,7 +237,8 @@ def lib():
     L.fvgp_hip_grad_trace_cols.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_l, c_l, c_p, c_l, c_p, P_d]
     bind_dist(L)
     for s in SYMBOLS:
-        if s not in ("fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_workspace_bytes", "fvgp_hip_dist_scratch"):
+        if s not in ("fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_workspace_bytes", "fvgp_hip_dist_scratch",
+                     "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes"):
             getattr(L, s).restype = c_i
     _lib = L
     return L
@@ -413,6 +428,32 @@ class Handle(DistCalls):
                                           ymean.shape[1], _ptr(KV), rows, KV.stride(0), _ptr(alpha), out, ctypes.byref(info)),
                "fvgp_hip_loglik_rows")
         return out[0], out[1], out[2], info.value
+
+    def loglik_batch(self, kernel_id, x, thetas, vdiag, ymean, KV):
+        """fvgp_hip_loglik_batch: the log marginal likelihood at the B rows of `thetas` (host, B x ntheta) in one call.
+        vdiag (1, n) / ymean (1, n, ncol) -- or 1-d / 2-d -- are shared by every problem; (B, n) / (B, n, ncol) give each its own.
+        KV: (B, dim, ld) device scratch, dim = loglik_batch_dim(n, ncol) (or any tensor whose first dimension strides the squares).
+        Returns (out (B, 3) ndarray of {log-likelihood, log|KV|, quad / ncol}, NaN where the factorisation failed; info (B,) ints)."""
+        t = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+        if t.ndim != 2:
+            raise ValueError("loglik_batch: thetas must be (B, ntheta)")
+        B, nt = t.shape
+        n, d = x.shape
+        vd = vdiag.reshape(1, n) if vdiag.dim() == 1 else vdiag
+        ym = ymean.reshape(1, *ymean.shape) if ymean.dim() == 2 else ymean
+        ncol = ym.shape[2]
+        for name, a in (("vdiag", vd), ("ymean", ym)):
+            if a.shape[0] not in (1, B) or not a.is_contiguous():
+                raise ValueError(f"loglik_batch: {name} must be contiguous with a leading dimension of 1 or B = {B}, got {tuple(a.shape)}")
+        if KV.dim() != 3 or KV.stride(2) != 1 or (B > 1 and KV.shape[0] < B):
+            raise ValueError(f"loglik_batch: KV must be a (B, dim, ld) tensor with unit column stride, got {tuple(KV.shape)}")
+        out = np.empty((B, 3), dtype=np.float64)
+        info = np.zeros(B, dtype=np.int32)
+        _check(lib().fvgp_hip_loglik_batch(self._h, int(kernel_id), _ptr(x), n, d, t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), nt, B,
+                                           _ptr(vd), n if vd.shape[0] > 1 else 0, _ptr(ym), n * ncol if ym.shape[0] > 1 else 0, ncol,
+                                           _ptr(KV), KV.stride(1), KV.stride(0), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                           info.ctypes.data_as(ctypes.POINTER(ctypes.c_int))), "fvgp_hip_loglik_batch")
+        return out, info
 
     def loglik_grad(self, kernel_id, x, theta, alpha, ncol, component, KV, work):
         t, tp, nt = _theta(theta)

@@ -4,6 +4,7 @@
 #include "common.h"
 #include <math.h>
 #include <string.h>
+#include <functional>
 
 // ---------------------------------------------------------------------------------------
 static thread_local std::string g_err;
@@ -43,6 +44,18 @@ int64_t fvgp_hip_padded_dim(int64_t n) { return pad128(n); }
 int64_t fvgp_hip_loglik_dim(int64_t n, int ncol) {
     if (n <= 0 || ncol < 1) return -1;
     return (pad128(n) - n) >= ncol ? pad128(n) : pad128(n + ncol);
+}
+int64_t fvgp_hip_loglik_batch_dim(int64_t n, int ncol) {
+    const int64_t dim = fvgp_hip_loglik_dim(n, ncol);
+    if (dim < 0) return -1;
+    return dim <= FVGP_BATCH_MAX_DIM ? dim : 0;
+}
+// per problem: the inverse of the diagonal block of the current step, the reciprocal pivots of every step, the theta table row, two
+// reductions, the info word (fvgp_hip_loglik_batch's layout, in this order)
+int64_t fvgp_hip_loglik_batch_workspace_bytes(int64_t n, int ncol, int64_t B) {
+    const int64_t dim = fvgp_hip_loglik_batch_dim(n, ncol);
+    if (dim <= 0 || B < 1) return -1;
+    return B * (LEAF_DOUBLES + dim + (1 + FVGP_MAX_DIM) + 2) * (int64_t)sizeof(double) + B * (int64_t)sizeof(int);
 }
 
 int fvgp_hip_create(fvgp_handle **out, int device, void *stream) {
@@ -90,6 +103,7 @@ int fvgp_hip_destroy(fvgp_handle *h) {
     if (h->chain_vhash) (void)hipFree(h->chain_vhash);
     if (h->vec) (void)hipFree(h->vec);
     if (h->hpin) (void)hipHostFree(h->hpin);
+    if (h->bat_ws) (void)hipFree(h->bat_ws);
     delete h;
     return 0;
 }
@@ -1270,6 +1284,120 @@ int fvgp_hip_loglik_rows(fvgp_handle *h, int kernel_id, const double *x, int64_t
     out_host[0] = -0.5 * (quad + logdet + (double)n * log(2.0 * M_PI));
     out_host[1] = logdet;
     out_host[2] = quad;
+    return 0;
+}
+
+// B independent evaluations side by side (batch.hip): assembly, appended rows, then per 128 columns one leaf launch, one panel TRSM
+// (product with the block inverse) and one update of the trailing lower tiles (K = 128), each over every problem, then one tail.
+// Every GEMM carries an explicit K range, so that it takes the 128-tile kernel whatever B is (a plain one-problem launch of a few
+// tiles would take the 64-tile kernel: other bits).
+int fvgp_hip_loglik_batch(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
+                          const double *thetas, int ntheta, int64_t B,
+                          const double *vdiag, int64_t vdiag_stride, const double *ymean, int64_t ymean_stride, int ncol,
+                          double *KV, int64_t ld, int64_t kv_stride, double *out_host, int *info_host) {
+    if (!h) return -1;
+    if (!x) return -3;
+    if (n <= 0) return -4;
+    if (n > FVGP_BATCH_MAX_DIM) { fvgp_set_error("loglik_batch: n exceeds FVGP_BATCH_MAX_DIM"); return -4; }
+    if (!thetas) return -6;
+    if (B < 1) { fvgp_set_error("loglik_batch: B >= 1"); return -8; }
+    KmatDesc k0d{};
+    int rc = kmat_desc_from_theta(kernel_id, d, thetas, ntheta, &k0d);
+    if (rc) return rc == -7 ? -5 : rc == -9 ? -7 : rc;
+    if (!vdiag) { fvgp_set_error("loglik_batch needs the noise variances (vdiag)"); return -9; }
+    if (vdiag_stride < 0) return -10;
+    if (!ymean) return -11;
+    if (ymean_stride < 0) return -12;
+    if (ncol < 1 || ncol > FVGP_MAX_RHS_VEC) { fvgp_set_error("1 <= ncol <= 8"); return -13; }
+    const int64_t dim = fvgp_hip_loglik_batch_dim(n, ncol);
+    if (dim <= 0) { fvgp_set_error("loglik_batch: fvgp_hip_loglik_batch_dim(n, ncol) exceeds FVGP_BATCH_MAX_DIM"); return -4; }
+    if (!KV || ((uintptr_t)KV & 15)) { fvgp_set_error("loglik_batch: KV must be 16-byte aligned"); return -14; }
+    if (ld < dim || (ld & 1)) { fvgp_set_error("loglik_batch: the leading dimension must be even and >= fvgp_hip_loglik_batch_dim(n, ncol)"); return -15; }
+    if (B > 1 && (kv_stride < dim * ld || (kv_stride & 1))) { fvgp_set_error("loglik_batch: kv_stride must be even and >= dim * ld"); return -16; }
+    if (!out_host) return -17;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t ws = (size_t)fvgp_hip_loglik_batch_workspace_bytes(n, ncol, B);
+    if (ws > h->bat_cap) {
+        if (h->bat_ws) HIPCHK(hipFree(h->bat_ws));
+        h->bat_ws = nullptr; h->bat_cap = 0;
+        HIPCHK(hipMalloc((void **)&h->bat_ws, ws));
+        h->bat_cap = ws;
+    }
+    constexpr int TW = 1 + FVGP_MAX_DIM;
+    double *linv = reinterpret_cast<double *>(h->bat_ws);
+    double *logdet = linv + B * LEAF_DOUBLES;
+    double *tab = logdet + B * dim;
+    double *red = tab + B * TW;
+    int *info = reinterpret_cast<int *>(red + 2 * B);
+    // sigma^2 and 1 / l of every problem, exactly as the single evaluation computes them (kmat_desc_from_theta)
+    h->bat_tab_host.assign((size_t)(B * TW), 0.0);
+    for (int64_t b = 0; b < B; ++b) {
+        KmatDesc kd{};
+        rc = kmat_desc_from_theta(kernel_id, d, thetas + b * ntheta, ntheta, &kd); if (rc) return rc == -7 ? -5 : rc == -9 ? -7 : rc;
+        h->bat_tab_host[(size_t)(b * TW)] = kd.sig;
+        for (int q = 0; q < d; ++q) h->bat_tab_host[(size_t)(b * TW + 1 + q)] = kd.invl[q];
+    }
+    HIPCHK(hipMemcpyAsync(tab, h->bat_tab_host.data(), (size_t)(B * TW) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(info, 0, (size_t)B * sizeof(int), h->stream));
+    const int kind = k0d.kind;
+    const int64_t stride = B > 1 ? kv_stride : 0;
+    // grid dimensions y / z take at most 65535: the problems go in groups of that many (results do not depend on the grouping)
+    constexpr int64_t GROUP = 65535;
+    for (int64_t b0 = 0; b0 < B; b0 += GROUP) {
+        const int64_t Bs = B - b0 < GROUP ? B - b0 : GROUP;
+        double *K0 = KV + b0 * stride;
+        rc = launch_kmat_batch(h, kind, x, n, d, tab + b0 * TW, vdiag + b0 * vdiag_stride, vdiag_stride, K0, ld, stride, dim, Bs); if (rc) return rc;
+        rc = launch_rhs_rows_batch(h, K0, stride, n, ld, ymean + b0 * ymean_stride, ymean_stride, ncol, vdiag + b0 * vdiag_stride, vdiag_stride, Bs);
+        if (rc) return rc;
+        // one 128-column step: leaf, then the TRSM of every row below by the block inverse
+        auto step = [&](int64_t k0) -> int {
+            const int64_t nv = n - k0, r0 = k0 + TILE, R = dim - r0;
+            int r = launch_leaf_batch(h, K0 + k0 * ld + k0, ld, stride, linv + b0 * LEAF_DOUBLES, logdet + b0 * dim + k0, dim, info + b0, (int)k0,
+                                      nv >= TILE ? TILE : (nv > 0 ? (int)nv : 0), Bs);
+            if (r || R <= 0) return r;
+            GemmDesc t{};          // rows below <- rows below * inv(L_kk)^T, in place
+            t.a_kmajor = 0; t.b_nmajor = 0; t.lower = 0; t.M = R; t.N = TILE; t.K = TILE; t.ke0 = TILE;
+            t.alpha = 1.0; t.beta = 0.0;
+            t.A = K0 + r0 * ld + k0; t.lda = ld; t.B = linv + b0 * LEAF_DOUBLES; t.ldb = TILE; t.C = K0 + r0 * ld + k0; t.ldc = ld;
+            t.batch_z = (int)Bs; t.a_bz = stride; t.b_bz = LEAF_DOUBLES; t.c_bz = stride;
+            return launch_gemm(h, t);
+        };
+        // recursive halving over the block columns (panel_factor_recursive's order, the whole square one panel): left half, ONE update
+        // of the right half's columns (every row below them, lower tiles) with K = the left half's width, right half.  The same flops
+        // as an update after every 128 columns, with far fewer read-modify-write passes over the trailing tiles.  The schedule
+        // depends on dim only.
+        std::function<int(int64_t, int64_t)> factor = [&](int64_t J0, int64_t Jend) -> int {
+            const int64_t blocks = (Jend - J0) / TILE;
+            if (blocks <= 1) return step(J0);
+            const int64_t mid = J0 + (blocks / 2) * TILE;
+            int r = factor(J0, mid); if (r) return r;
+            GemmDesc u{};          // rows [mid, dim) x columns [mid, Jend) -= L[mid:, J0:mid] L[mid:Jend, J0:mid]^T, lower tiles
+            u.a_kmajor = 0; u.b_nmajor = 0; u.lower = 1; u.M = dim - mid; u.N = Jend - mid; u.K = mid - J0; u.ke0 = mid - J0;
+            u.alpha = -1.0; u.beta = 1.0;
+            u.A = K0 + mid * ld + J0; u.lda = ld; u.B = u.A; u.ldb = ld; u.C = K0 + mid * ld + mid; u.ldc = ld;
+            u.batch_z = (int)Bs; u.a_bz = stride; u.b_bz = stride; u.c_bz = stride;
+            r = launch_gemm(h, u); if (r) return r;
+            return factor(mid, Jend);
+        };
+        rc = factor(0, dim); if (rc) return rc;
+        rc = launch_loglik_tail_batch(h, logdet + b0 * dim, dim, K0, stride, ld, n, ncol, red + 2 * b0, Bs); if (rc) return rc;
+    }
+    // ONE host round trip: the B reductions and the B info words in one copy
+    const size_t rbytes = (size_t)B * (2 * sizeof(double) + sizeof(int));
+    h->bat_out_host.resize(rbytes);
+    HIPCHK(hipMemcpyAsync(h->bat_out_host.data(), red, rbytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const double *r = reinterpret_cast<const double *>(h->bat_out_host.data());
+    const int *inf = reinterpret_cast<const int *>(r + 2 * B);
+    for (int64_t b = 0; b < B; ++b) {
+        const int ib = inf[b] > n ? 0 : inf[b];        // (cannot exceed n: the padding is an identity block)
+        if (info_host) info_host[b] = ib;
+        if (ib != 0) { out_host[3 * b] = out_host[3 * b + 1] = out_host[3 * b + 2] = NAN; continue; }
+        const double logdet_b = 2.0 * r[2 * b], quad = r[2 * b + 1] / (double)ncol;
+        out_host[3 * b] = -0.5 * (quad + logdet_b + (double)n * log(2.0 * M_PI));
+        out_host[3 * b + 1] = logdet_b;
+        out_host[3 * b + 2] = quad;
+    }
     return 0;
 }
 

@@ -143,6 +143,11 @@ struct fvgp_handle {
     struct CollRec { int kind; double bytes; hipEvent_t e0, e1; };
     std::vector<CollRec> coll_rec;
     std::vector<hipEvent_t> coll_ev_pool;
+    // batched evaluation (fvgp_hip_loglik_batch, batch.hip): per-problem block inverses, log-det parts, reductions, info words and the
+    // theta table (fvgp_hip_loglik_batch_workspace_bytes), and the host staging of the table / the results
+    char *bat_ws = nullptr; size_t bat_cap = 0;
+    std::vector<double> bat_tab_host;
+    std::vector<char> bat_out_host;
 };
 constexpr int RED_SLOTS = 4096;
 
@@ -265,6 +270,16 @@ int launch_transpose(fvgp_handle *h, const double *src, int64_t lds, double *dst
 int launch_transpose_lower_tiles(fvgp_handle *h, const double *src, int64_t lds, double *dst, int64_t ldd, int64_t np);
 int launch_trace_dot(fvgp_handle *h, const double *W, int64_t ldw, const double *D, int64_t ldd, const double *b, int64_t ldb, int64_t n,
                      double *partial, int *nblocks);
+
+// batched evaluation (batch.hip): every launch covers B problems, problem b at base + b * stride
+int launch_kmat_batch(fvgp_handle *h, int kind, const double *x, int64_t n, int d, const double *tab, const double *vdiag, int64_t vd_stride,
+                      double *KV, int64_t ld, int64_t kv_stride, int64_t dim, int64_t B);
+int launch_rhs_rows_batch(fvgp_handle *h, double *KV, int64_t kv_stride, int64_t n, int64_t ld, const double *ymean, int64_t ym_stride, int ncol,
+                          const double *vdiag, int64_t vd_stride, int64_t B);
+int launch_leaf_batch(fvgp_handle *h, double *A, int64_t lda, int64_t a_stride, double *linv, double *logdet_part, int64_t logdet_stride,
+                      int *info, int info_base, int nvalid, int64_t B);
+int launch_loglik_tail_batch(fvgp_handle *h, const double *v, int64_t dim, const double *KV, int64_t kv_stride, int64_t ld, int64_t n, int ncol,
+                             double *out, int64_t B);
 
 int ensure_linv(fvgp_handle *h, const double *L, int64_t n, int64_t ldl);
 int ensure_scratch(fvgp_handle *h, int64_t np);

@@ -15,12 +15,9 @@
 // The same file holds the fused gradient kernel: sum_jk W_jk dK_jk/dtheta_i evaluated on
 // the fly from x, replacing the (H,N,N) dK_dH tensor and the batched LU solve of
 // gp_marginal_likelihood.py:260-274.
-#include "common.h"
+#include "radial.h"
 
 namespace {
-
-constexpr double SQRT3 = 1.7320508075688772935;
-constexpr double SQRT5 = 2.2360679774997896964;
 
 struct KArgs {
     const double *x1; const double *x2; const double *vdiag; double *K;
@@ -29,58 +26,6 @@ struct KArgs {
     double sig;
     double invl[FVGP_MAX_DIM];
 };
-
-// exp(-a) for a >= 0, a streaming kernel's version: Cody-Waite reduction a = n ln2 + r, |r| <= ln2 / 2, a degree-12 polynomial for
-// exp(-r) (max. relative error 2e-17 of the polynomial, below 1 ulp with the rounding of the Horner steps), the scaling by one
-// v_ldexp_f64 (which flushes through the subnormals to 0 by itself: no range checks).  17 fp64 operations, no comparison, no
-// select (the library call carries four of each for arguments that cannot occur here).
-__device__ __forceinline__ double exp_neg(const double a0) {
-    // beyond 800 the result is 0 whatever the argument (+inf included: the reduction below would make inf - inf of it); a NaN
-    // fails the comparison and stays a NaN, as numpy's exp leaves it (kernels.py:16-33)
-    const double a = a0 > 800.0 ? 800.0 : a0;
-    const double n = __builtin_rint(a * 1.4426950408889634074);          // a / ln 2
-    double r = fma(n, -6.93147180369123816490e-01, a);                    // ln2 in two pieces: r = a - n ln2, exact product
-    r = fma(n, -1.90821492927058770002e-10, r);
-    const double x = -r;
-    double p = 2.08767569878680989792e-09;                                // 1 / 12!
-    p = fma(p, x, 2.50521083854417187751e-08);
-    p = fma(p, x, 2.75573192239858906526e-07);
-    p = fma(p, x, 2.75573192239858906526e-06);
-    p = fma(p, x, 2.48015873015873015873e-05);
-    p = fma(p, x, 1.98412698412698412698e-04);
-    p = fma(p, x, 1.38888888888888888889e-03);
-    p = fma(p, x, 8.33333333333333333333e-03);
-    p = fma(p, x, 4.16666666666666666667e-02);
-    p = fma(p, x, 1.66666666666666666667e-01);
-    p = fma(p, x, 0.5);
-    p = fma(p, x, 1.0);
-    p = fma(p, x, 1.0);
-    return __builtin_ldexp(p, -(int)n);
-}
-
-// sqrt(x) for x >= 0 from the hardware reciprocal square root: one coupled Newton (Goldschmidt) step on g ~ sqrt(x), h ~ 1 / (2 sqrt(x))
-// and one correction of g (the library's sqrt rescales for subnormal arguments, classifies its input and corrects twice: squared
-// scaled distances need none of it).  x is first raised to 1e-300, so the diagonal (x = 0) gives 1e-150, which every radial function
-// here maps to the same bits as 0.
-__device__ __forceinline__ double sqrt_pos(const double x0) {
-    const double x = x0 < 1e-300 ? 1e-300 : x0;          // (not fmax: a NaN distance stays a NaN, kernels.py:461-481)
-    const double y = __builtin_amdgcn_rsq(x);
-    double g = x * y, h = 0.5 * y;
-    const double r = fma(-h, g, 0.5);
-    g = fma(g, r, g);
-    h = fma(h, r, h);
-    const double d = fma(-g, g, x);
-    return fma(d, h, g);
-}
-
-template <int KIND>
-__device__ __forceinline__ double radial(double r2, double sig) {
-    if (KIND == 0) return sig * exp_neg(0.5 * r2);
-    const double r = sqrt_pos(r2);
-    if (KIND == 1) { const double a = SQRT3 * r; return sig * (1.0 + a) * exp_neg(a); }
-    const double a = SQRT5 * r;
-    return sig * fma(5.0 / 3.0, r2, 1.0 + a) * exp_neg(a);
-}
 
 template <int KIND, int D>   // D == 0: runtime dimension (<= FVGP_MAX_DIM)
 __global__ __launch_bounds__(256) void kmat_kernel(KArgs a) {

@@ -28,6 +28,16 @@ from .device import default_handle
 from .gp_lin_alg import NonPositiveDefiniteError, _non_pd_message
 from .gp_validation import ValidationMixin
 
+# device-memory budget of the B squares one batched evaluation factors at once (GP.log_likelihood_batch; args["batch_max_bytes"]
+# overrides it per GP): a larger population goes in chunks, with the same results (fvgp_hip_loglik_batch: batch-independent bits)
+BATCH_MAX_BYTES = 8 << 30
+
+
+def _batch_chunks(B, per_problem_bytes, budget):
+    """[start, stop) ranges covering problems 0 .. B-1 once, in order, each of as many problems as fit `budget` bytes (at least one)"""
+    k = max(1, int(budget) // max(1, int(per_problem_bytes)))
+    return [(s, min(int(B), s + k)) for s in range(0, int(B), k)]
+
 
 class GP(ValidationMixin):
     def __init__(
@@ -559,6 +569,73 @@ class GP(ValidationMixin):
 
     def neg_log_likelihood(self, hyperparameters=None):
         return -self.log_likelihood(hyperparameters=hyperparameters)
+
+    def log_likelihood_batch(self, hyperparameters):
+        """log_likelihood at each row of `hyperparameters` (B, ntheta): exactly [self.log_likelihood(t) for t in hyperparameters] --
+        no state is touched, the first non-positive-definite row raises what log_likelihood raises for it -- as one batched device
+        evaluation per chunk (fvgp_hip_loglik_batch) wherever log_likelihood takes the fused path: built-in kernel, vector noise > 0,
+        ncol <= 8, no linalg_mode callables, not sharded, loglik_dim(n, ncol) <= 4096.  Other configurations (and rows whose noise
+        is not such a vector) are evaluated one by one.  Chunks hold as many squares as fit args["batch_max_bytes"] (default
+        BATCH_MAX_BYTES); the results do not depend on the chunking."""
+        hp = np.asarray(hyperparameters, dtype=np.float64)
+        if hp.ndim != 2:
+            raise ValueError(f"log_likelihood_batch takes a (B, ntheta) array, got shape {hp.shape}")
+        B, n, ncol = len(hp), self.point_number, self.y_data.shape[1]
+        out = np.empty(B, dtype=np.float64)
+        dim = _lib.loglik_batch_dim(n, ncol) if ncol <= _lib.MAX_RHS_VEC else 0
+        if (self._native is None or self._sharded or self._linalg_callables is not None or dim == 0) or B == 0:
+            for b in range(B):
+                out[b] = self.log_likelihood(hyperparameters[b])
+            return out
+        H, kid = self._H, self._native.kernel_id
+        shared = self._mean_callable is None and self._noise_callable is None      # m and V do not depend on theta: uploaded once
+
+        def targets(t):
+            m, V = self._mean(self.x_data, t), self._noise(self.x_data, t)
+            ok = np.ndim(V) == 1 and float(np.min(V)) > 0.0                        # what the fused single evaluation needs
+            return ok, (np.ascontiguousarray(V, dtype=np.float64), self.y_data - m[:, None]) if ok else None
+        if shared:
+            ok0, tg0 = targets(hp[0])
+            if not ok0:
+                for b in range(B):
+                    out[b] = self.log_likelihood(hyperparameters[b])
+                return out
+            vd_sh, ym_sh = H.to_device(tg0[0]), H.to_device(tg0[1])
+        res = [None] * B                       # (ll, info, min V) per natively evaluated row; None: one by one
+        budget = self.args.get("batch_max_bytes", BATCH_MAX_BYTES)
+        for s, e in _batch_chunks(B, dim * dim * 8, budget):
+            if shared:
+                idx, vd, ym = list(range(s, e)), vd_sh, ym_sh
+                vmin = [float(np.min(tg0[0]))] * (e - s)
+            else:
+                idx, Vs, Ys = [], [], []
+                for b in range(s, e):
+                    ok, tg = targets(hp[b])
+                    if ok:
+                        idx.append(b); Vs.append(tg[0]); Ys.append(tg[1])
+                if not idx:
+                    continue
+                vd, ym = H.to_device(np.stack(Vs)), H.to_device(np.stack(Ys))
+                vmin = [float(np.min(v)) for v in Vs]
+            KV = H.empty(len(idx), dim, dim)
+            o, info = H.loglik_batch(kid, self._x_dev, hp[idx], vd, ym, KV)
+            del KV
+            for j, b in enumerate(idx):
+                res[b] = (float(o[j, 0]), int(info[j]), vmin[j])
+        for b in range(B):
+            if res[b] is None:
+                out[b] = self.log_likelihood(hyperparameters[b])
+                continue
+            ll, info, vmin = res[b]
+            if info != 0:
+                e = NonPositiveDefiniteError(_non_pd_message(n, info, vmin, 0.0))
+                raise Exception(f"Linear algebra failed for hyperparameters {hyperparameters[b]}: {e}") from e
+            out[b] = ll
+        return out
+
+    def neg_log_likelihood_batch(self, hyperparameters):
+        """-log_likelihood_batch(hyperparameters): the objective of a vectorised population-based optimiser"""
+        return -self.log_likelihood_batch(hyperparameters)
 
     def _check_sharded_gradient(self):
         """The row-sharded gradient re-evaluates dK/dtheta inside its trace kernel: with a kernel callable there is no device

@@ -230,6 +230,9 @@ def train(gp, bounds, init_hyperparameters, method="mcmc", pop_size=20, toleranc
         raise Exception("init_hyperparameters and hyperparameter_bounds have different lengths")
     if not _in_bounds(init_hyperparameters, bounds):
         raise Exception("Starting positions outside of optimization bounds.", init_hyperparameters, bounds)
+    # GP(..., args={"batch_population": True}): 'global' scores each generation's population in ONE batched evaluation
+    # (GP.neg_log_likelihood_batch); a user objective is never vectorised
+    batch_population = (objective_function is None and method == "global" and bool(getattr(gp, "args", {}).get("batch_population", False)))
     if objective_function is None and method in ("mcmc", "global", "local", "adam"):
         objective_function = gp.log_likelihood if method == "mcmc" else gp.neg_log_likelihood
     if objective_function_gradient is None and method in ("local", "adam"):
@@ -246,9 +249,15 @@ def train(gp, bounds, init_hyperparameters, method="mcmc", pop_size=20, toleranc
         hps = res["median(x)"]
     elif method == "global":
         from scipy.optimize import differential_evolution
-        res = differential_evolution(objective_function, bounds, maxiter=max_iter, popsize=pop_size, tol=tolerance,
-                                     disp=info, polish=False, x0=init_hyperparameters.reshape(1, -1),
-                                     constraints=constraints, workers=1, seed=seed)
+        if batch_population:
+            # vectorized: the objective gets the (ntheta, S) trial population; deferred updating scores a generation at once
+            res = differential_evolution(lambda X: gp.neg_log_likelihood_batch(X.T), bounds, maxiter=max_iter, popsize=pop_size,
+                                         tol=tolerance, disp=info, polish=False, x0=init_hyperparameters.reshape(1, -1),
+                                         constraints=constraints, workers=1, seed=seed, vectorized=True, updating="deferred")
+        else:
+            res = differential_evolution(objective_function, bounds, maxiter=max_iter, popsize=pop_size, tol=tolerance,
+                                         disp=info, polish=False, x0=init_hyperparameters.reshape(1, -1),
+                                         constraints=constraints, workers=1, seed=seed)
         hps = np.array(res["x"])
     elif method == "local":
         from scipy.optimize import minimize

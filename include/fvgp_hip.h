@@ -53,6 +53,7 @@ enum fvgp_uplo { FVGP_FULL = 0, FVGP_LOWER = 1 };
 #define FVGP_MAX_DIM 16     /* input dimension limit of the assembly kernels */
 #define FVGP_MAX_RHS_VEC 8  /* potrs switches from the GEMV path to the GEMM path above this */
 #define FVGP_CHAIN_MAX_BLOCKS 32   /* widest panel (in 128-column blocks) the resident panel kernel takes; wider ones use the launch-per-step chain */
+#define FVGP_BATCH_MAX_DIM 4096    /* largest per-problem square the batched evaluation takes (32 block columns) */
 
 int fvgp_hip_version(void);
 const char *fvgp_hip_last_error_string(void);
@@ -309,6 +310,34 @@ int fvgp_hip_loglik_rows(fvgp_handle *h, int kernel_id, const double *x, int64_t
                          const double *theta_host, int ntheta, const double *vdiag,
                          const double *ymean, int ncol, double *KV, int64_t kv_rows, int64_t ld,
                          double *alpha, double *out_host, int *info_host);
+
+/* loglik_batch: GPMarginalLikelihood.log_likelihood (gp_marginal_likelihood.py:137-179) at B hyperparameter vectors on the same
+ * resident x, in one call -- the objective of a population-based optimiser (differential_evolution scores a whole population per
+ * generation: fvgp/gp_training.py:66-76) or of a grid scan.  B independent factorisations side by side fill the chip where one at
+ * training sizes cannot (csrc/batch.hip: per 128 columns a leaf and a panel-TRSM launch, trailing updates between halves of a
+ * recursive halving over the block columns, every launch over all B problems).
+ *   thetas_host   B x ntheta, row-major, host
+ *   vdiag         n noise variances per problem (all > 0); problem b reads vdiag + b * vdiag_stride (0 = shared by all)
+ *   ymean         (n, ncol) per problem = y - m(theta_b); problem b reads ymean + b * ymean_stride (0 = shared)
+ *   KV            caller-owned scratch: problem b's square at KV + b * kv_stride, fvgp_hip_loglik_batch_dim(n, ncol) rows at leading
+ *                 dimension ld (ld even, kv_stride even and >= dim * ld when B > 1, KV 16-byte aligned); contents on return unspecified;
+ *                 nothing outside the B dim x dim squares is touched; the strict upper triangle of each square is never read
+ *   out_host      B x 3: {log-likelihood, log|KV|, (y-m)^T KV^-1 (y-m) / ncol}, NaN for a problem whose factorisation failed
+ *   info_host     B dpotrf info words (0, or the order of the first non-positive leading minor); may be NULL
+ * Errors (argument numbers): -4 n past FVGP_BATCH_MAX_DIM (or fvgp_hip_loglik_batch_dim(n, ncol) == 0), -13 ncol outside 1..8
+ * (FVGP_MAX_RHS_VEC), -8 B < 1.  Returns 0 even when some problems are not positive definite (their info says so).  One host
+ * synchronisation per call.  Problem b's results are bitwise the same whatever B is, whatever position b holds and whatever else is in
+ * the batch (kernel variants depend on the per-problem shape only, per-problem fixed-order reductions, no split K); they agree with
+ * fvgp_hip_loglik to rounding (another schedule of the same factorisation). */
+int fvgp_hip_loglik_batch(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
+                          const double *thetas_host, int ntheta, int64_t B,
+                          const double *vdiag, int64_t vdiag_stride, const double *ymean, int64_t ymean_stride, int ncol,
+                          double *KV, int64_t ld, int64_t kv_stride, double *out_host, int *info_host);
+/* rows = columns of ONE problem's square in the batched scratch: fvgp_hip_loglik_dim(n, ncol); 0 when that exceeds FVGP_BATCH_MAX_DIM */
+int64_t fvgp_hip_loglik_batch_dim(int64_t n, int ncol);
+/* device bytes the HANDLE allocates for a batch of B problems (the block inverse of the current step, reciprocal pivots, the theta
+ * table, reductions and info word per problem); -1 for invalid arguments */
+int64_t fvgp_hip_loglik_batch_workspace_bytes(int64_t n, int ncol, int64_t B);
 
 /* loglik_grad: GPMarginalLikelihood.neg_log_likelihood_gradient  gp_marginal_likelihood.py:224-309
  *   g_i = 1/2 sum_jk (KVinv_jk - b_j b_k) dK_jk/dtheta_i,  b = KVinvY[:,component];
