@@ -32,6 +32,7 @@ SYMBOLS = [
     "fvgp_hip_all_gather", "fvgp_hip_comm_profile", "fvgp_hip_dist_workspace", "fvgp_hip_loglik_dist", "fvgp_hip_dist_scratch", "fvgp_hip_solve_dist",
     "fvgp_hip_posterior_dist", "fvgp_hip_grad_dist", "fvgp_hip_loglik_rows", "fvgp_hip_get_profile_ex", "fvgp_hip_comm_info", "fvgp_hip_comm_check", "fvgp_hip_posterior_prepare",
     "fvgp_hip_loglik_batch", "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes",
+    "fvgp_hip_loglik_grad_batch", "fvgp_hip_loglik_grad_batch_workspace_bytes",
 ]
 BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
 
@@ -209,6 +210,10 @@ def lib():
     L.fvgp_hip_loglik_batch_dim.restype = c_l
     L.fvgp_hip_loglik_batch_workspace_bytes.argtypes = [c_l, c_i, c_l]
     L.fvgp_hip_loglik_batch_workspace_bytes.restype = c_l
+    L.fvgp_hip_loglik_grad_batch.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_l, c_p, c_l, c_p, c_l, c_i, c_i, c_p, c_l, c_l,
+                                             c_p, c_l, c_l, P_d, P_d, P_i, c_p, c_p]
+    L.fvgp_hip_loglik_grad_batch_workspace_bytes.argtypes = [c_l, c_i, c_l]
+    L.fvgp_hip_loglik_grad_batch_workspace_bytes.restype = c_l
     L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
     L.fvgp_hip_grad_trace.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, P_d]
     L.fvgp_hip_posterior.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_p, c_l,
@@ -238,7 +243,7 @@ def lib():
     bind_dist(L)
     for s in SYMBOLS:
         if s not in ("fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_workspace_bytes", "fvgp_hip_dist_scratch",
-                     "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes"):
+                     "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes", "fvgp_hip_loglik_grad_batch_workspace_bytes"):
             getattr(L, s).restype = c_i
     _lib = L
     return L
@@ -454,6 +459,39 @@ class Handle(DistCalls):
                                            _ptr(KV), KV.stride(1), KV.stride(0), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                            info.ctypes.data_as(ctypes.POINTER(ctypes.c_int))), "fvgp_hip_loglik_batch")
         return out, info
+
+    def loglik_grad_batch(self, kernel_id, x, thetas, vdiag, ymean, KV, work, component=0, b_out=None, diag_out=None):
+        """fvgp_hip_loglik_grad_batch: loglik_batch's values and the kernel-owned gradient at the B rows of `thetas` in one call.
+        vdiag / ymean / KV as loglik_batch; work: (B, rows, ldw) second device scratch, rows >= pad128(n).  b_out / diag_out: optional
+        (B, n) device tensors for b = KV^-1 (y - m)[:, component] and diag(KV^-1).  Returns (out (B, 3), grad (B, ntheta), info (B,)):
+        NaN rows where the factorisation failed."""
+        t = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+        if t.ndim != 2:
+            raise ValueError("loglik_grad_batch: thetas must be (B, ntheta)")
+        B, nt = t.shape
+        n, d = x.shape
+        vd = vdiag.reshape(1, n) if vdiag.dim() == 1 else vdiag
+        ym = ymean.reshape(1, *ymean.shape) if ymean.dim() == 2 else ymean
+        ncol = ym.shape[2]
+        for name, a in (("vdiag", vd), ("ymean", ym)):
+            if a.shape[0] not in (1, B) or not a.is_contiguous():
+                raise ValueError(f"loglik_grad_batch: {name} must be contiguous with a leading dimension of 1 or B = {B}, got {tuple(a.shape)}")
+        for name, a in (("KV", KV), ("work", work)):
+            if a.dim() != 3 or a.stride(2) != 1 or (B > 1 and a.shape[0] < B):
+                raise ValueError(f"loglik_grad_batch: {name} must be a (B, rows, ld) tensor with unit column stride, got {tuple(a.shape)}")
+        for name, a in (("b_out", b_out), ("diag_out", diag_out)):
+            if a is not None and (not a.is_contiguous() or a.numel() < B * n):
+                raise ValueError(f"loglik_grad_batch: {name} must be a contiguous (B, n) tensor, got {tuple(a.shape)}")
+        out = np.empty((B, 3), dtype=np.float64)
+        grad = np.empty((B, nt), dtype=np.float64)
+        info = np.zeros(B, dtype=np.int32)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _check(lib().fvgp_hip_loglik_grad_batch(self._h, int(kernel_id), _ptr(x), n, d, t.ctypes.data_as(dp), nt, B,
+                                                _ptr(vd), n if vd.shape[0] > 1 else 0, _ptr(ym), n * ncol if ym.shape[0] > 1 else 0, ncol,
+                                                int(component), _ptr(KV), KV.stride(1), KV.stride(0), _ptr(work), work.stride(1), work.stride(0),
+                                                out.ctypes.data_as(dp), grad.ctypes.data_as(dp), info.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                _ptr(b_out), _ptr(diag_out)), "fvgp_hip_loglik_grad_batch")
+        return out, grad, info
 
     def loglik_grad(self, kernel_id, x, theta, alpha, ncol, component, KV, work):
         t, tp, nt = _theta(theta)

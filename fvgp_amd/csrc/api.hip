@@ -58,6 +58,16 @@ int64_t fvgp_hip_loglik_batch_workspace_bytes(int64_t n, int ncol, int64_t B) {
     return B * (LEAF_DOUBLES + dim + (1 + FVGP_MAX_DIM) + 2) * (int64_t)sizeof(double) + B * (int64_t)sizeof(int);
 }
 
+// per problem: every leaf's block inverse (dim / 128 of them), the reciprocal pivots, the theta table row, z and b (2 padded_dim(n)),
+// the trace's partial sums (T (T + 1) / 2 tiles x (1 + FVGP_MAX_DIM), T = padded_dim(n) / 128), two reductions, the gradient row, the
+// info word (fvgp_hip_loglik_grad_batch's layout, in this order)
+int64_t fvgp_hip_loglik_grad_batch_workspace_bytes(int64_t n, int ncol, int64_t B) {
+    const int64_t dim = fvgp_hip_loglik_batch_dim(n, ncol);
+    if (dim <= 0 || B < 1) return -1;
+    const int64_t np = pad128(n), T = np / TILE, TW = 1 + FVGP_MAX_DIM;
+    return B * ((dim / TILE) * LEAF_DOUBLES + dim + TW + 2 * np + T * (T + 1) / 2 * TW + 2 + TW) * (int64_t)sizeof(double) + B * (int64_t)sizeof(int);
+}
+
 int fvgp_hip_create(fvgp_handle **out, int device, void *stream) {
     if (!out) return -1;
     int ndev = 0;
@@ -1287,10 +1297,91 @@ int fvgp_hip_loglik_rows(fvgp_handle *h, int kernel_id, const double *x, int64_t
     return 0;
 }
 
+// sigma^2 and 1 / l of every problem, exactly as the single evaluation computes them (kmat_desc_from_theta), into the device table `tab`
+// (B rows of 1 + FVGP_MAX_DIM); argument errors numbered as in fvgp_hip_loglik_batch
+static int batch_theta_table(fvgp_handle *h, int kernel_id, int d, const double *thetas, int ntheta, int64_t B, double *tab) {
+    constexpr int TW = 1 + FVGP_MAX_DIM;
+    h->bat_tab_host.assign((size_t)(B * TW), 0.0);
+    for (int64_t b = 0; b < B; ++b) {
+        KmatDesc kd{};
+        const int rc = kmat_desc_from_theta(kernel_id, d, thetas + b * ntheta, ntheta, &kd); if (rc) return rc == -7 ? -5 : rc == -9 ? -7 : rc;
+        h->bat_tab_host[(size_t)(b * TW)] = kd.sig;
+        for (int q = 0; q < d; ++q) h->bat_tab_host[(size_t)(b * TW + 1 + q)] = kd.invl[q];
+    }
+    HIPCHK(hipMemcpyAsync(tab, h->bat_tab_host.data(), (size_t)(B * TW) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+static int batch_workspace(fvgp_handle *h, size_t ws) {
+    if (ws > h->bat_cap) {
+        if (h->bat_ws) HIPCHK(hipFree(h->bat_ws));
+        h->bat_ws = nullptr; h->bat_cap = 0;
+        HIPCHK(hipMalloc((void **)&h->bat_ws, ws));
+        h->bat_cap = ws;
+    }
+    return 0;
+}
+
+// the batched evaluation of Bs problems whose squares start at K0 (stride apart; stride 0 for one): assembly, appended rows, the
+// factorisation by recursive halving, tail -> red (2 per problem).  The leaf of block column k0 of problem b writes its block inverse to
+// linv + b * linv_stride + (k0 / 128) * leaf_step (leaf_step 0: one slot per problem, overwritten step by step).  Every GEMM carries an
+// explicit K range, so that it takes the 128-tile kernel whatever Bs is (a plain one-problem launch of a few tiles would take the
+// 64-tile kernel: other bits).
+static int batch_factor(fvgp_handle *h, int kind, const double *x, int64_t n, int d, const double *tab, const double *vdiag, int64_t vdiag_stride,
+                        const double *ymean, int64_t ymean_stride, int ncol, double *K0, int64_t ld, int64_t stride, int64_t dim,
+                        double *linv, int64_t linv_stride, int64_t leaf_step, double *logdet, int *info, double *red, int64_t Bs) {
+    int rc = launch_kmat_batch(h, kind, x, n, d, tab, vdiag, vdiag_stride, K0, ld, stride, dim, Bs); if (rc) return rc;
+    rc = launch_rhs_rows_batch(h, K0, stride, n, ld, ymean, ymean_stride, ncol, vdiag, vdiag_stride, Bs); if (rc) return rc;
+    // one 128-column step: leaf, then the TRSM of every row below by the block inverse
+    auto step = [&](int64_t k0) -> int {
+        const int64_t nv = n - k0, r0 = k0 + TILE, R = dim - r0;
+        double *li = linv + (k0 / TILE) * leaf_step;
+        int r = launch_leaf_batch(h, K0 + k0 * ld + k0, ld, stride, li, logdet + k0, dim, info, (int)k0,
+                                  nv >= TILE ? TILE : (nv > 0 ? (int)nv : 0), Bs, linv_stride);
+        if (r || R <= 0) return r;
+        GemmDesc t{};          // rows below <- rows below * inv(L_kk)^T, in place
+        t.a_kmajor = 0; t.b_nmajor = 0; t.lower = 0; t.M = R; t.N = TILE; t.K = TILE; t.ke0 = TILE;
+        t.alpha = 1.0; t.beta = 0.0;
+        t.A = K0 + r0 * ld + k0; t.lda = ld; t.B = li; t.ldb = TILE; t.C = K0 + r0 * ld + k0; t.ldc = ld;
+        t.batch_z = (int)Bs; t.a_bz = stride; t.b_bz = linv_stride; t.c_bz = stride;
+        return launch_gemm(h, t);
+    };
+    // recursive halving over the block columns (panel_factor_recursive's order, the whole square one panel): left half, ONE update
+    // of the right half's columns (every row below them, lower tiles) with K = the left half's width, right half.  The same flops
+    // as an update after every 128 columns, with far fewer read-modify-write passes over the trailing tiles.  The schedule
+    // depends on dim only.
+    std::function<int(int64_t, int64_t)> factor = [&](int64_t J0, int64_t Jend) -> int {
+        const int64_t blocks = (Jend - J0) / TILE;
+        if (blocks <= 1) return step(J0);
+        const int64_t mid = J0 + (blocks / 2) * TILE;
+        int r = factor(J0, mid); if (r) return r;
+        GemmDesc u{};          // rows [mid, dim) x columns [mid, Jend) -= L[mid:, J0:mid] L[mid:Jend, J0:mid]^T, lower tiles
+        u.a_kmajor = 0; u.b_nmajor = 0; u.lower = 1; u.M = dim - mid; u.N = Jend - mid; u.K = mid - J0; u.ke0 = mid - J0;
+        u.alpha = -1.0; u.beta = 1.0;
+        u.A = K0 + mid * ld + J0; u.lda = ld; u.B = u.A; u.ldb = ld; u.C = K0 + mid * ld + mid; u.ldc = ld;
+        u.batch_z = (int)Bs; u.a_bz = stride; u.b_bz = stride; u.c_bz = stride;
+        r = launch_gemm(h, u); if (r) return r;
+        return factor(mid, Jend);
+    };
+    rc = factor(0, dim); if (rc) return rc;
+    return launch_loglik_tail_batch(h, logdet, dim, K0, stride, ld, n, ncol, red, Bs);
+}
+
+// {log-likelihood, log|KV|, quad / ncol} of problem b from its two reductions, NaN where info says the factorisation failed
+static void batch_results(int64_t n, int ncol, int64_t B, const double *r, const int *inf, double *out_host, int *info_host) {
+    for (int64_t b = 0; b < B; ++b) {
+        const int ib = inf[b] > n ? 0 : inf[b];        // (cannot exceed n: the padding is an identity block)
+        if (info_host) info_host[b] = ib;
+        if (ib != 0) { out_host[3 * b] = out_host[3 * b + 1] = out_host[3 * b + 2] = NAN; continue; }
+        const double logdet_b = 2.0 * r[2 * b], quad = r[2 * b + 1] / (double)ncol;
+        out_host[3 * b] = -0.5 * (quad + logdet_b + (double)n * log(2.0 * M_PI));
+        out_host[3 * b + 1] = logdet_b;
+        out_host[3 * b + 2] = quad;
+    }
+}
+
 // B independent evaluations side by side (batch.hip): assembly, appended rows, then per 128 columns one leaf launch, one panel TRSM
 // (product with the block inverse) and one update of the trailing lower tiles (K = 128), each over every problem, then one tail.
-// Every GEMM carries an explicit K range, so that it takes the 128-tile kernel whatever B is (a plain one-problem launch of a few
-// tiles would take the 64-tile kernel: other bits).
 int fvgp_hip_loglik_batch(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
                           const double *thetas, int ntheta, int64_t B,
                           const double *vdiag, int64_t vdiag_stride, const double *ymean, int64_t ymean_stride, int ncol,
@@ -1316,71 +1407,23 @@ int fvgp_hip_loglik_batch(fvgp_handle *h, int kernel_id, const double *x, int64_
     if (B > 1 && (kv_stride < dim * ld || (kv_stride & 1))) { fvgp_set_error("loglik_batch: kv_stride must be even and >= dim * ld"); return -16; }
     if (!out_host) return -17;
     HIPCHK(hipSetDevice(h->device));
-    const size_t ws = (size_t)fvgp_hip_loglik_batch_workspace_bytes(n, ncol, B);
-    if (ws > h->bat_cap) {
-        if (h->bat_ws) HIPCHK(hipFree(h->bat_ws));
-        h->bat_ws = nullptr; h->bat_cap = 0;
-        HIPCHK(hipMalloc((void **)&h->bat_ws, ws));
-        h->bat_cap = ws;
-    }
+    rc = batch_workspace(h, (size_t)fvgp_hip_loglik_batch_workspace_bytes(n, ncol, B)); if (rc) return rc;
     constexpr int TW = 1 + FVGP_MAX_DIM;
     double *linv = reinterpret_cast<double *>(h->bat_ws);
     double *logdet = linv + B * LEAF_DOUBLES;
     double *tab = logdet + B * dim;
     double *red = tab + B * TW;
     int *info = reinterpret_cast<int *>(red + 2 * B);
-    // sigma^2 and 1 / l of every problem, exactly as the single evaluation computes them (kmat_desc_from_theta)
-    h->bat_tab_host.assign((size_t)(B * TW), 0.0);
-    for (int64_t b = 0; b < B; ++b) {
-        KmatDesc kd{};
-        rc = kmat_desc_from_theta(kernel_id, d, thetas + b * ntheta, ntheta, &kd); if (rc) return rc == -7 ? -5 : rc == -9 ? -7 : rc;
-        h->bat_tab_host[(size_t)(b * TW)] = kd.sig;
-        for (int q = 0; q < d; ++q) h->bat_tab_host[(size_t)(b * TW + 1 + q)] = kd.invl[q];
-    }
-    HIPCHK(hipMemcpyAsync(tab, h->bat_tab_host.data(), (size_t)(B * TW) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    rc = batch_theta_table(h, kernel_id, d, thetas, ntheta, B, tab); if (rc) return rc;
     HIPCHK(hipMemsetAsync(info, 0, (size_t)B * sizeof(int), h->stream));
-    const int kind = k0d.kind;
     const int64_t stride = B > 1 ? kv_stride : 0;
     // grid dimensions y / z take at most 65535: the problems go in groups of that many (results do not depend on the grouping)
     constexpr int64_t GROUP = 65535;
     for (int64_t b0 = 0; b0 < B; b0 += GROUP) {
         const int64_t Bs = B - b0 < GROUP ? B - b0 : GROUP;
-        double *K0 = KV + b0 * stride;
-        rc = launch_kmat_batch(h, kind, x, n, d, tab + b0 * TW, vdiag + b0 * vdiag_stride, vdiag_stride, K0, ld, stride, dim, Bs); if (rc) return rc;
-        rc = launch_rhs_rows_batch(h, K0, stride, n, ld, ymean + b0 * ymean_stride, ymean_stride, ncol, vdiag + b0 * vdiag_stride, vdiag_stride, Bs);
+        rc = batch_factor(h, k0d.kind, x, n, d, tab + b0 * TW, vdiag + b0 * vdiag_stride, vdiag_stride, ymean + b0 * ymean_stride, ymean_stride, ncol,
+                          KV + b0 * stride, ld, stride, dim, linv + b0 * LEAF_DOUBLES, LEAF_DOUBLES, 0, logdet + b0 * dim, info + b0, red + 2 * b0, Bs);
         if (rc) return rc;
-        // one 128-column step: leaf, then the TRSM of every row below by the block inverse
-        auto step = [&](int64_t k0) -> int {
-            const int64_t nv = n - k0, r0 = k0 + TILE, R = dim - r0;
-            int r = launch_leaf_batch(h, K0 + k0 * ld + k0, ld, stride, linv + b0 * LEAF_DOUBLES, logdet + b0 * dim + k0, dim, info + b0, (int)k0,
-                                      nv >= TILE ? TILE : (nv > 0 ? (int)nv : 0), Bs);
-            if (r || R <= 0) return r;
-            GemmDesc t{};          // rows below <- rows below * inv(L_kk)^T, in place
-            t.a_kmajor = 0; t.b_nmajor = 0; t.lower = 0; t.M = R; t.N = TILE; t.K = TILE; t.ke0 = TILE;
-            t.alpha = 1.0; t.beta = 0.0;
-            t.A = K0 + r0 * ld + k0; t.lda = ld; t.B = linv + b0 * LEAF_DOUBLES; t.ldb = TILE; t.C = K0 + r0 * ld + k0; t.ldc = ld;
-            t.batch_z = (int)Bs; t.a_bz = stride; t.b_bz = LEAF_DOUBLES; t.c_bz = stride;
-            return launch_gemm(h, t);
-        };
-        // recursive halving over the block columns (panel_factor_recursive's order, the whole square one panel): left half, ONE update
-        // of the right half's columns (every row below them, lower tiles) with K = the left half's width, right half.  The same flops
-        // as an update after every 128 columns, with far fewer read-modify-write passes over the trailing tiles.  The schedule
-        // depends on dim only.
-        std::function<int(int64_t, int64_t)> factor = [&](int64_t J0, int64_t Jend) -> int {
-            const int64_t blocks = (Jend - J0) / TILE;
-            if (blocks <= 1) return step(J0);
-            const int64_t mid = J0 + (blocks / 2) * TILE;
-            int r = factor(J0, mid); if (r) return r;
-            GemmDesc u{};          // rows [mid, dim) x columns [mid, Jend) -= L[mid:, J0:mid] L[mid:Jend, J0:mid]^T, lower tiles
-            u.a_kmajor = 0; u.b_nmajor = 0; u.lower = 1; u.M = dim - mid; u.N = Jend - mid; u.K = mid - J0; u.ke0 = mid - J0;
-            u.alpha = -1.0; u.beta = 1.0;
-            u.A = K0 + mid * ld + J0; u.lda = ld; u.B = u.A; u.ldb = ld; u.C = K0 + mid * ld + mid; u.ldc = ld;
-            u.batch_z = (int)Bs; u.a_bz = stride; u.b_bz = stride; u.c_bz = stride;
-            r = launch_gemm(h, u); if (r) return r;
-            return factor(mid, Jend);
-        };
-        rc = factor(0, dim); if (rc) return rc;
-        rc = launch_loglik_tail_batch(h, logdet + b0 * dim, dim, K0, stride, ld, n, ncol, red + 2 * b0, Bs); if (rc) return rc;
     }
     // ONE host round trip: the B reductions and the B info words in one copy
     const size_t rbytes = (size_t)B * (2 * sizeof(double) + sizeof(int));
@@ -1388,15 +1431,121 @@ int fvgp_hip_loglik_batch(fvgp_handle *h, int kernel_id, const double *x, int64_
     HIPCHK(hipMemcpyAsync(h->bat_out_host.data(), red, rbytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     const double *r = reinterpret_cast<const double *>(h->bat_out_host.data());
-    const int *inf = reinterpret_cast<const int *>(r + 2 * B);
+    batch_results(n, ncol, B, r, reinterpret_cast<const int *>(r + 2 * B), out_host, info_host);
+    return 0;
+}
+
+// the value and the kernel-owned gradient at B hyperparameter vectors (grad_batch.hip): the factorisation of fvgp_hip_loglik_batch with
+// every leaf inverse kept, then per problem W = L^-1 (recursive halving), b = W^T z, KV^-1 = W^T W, the fused trace and its per-problem
+// reduction; one host copy of {reductions, gradients, info words} at the end
+int fvgp_hip_loglik_grad_batch(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
+                               const double *thetas, int ntheta, int64_t B,
+                               const double *vdiag, int64_t vdiag_stride, const double *ymean, int64_t ymean_stride,
+                               int ncol, int component,
+                               double *KV, int64_t ld, int64_t kv_stride,
+                               double *work, int64_t ldw, int64_t work_stride,
+                               double *out_host, double *grad_host, int *info_host,
+                               double *b_out, double *diag_out) {
+    if (!h) return -1;
+    if (!x) return -3;
+    if (n <= 0) return -4;
+    if (n > FVGP_BATCH_MAX_DIM) { fvgp_set_error("loglik_grad_batch: n exceeds FVGP_BATCH_MAX_DIM"); return -4; }
+    if (!thetas) return -6;
+    if (B < 1) { fvgp_set_error("loglik_grad_batch: B >= 1"); return -8; }
+    KmatDesc k0d{};
+    int rc = kmat_desc_from_theta(kernel_id, d, thetas, ntheta, &k0d);
+    if (rc) return rc == -7 ? -5 : rc == -9 ? -7 : rc;
+    if (!vdiag) { fvgp_set_error("loglik_grad_batch needs the noise variances (vdiag)"); return -9; }
+    if (vdiag_stride < 0) return -10;
+    if (!ymean) return -11;
+    if (ymean_stride < 0) return -12;
+    if (ncol < 1 || ncol > FVGP_MAX_RHS_VEC) { fvgp_set_error("1 <= ncol <= 8"); return -13; }
+    if (component < 0 || component >= ncol) { fvgp_set_error("loglik_grad_batch: 0 <= component < ncol"); return -14; }
+    const int64_t dim = fvgp_hip_loglik_batch_dim(n, ncol), np = pad128(n);
+    if (dim <= 0) { fvgp_set_error("loglik_grad_batch: fvgp_hip_loglik_batch_dim(n, ncol) exceeds FVGP_BATCH_MAX_DIM"); return -4; }
+    if (!KV || ((uintptr_t)KV & 15)) { fvgp_set_error("loglik_grad_batch: KV must be 16-byte aligned"); return -15; }
+    if (ld < dim || (ld & 1)) { fvgp_set_error("loglik_grad_batch: the leading dimension must be even and >= fvgp_hip_loglik_batch_dim(n, ncol)"); return -16; }
+    if (B > 1 && (kv_stride < dim * ld || (kv_stride & 1))) { fvgp_set_error("loglik_grad_batch: kv_stride must be even and >= dim * ld"); return -17; }
+    if (!work || ((uintptr_t)work & 15)) { fvgp_set_error("loglik_grad_batch: work must be 16-byte aligned"); return -18; }
+    if (ldw < np || (ldw & 1)) { fvgp_set_error("loglik_grad_batch: ldw must be even and >= padded_dim(n)"); return -19; }
+    if (B > 1 && (work_stride < np * ldw || (work_stride & 1))) { fvgp_set_error("loglik_grad_batch: work_stride must be even and >= padded_dim(n) * ldw"); return -20; }
+    if (!out_host) return -21;
+    if (!grad_host) return -22;
+    HIPCHK(hipSetDevice(h->device));
+    rc = batch_workspace(h, (size_t)fvgp_hip_loglik_grad_batch_workspace_bytes(n, ncol, B)); if (rc) return rc;
+    constexpr int TW = 1 + FVGP_MAX_DIM;
+    const int64_t T = np / TILE, ntiles = T * (T + 1) / 2, lstride = (dim / TILE) * LEAF_DOUBLES, zstride = 2 * np, pstride = ntiles * TW;
+    // workspace layout (fvgp_hip_loglik_grad_batch_workspace_bytes): every leaf inverse, reciprocal pivots, theta table, z and b,
+    // partial sums, then {reductions, gradients, info words} -- the block the host copies back
+    double *linv = reinterpret_cast<double *>(h->bat_ws);
+    double *logdet = linv + B * lstride;
+    double *tab = logdet + B * dim;
+    double *zb = tab + B * TW;
+    double *partial = zb + B * zstride;
+    double *red = partial + B * pstride;
+    double *grad = red + 2 * B;
+    int *info = reinterpret_cast<int *>(grad + B * TW);
+    rc = batch_theta_table(h, kernel_id, d, thetas, ntheta, B, tab); if (rc) return rc;
+    HIPCHK(hipMemsetAsync(info, 0, (size_t)B * sizeof(int), h->stream));
+    const int kind = k0d.kind, iso = kernel_id >= 3, nk = iso ? 2 : d + 1;
+    const int64_t stride = B > 1 ? kv_stride : 0, wstride = B > 1 ? work_stride : 0;
+    constexpr int64_t GROUP = 65535;
+    for (int64_t b0 = 0; b0 < B; b0 += GROUP) {
+        const int64_t Bs = B - b0 < GROUP ? B - b0 : GROUP;
+        double *K0 = KV + b0 * stride, *W0 = work + b0 * wstride, *li = linv + b0 * lstride, *z = zb + b0 * zstride;
+        rc = batch_factor(h, kind, x, n, d, tab + b0 * TW, vdiag + b0 * vdiag_stride, vdiag_stride, ymean + b0 * ymean_stride, ymean_stride, ncol,
+                          K0, ld, stride, dim, li, lstride, LEAF_DOUBLES, logdet + b0 * dim, info + b0, red + 2 * b0, Bs);
+        if (rc) return rc;
+        rc = launch_grad_init_batch(h, K0, stride, ld, n, component, li, lstride, z, zstride, Bs); if (rc) return rc;
+        // W = L^-1 over the padded np x np factor, in place, by recursive halving: inv([[A,0],[C,D]]) = [[A^-1,0],[-D^-1 C A^-1, D^-1]]
+        std::function<int(int64_t, int64_t)> invert = [&](int64_t J0, int64_t Jend) -> int {
+            const int64_t blocks = (Jend - J0) / TILE;
+            if (blocks <= 1) return 0;
+            const int64_t mid = J0 + (blocks / 2) * TILE;
+            int r = invert(J0, mid); if (r) return r;
+            r = invert(mid, Jend); if (r) return r;
+            GemmDesc t{};      // X^T = A^-1^T C^T -> work[J0:mid, mid:Jend] (A^-1 read k-major; lower: k >= row tile)
+            t.a_kmajor = 1; t.b_nmajor = 0; t.lower = 0; t.M = mid - J0; t.N = Jend - mid; t.K = mid - J0; t.alpha = 1.0; t.beta = 0.0;
+            t.A = K0 + J0 * ld + J0; t.lda = ld; t.B = K0 + mid * ld + J0; t.ldb = ld; t.C = W0 + J0 * ldw + mid; t.ldc = ldw;
+            t.kb0 = 0; t.kbi = TILE; t.kbj = 0; t.ke0 = mid - J0;
+            t.batch_z = (int)Bs; t.a_bz = stride; t.b_bz = stride; t.c_bz = wstride;
+            r = launch_gemm(h, t); if (r) return r;
+            GemmDesc u{};      // C <- -D^-1 X  (D^-1 lower: k < (row tile + 1) * 128)
+            u.a_kmajor = 0; u.b_nmajor = 0; u.lower = 0; u.M = Jend - mid; u.N = mid - J0; u.K = Jend - mid; u.alpha = -1.0; u.beta = 0.0;
+            u.A = K0 + mid * ld + mid; u.lda = ld; u.B = W0 + J0 * ldw + mid; u.ldb = ldw; u.C = K0 + mid * ld + J0; u.ldc = ld;
+            u.kb0 = 0; u.ke0 = TILE; u.kei = TILE; u.kej = 0;
+            u.batch_z = (int)Bs; u.a_bz = stride; u.b_bz = wstride; u.c_bz = stride;
+            return launch_gemm(h, u);
+        };
+        rc = invert(0, np); if (rc) return rc;
+        rc = launch_wtz_batch(h, K0, stride, ld, n, z, z + np, zstride, Bs); if (rc) return rc;
+        // KV^-1 = W^T W = (W^T)(W^T)^T: W^T into work, the lower tiles of the product over W (k >= row tile)
+        rc = launch_transpose_lower_batch(h, K0, stride, ld, W0, wstride, ldw, np, Bs); if (rc) return rc;
+        GemmDesc s{};
+        s.a_kmajor = 0; s.b_nmajor = 0; s.lower = 1; s.M = np; s.N = np; s.K = np; s.alpha = 1.0; s.beta = 0.0;
+        s.A = W0; s.lda = ldw; s.B = W0; s.ldb = ldw; s.C = K0; s.ldc = ld;
+        s.kb0 = 0; s.kbi = TILE; s.kbj = 0; s.ke0 = np;
+        s.batch_z = (int)Bs; s.a_bz = wstride; s.b_bz = wstride; s.c_bz = stride;
+        rc = launch_gemm(h, s); if (rc) return rc;
+        rc = launch_grad_trace_batch(h, kind, iso, x, n, d, K0, stride, ld, z + np, zstride, tab + b0 * TW, partial + b0 * pstride, pstride, Bs);
+        if (rc) return rc;
+        rc = launch_grad_reduce_batch(h, partial + b0 * pstride, pstride, ntiles, nk, grad + b0 * TW, Bs); if (rc) return rc;
+        if (b_out || diag_out) {
+            rc = launch_grad_outputs_batch(h, z + np, zstride, K0, stride, ld, n, b_out ? b_out + b0 * n : nullptr, diag_out ? diag_out + b0 * n : nullptr, Bs);
+            if (rc) return rc;
+        }
+    }
+    // ONE host round trip: reductions, gradients and info words in one copy
+    const size_t rbytes = (size_t)B * ((2 + TW) * sizeof(double) + sizeof(int));
+    h->bat_out_host.resize(rbytes);
+    HIPCHK(hipMemcpyAsync(h->bat_out_host.data(), red, rbytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const double *r = reinterpret_cast<const double *>(h->bat_out_host.data()), *g = r + 2 * B;
+    const int *inf = reinterpret_cast<const int *>(g + B * TW);
+    batch_results(n, ncol, B, r, inf, out_host, info_host);
     for (int64_t b = 0; b < B; ++b) {
-        const int ib = inf[b] > n ? 0 : inf[b];        // (cannot exceed n: the padding is an identity block)
-        if (info_host) info_host[b] = ib;
-        if (ib != 0) { out_host[3 * b] = out_host[3 * b + 1] = out_host[3 * b + 2] = NAN; continue; }
-        const double logdet_b = 2.0 * r[2 * b], quad = r[2 * b + 1] / (double)ncol;
-        out_host[3 * b] = -0.5 * (quad + logdet_b + (double)n * log(2.0 * M_PI));
-        out_host[3 * b + 1] = logdet_b;
-        out_host[3 * b + 2] = quad;
+        const bool bad = inf[b] != 0 && inf[b] <= n;
+        for (int i = 0; i < ntheta; ++i) grad_host[b * ntheta + i] = bad ? NAN : (i < nk ? g[b * TW + i] : 0.0);
     }
     return 0;
 }

@@ -220,10 +220,10 @@ int launch_rhs_rows_batch(fvgp_handle *h, double *KV, int64_t kv_stride, int64_t
 }
 
 int launch_leaf_batch(fvgp_handle *h, double *A, int64_t lda, int64_t a_stride, double *linv, double *logdet_part, int64_t logdet_stride,
-                      int *info, int info_base, int nvalid, int64_t B) {
+                      int *info, int info_base, int nvalid, int64_t B, int64_t linv_stride) {
     LeafArgs g;
     g.A = A; g.lda = lda; g.linv = linv; g.logdet_part = logdet_part; g.info = info; g.info_base = info_base;
-    g.do_factor = 1; g.a_stride = a_stride; g.linv_stride = LEAF_DOUBLES; g.nvalid = nvalid; g.stamps = nullptr;
+    g.do_factor = 1; g.a_stride = a_stride; g.linv_stride = linv_stride; g.nvalid = nvalid; g.stamps = nullptr;
     g.tiles_only = 0; g.preloaded = 0; g.yield = nullptr; g.col_flag = nullptr; g.col_base = 0;
     hipLaunchKernelGGL(leaf_batch_kernel, dim3((unsigned)B), dim3(512), 0, h->stream, g, (long)logdet_stride);
     HIPCHK(hipGetLastError());

@@ -277,9 +277,21 @@ int launch_kmat_batch(fvgp_handle *h, int kind, const double *x, int64_t n, int 
 int launch_rhs_rows_batch(fvgp_handle *h, double *KV, int64_t kv_stride, int64_t n, int64_t ld, const double *ymean, int64_t ym_stride, int ncol,
                           const double *vdiag, int64_t vd_stride, int64_t B);
 int launch_leaf_batch(fvgp_handle *h, double *A, int64_t lda, int64_t a_stride, double *linv, double *logdet_part, int64_t logdet_stride,
-                      int *info, int info_base, int nvalid, int64_t B);
+                      int *info, int info_base, int nvalid, int64_t B, int64_t linv_stride = LEAF_DOUBLES);
 int launch_loglik_tail_batch(fvgp_handle *h, const double *v, int64_t dim, const double *KV, int64_t kv_stride, int64_t ld, int64_t n, int ncol,
                              double *out, int64_t B);
+// batched gradient (grad_batch.hip)
+int launch_grad_init_batch(fvgp_handle *h, double *KV, int64_t kv_stride, int64_t ld, int64_t n, int component, const double *linv,
+                           int64_t linv_stride, double *z, int64_t z_stride, int64_t B);
+int launch_wtz_batch(fvgp_handle *h, const double *KV, int64_t kv_stride, int64_t ld, int64_t n, const double *z, double *bv, int64_t z_stride,
+                     int64_t B);
+int launch_transpose_lower_batch(fvgp_handle *h, const double *src, int64_t s_stride, int64_t lds, double *dst, int64_t d_stride, int64_t ldd,
+                                 int64_t np, int64_t B);
+int launch_grad_trace_batch(fvgp_handle *h, int kind, int iso, const double *x, int64_t n, int d, const double *W, int64_t w_stride, int64_t ldw,
+                            const double *b, int64_t b_stride, const double *tab, double *partial, int64_t p_stride, int64_t B);
+int launch_grad_reduce_batch(fvgp_handle *h, const double *partial, int64_t p_stride, int64_t ntiles, int nk, double *grad, int64_t B);
+int launch_grad_outputs_batch(fvgp_handle *h, const double *bv, int64_t bv_stride, const double *KV, int64_t kv_stride, int64_t ld, int64_t n,
+                              double *b_out, double *diag_out, int64_t B);
 
 int ensure_linv(fvgp_handle *h, const double *L, int64_t n, int64_t ldl);
 int ensure_scratch(fvgp_handle *h, int64_t np);

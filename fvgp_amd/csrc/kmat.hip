@@ -145,16 +145,6 @@ struct GArgs {
     long wcol0;               //   matrix column wcol0); grid = (tile rows, ntj)
 };
 
-// phi and the common factor cf such that dK/dl_k = cf * e2[k] * invl[k]  (e2 = D^2 / l^2), one exp and one square root per entry
-template <int KIND>
-__device__ __forceinline__ void radial_grad(const double r2, const double sig, double &phi, double &cf) {
-    if (KIND == 0) { phi = exp_neg(0.5 * r2); cf = sig * phi; return; }
-    const double r = sqrt_pos(r2);
-    if (KIND == 1) { const double ea = exp_neg(SQRT3 * r); phi = fma(SQRT3, r, 1.0) * ea; cf = 3.0 * sig * ea; return; }
-    const double ea = exp_neg(SQRT5 * r), t = fma(SQRT5, r, 1.0);
-    phi = fma(5.0 / 3.0, r2, t) * ea; cf = (5.0 / 3.0) * sig * t * ea;
-}
-
 template <int KIND, int D>   // D == 0: runtime dimension (<= FVGP_MAX_DIM); a 16-deep predicated loop per entry made d = 3 run at a tenth of the memory rate
 __global__ __launch_bounds__(256) void grad_trace_kernel(GArgs a) {
     int ti, tj;

@@ -637,6 +637,80 @@ class GP(ValidationMixin):
         """-log_likelihood_batch(hyperparameters): the objective of a vectorised population-based optimiser"""
         return -self.log_likelihood_batch(hyperparameters)
 
+    def neg_log_likelihood_gradient_batch(self, hyperparameters, component=0):
+        """neg_log_likelihood_gradient at each row of `hyperparameters` (B, ntheta): [self.neg_log_likelihood_gradient(t, component)
+        for t in hyperparameters] -- no state is touched, the first non-positive-definite row raises what the single call raises for it
+        -- as one batched device call per chunk (fvgp_hip_loglik_grad_batch) wherever the single gradient calls Handle.loglik_grad on the
+        fused evaluation: built-in kernel, not sharded, vector noise > 0, loglik_batch_dim(n, ncol) > 0.  Diagonal noise and mean
+        hyperparameters are added on the host from b and diag(KV^-1) as the single path adds them; kernel callables, matrix-valued noise
+        or noise derivatives and sharded GPs are evaluated one by one.  Chunks hold as many pairs of squares as fit
+        args["batch_max_bytes"] (default BATCH_MAX_BYTES); the results do not depend on the chunking."""
+        return self._nlml_and_gradient_batch(hyperparameters, component)[1]
+
+    def neg_log_likelihood_and_gradient_batch(self, hyperparameters, component=0):
+        """(neg_log_likelihood (B,), neg_log_likelihood_gradient (B, ntheta)) at the rows of `hyperparameters` from the same batched
+        calls as neg_log_likelihood_gradient_batch: the objective of a vectorised gradient optimiser (multi-start Adam)"""
+        return self._nlml_and_gradient_batch(hyperparameters, component)
+
+    def _nlml_and_gradient_batch(self, hyperparameters, component):
+        hp = np.asarray(hyperparameters, dtype=np.float64)
+        if hp.ndim != 2:
+            raise ValueError(f"the batched gradient takes a (B, ntheta) array, got shape {hp.shape}")
+        B, n, ncol = len(hp), self.point_number, self.y_data.shape[1]
+        f, g = np.empty(B, dtype=np.float64), np.empty(hp.shape, dtype=np.float64)
+        dim = _lib.loglik_batch_dim(n, ncol) if ncol <= _lib.MAX_RHS_VEC else 0
+        res = [None] * B                   # (nlml, grad, info, min V) per natively evaluated row; None: one by one
+        if self._native is not None and not self._sharded and dim > 0 and B > 0:
+            H, kid, npd = self._H, self._native.kernel_id, _lib.pad128(n)
+            noise_fn, mean_fn = self._noise_callable is not None, self._mean_callable is not None
+            budget = self.args.get("batch_max_bytes", BATCH_MAX_BYTES)
+            for s, e in _batch_chunks(B, (dim * dim + npd * npd) * 8, budget):
+                idx, Vs, Ys, dVs = [], [], [], []
+                for b in range(s, e):
+                    m, V = self._mean(self.x_data, hp[b]), self._noise(self.x_data, hp[b])
+                    if not (np.ndim(V) == 1 and float(np.min(V)) > 0.0):
+                        continue
+                    dV = self._noise_grad(hp[b]) if noise_fn else None
+                    if dV is not None and np.ndim(dV) == 3:           # matrix-valued noise derivative: the single path's trace_dot
+                        continue
+                    idx.append(b); Vs.append(np.ascontiguousarray(V, dtype=np.float64)); Ys.append(self.y_data - m[:, None]); dVs.append(dV)
+                if not idx:
+                    continue
+                shared = not noise_fn and not mean_fn                    # m and V do not depend on theta: uploaded once
+                vd = H.to_device(Vs[0] if shared else np.stack(Vs))
+                ym = H.to_device(Ys[0] if shared else np.stack(Ys))
+                KV, W = H.empty(len(idx), dim, dim), H.empty(len(idx), npd, npd)
+                bo = H.empty(len(idx), n) if (noise_fn or mean_fn) else None
+                do = H.empty(len(idx), n) if noise_fn else None
+                o, gr, info = H.loglik_grad_batch(kid, self._x_dev, hp[idx], vd, ym, KV, W, component, bo, do)
+                del KV, W
+                bo_h = bo.cpu().numpy() if bo is not None else None
+                do_h = do.cpu().numpy() if do is not None else None
+                for j, b in enumerate(idx):
+                    gj, bj = gr[j].copy(), None
+                    if info[j] == 0:
+                        # noise-owned hyperparameters (gp_marginal_likelihood.py:262-267) and mean-owned ones (:281,301-308), as
+                        # neg_log_likelihood_gradient adds them
+                        if noise_fn and np.any(dVs[j] != 0.0):
+                            bj = bo_h[j]
+                            gj = gj + 0.5 * (dVs[j] @ (do_h[j] - bj * bj))
+                        if mean_fn:
+                            if bj is None:
+                                bj = bo_h[j]
+                            gm = -(self._mean_grad(hp[b]) @ bj)
+                            gj = np.where(gm == 0.0, gj, 0.0) + gm
+                    res[b] = (-float(o[j, 0]), gj, int(info[j]), float(np.min(Vs[j])))
+        for b in range(B):
+            if res[b] is None:
+                g[b] = self.neg_log_likelihood_gradient(hyperparameters[b], component)
+                f[b] = self.neg_log_likelihood(hyperparameters[b])
+                continue
+            nl, gb, info, vmin = res[b]
+            if info != 0:
+                raise NonPositiveDefiniteError(_non_pd_message(n, info, vmin, 0.0))
+            f[b], g[b] = nl, gb
+        return f, g
+
     def _check_sharded_gradient(self):
         """The row-sharded gradient re-evaluates dK/dtheta inside its trace kernel: with a kernel callable there is no device
         formula, and the reference itself refuses a gradient in its distributed mode (gp_marginal_likelihood.py:240)."""

@@ -218,6 +218,50 @@ def adam_optimize(nlml, grad_nlml, theta0, lr=1e-2, beta1=0.9, beta2=0.999, eps=
     return theta, history
 
 
+def adam_optimize_batch(f_and_g, thetas0, lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8, max_iter=1000, tol=1e-6, callback=None):
+    """S Adam trajectories in lockstep: adam_optimize's update and stop rule per row of `thetas0` (S, p), one call
+    f_and_g(thetas (k, p)) -> (values (k,), gradients (k, p)) per step over the k trajectories still running.  A trajectory whose
+    update is shorter than `tol` takes that last step and freezes; the loop ends when all have frozen or after max_iter steps.
+    Returns (thetas (S, p), [history per trajectory]), each history as adam_optimize keeps it."""
+    thetas = np.array(thetas0, dtype=np.float64, ndmin=2)
+    m, v = np.zeros_like(thetas), np.zeros_like(thetas)
+    histories = [{"theta": [], "nlml": [], "grad_norm": []} for _ in range(len(thetas))]
+    active = np.ones(len(thetas), dtype=bool)
+    for t in range(1, int(max_iter) + 1):
+        idx = np.flatnonzero(active)
+        if idx.size == 0:
+            break
+        fvals, G = f_and_g(thetas[idx].copy())
+        G = np.asarray(G, dtype=np.float64).reshape(len(idx), thetas.shape[1])
+        m[idx] = beta1 * m[idx] + (1.0 - beta1) * G
+        v[idx] = beta2 * v[idx] + (1.0 - beta2) * (G ** 2)
+        m_hat = m[idx] / (1.0 - beta1 ** t)
+        v_hat = v[idx] / (1.0 - beta2 ** t)
+        new = thetas[idx] - lr * m_hat / (np.sqrt(v_hat) + eps)
+        for j, s in enumerate(idx):
+            h = histories[s]
+            h["theta"].append(thetas[s].copy())
+            h["nlml"].append(fvals[j])
+            h["grad_norm"].append(np.linalg.norm(G[j]))
+            if np.linalg.norm(new[j] - thetas[s]) < tol:
+                active[s] = False
+        thetas[idx] = new
+        if callback is not None:
+            callback(thetas, idx, fvals, G, t)
+    return thetas, histories
+
+
+def adam_start_points(init_hyperparameters, bounds, starts, seed=None):
+    """(starts, p) starting points of a multi-start Adam: row 0 is init_hyperparameters, the others uniform in the bounds from
+    np.random.RandomState(seed) (numpy's global stream when seed is None, as GP.train's redraw)"""
+    rng = np.random if seed is None else np.random.RandomState(seed)
+    x0 = np.empty((int(starts), len(bounds)), dtype=np.float64)
+    x0[0] = init_hyperparameters
+    if starts > 1:
+        x0[1:] = rng.uniform(low=bounds[:, 0], high=bounds[:, 1], size=(int(starts) - 1, len(bounds)))
+    return x0
+
+
 def train(gp, bounds, init_hyperparameters, method="mcmc", pop_size=20, tolerance=1e-4, max_iter=10000,
           local_optimizer="L-BFGS-B", constraints=(), info=False, seed=None, objective_function=None,
           objective_function_gradient=None, objective_function_hessian=None, mcmc_prior=None, mcmc_args=None,
@@ -233,6 +277,11 @@ def train(gp, bounds, init_hyperparameters, method="mcmc", pop_size=20, toleranc
     # GP(..., args={"batch_population": True}): 'global' scores each generation's population in ONE batched evaluation
     # (GP.neg_log_likelihood_batch); a user objective is never vectorised
     batch_population = (objective_function is None and method == "global" and bool(getattr(gp, "args", {}).get("batch_population", False)))
+    # GP(..., args={"adam_starts": S}), S >= 2: 'adam' runs S trajectories in lockstep, one batched value + gradient evaluation per step
+    # (GP.neg_log_likelihood_and_gradient_batch); a user objective is never vectorised
+    adam_starts = 0
+    if objective_function is None and objective_function_gradient is None and method == "adam":
+        adam_starts = int(getattr(gp, "args", {}).get("adam_starts", 0) or 0)
     if objective_function is None and method in ("mcmc", "global", "local", "adam"):
         objective_function = gp.log_likelihood if method == "mcmc" else gp.neg_log_likelihood
     if objective_function_gradient is None and method in ("local", "adam"):
@@ -274,6 +323,19 @@ def train(gp, bounds, init_hyperparameters, method="mcmc", pop_size=20, toleranc
                            jac=objective_function_gradient, hess=objective_function_hessian, bounds=bounds,
                            tol=tolerance, callback=progress, constraints=constraints, options={"maxiter": max_iter})
         hps = res["x"]
+    elif method == "adam" and adam_starts >= 2:
+        x0 = adam_start_points(init_hyperparameters, bounds, adam_starts, seed)
+        progress = None
+        if info:
+            def progress(thetas, idx, fvals, grads, iteration):
+                if iteration % 10 == 0 or iteration == 1:
+                    print(f"fvGP adam iteration {iteration} out of {max_iter}: {len(idx)} trajectories running, min f(x)= {float(np.min(fvals))}")
+        xs, histories = adam_optimize_batch(gp.neg_log_likelihood_and_gradient_batch, x0, max_iter=max_iter, callback=progress)
+        fx = gp.neg_log_likelihood_batch(xs)
+        best = int(np.argmin(np.where(np.isnan(fx), np.inf, fx)))
+        gp.adam_history = histories[best]
+        gp.adam_multistart_info = {"x0": x0, "x": xs, "f(x)": fx, "best": best}
+        hps = xs[best].copy()
     elif method == "adam":
         progress = None
         if info:

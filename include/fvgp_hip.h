@@ -339,6 +339,35 @@ int64_t fvgp_hip_loglik_batch_dim(int64_t n, int ncol);
  * table, reductions and info word per problem); -1 for invalid arguments */
 int64_t fvgp_hip_loglik_batch_workspace_bytes(int64_t n, int ncol, int64_t B);
 
+/* loglik_grad_batch: fvgp_hip_loglik followed by fvgp_hip_loglik_grad at each of B hyperparameter vectors on the same resident x, in
+ * one call -- the step of a multi-start gradient optimiser (csrc/grad_batch.hip: the batched factorisation of fvgp_hip_loglik_batch
+ * with every leaf inverse kept, W = L^-1 by recursive halving, b = W^T z, KV^-1 = W^T W, the fused trace and a per-problem reduction,
+ * every launch over all B problems).  Arguments 1-13 as fvgp_hip_loglik_batch, then:
+ *   component     which column of y - m gives b (0 <= component < ncol), as in fvgp_hip_loglik_grad
+ *   KV, ld, kv_stride    as fvgp_hip_loglik_batch (contents on return: KV^-1 in the lower tiles of the padded_dim(n) square)
+ *   work, ldw, work_stride   a second caller-owned square per problem, padded_dim(n) rows at leading dimension ldw (even, >= padded_dim(n);
+ *                 work_stride even and >= padded_dim(n) * ldw when B > 1; 16-byte aligned); contents on return unspecified
+ *   out_host      B x 3, each value bitwise equal to what fvgp_hip_loglik_batch returns for that theta
+ *   grad_host     B x ntheta: g_i = 1/2 sum_jk (KV^-1_jk - b_j b_k) dK_jk/dtheta_i for the kernel-owned hyperparameters, 0 for the rest
+ *   info_host     B dpotrf info words (may be NULL); a problem with info > 0 gets NaN in its out_host and grad_host rows
+ *   b_out         optional device B x n: b = KV^-1 (y - m)[:, component]
+ *   diag_out      optional device B x n: diag(KV^-1)
+ * Errors (argument numbers): -4 n past FVGP_BATCH_MAX_DIM, -8 B < 1, -13 ncol outside 1..8, -14 component, -15..-17 KV, -18..-20 work,
+ * -21 / -22 missing out_host / grad_host.  One host synchronisation per call.  Problem b's results are bitwise the same whatever B is,
+ * whatever position b holds and whatever else is in the batch. */
+int fvgp_hip_loglik_grad_batch(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
+                               const double *thetas_host, int ntheta, int64_t B,
+                               const double *vdiag, int64_t vdiag_stride, const double *ymean, int64_t ymean_stride,
+                               int ncol, int component,
+                               double *KV, int64_t ld, int64_t kv_stride,
+                               double *work, int64_t ldw, int64_t work_stride,
+                               double *out_host, double *grad_host, int *info_host,
+                               double *b_out, double *diag_out);
+/* device bytes the HANDLE allocates for fvgp_hip_loglik_grad_batch (per problem: every leaf inverse, reciprocal pivots, the theta table
+ * row, z and b, the trace's partial sums for 1 + FVGP_MAX_DIM hyperparameters, two reductions, the gradient row, the info word);
+ * -1 for invalid arguments or where fvgp_hip_loglik_batch_dim(n, ncol) is 0 */
+int64_t fvgp_hip_loglik_grad_batch_workspace_bytes(int64_t n, int ncol, int64_t B);
+
 /* loglik_grad: GPMarginalLikelihood.neg_log_likelihood_gradient  gp_marginal_likelihood.py:224-309
  *   g_i = 1/2 sum_jk (KVinv_jk - b_j b_k) dK_jk/dtheta_i,  b = KVinvY[:,component];
  *   dK/dtheta re-evaluated on the fly (gp_prior.py:421-436, gp_bo.py:167-201).
