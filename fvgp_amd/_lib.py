@@ -33,6 +33,7 @@ SYMBOLS = [
     "fvgp_hip_posterior_dist", "fvgp_hip_grad_dist", "fvgp_hip_loglik_rows", "fvgp_hip_get_profile_ex", "fvgp_hip_comm_info", "fvgp_hip_comm_check", "fvgp_hip_posterior_prepare",
     "fvgp_hip_loglik_batch", "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes",
     "fvgp_hip_loglik_grad_batch", "fvgp_hip_loglik_grad_batch_workspace_bytes",
+    "fvgp_hip_posterior_batch", "fvgp_hip_posterior_batch_workspace_bytes",
 ]
 BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
 
@@ -156,6 +157,11 @@ def loglik_batch_dim(n, ncol=1):
     return d if d <= BATCH_MAX_DIM else 0
 
 
+def posterior_batch_workspace_bytes(n, ncol, B, P_chunk):
+    """device bytes the handle allocates for Handle.posterior_batch (fvgp_hip_posterior_batch_workspace_bytes); <= 0: invalid arguments"""
+    return int(lib().fvgp_hip_posterior_batch_workspace_bytes(int(n), int(ncol), int(B), int(P_chunk)))
+
+
 def lib():
     """Load (once) and return the ctypes library with argtypes set."""
     global _lib
@@ -214,6 +220,10 @@ def lib():
                                              c_p, c_l, c_l, P_d, P_d, P_i, c_p, c_p]
     L.fvgp_hip_loglik_grad_batch_workspace_bytes.argtypes = [c_l, c_i, c_l]
     L.fvgp_hip_loglik_grad_batch_workspace_bytes.restype = c_l
+    L.fvgp_hip_posterior_batch.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l,
+                                           c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_l, c_l, P_d, P_i]
+    L.fvgp_hip_posterior_batch_workspace_bytes.argtypes = [c_l, c_i, c_l, c_l]
+    L.fvgp_hip_posterior_batch_workspace_bytes.restype = c_l
     L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
     L.fvgp_hip_grad_trace.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, P_d]
     L.fvgp_hip_posterior.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_p, c_l,
@@ -243,7 +253,8 @@ def lib():
     bind_dist(L)
     for s in SYMBOLS:
         if s not in ("fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_workspace_bytes", "fvgp_hip_dist_scratch",
-                     "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes", "fvgp_hip_loglik_grad_batch_workspace_bytes"):
+                     "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes", "fvgp_hip_loglik_grad_batch_workspace_bytes",
+                     "fvgp_hip_posterior_batch_workspace_bytes"):
             getattr(L, s).restype = c_i
     _lib = L
     return L
@@ -492,6 +503,47 @@ class Handle(DistCalls):
                                                 out.ctypes.data_as(dp), grad.ctypes.data_as(dp), info.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
                                                 _ptr(b_out), _ptr(diag_out)), "fvgp_hip_loglik_grad_batch")
         return out, grad, info
+
+    def posterior_batch(self, kernel_id, x, thetas, vdiag, ymean, xpred, KV, mean_out, var_out=None, S_out=None, want_loglik=False):
+        """fvgp_hip_posterior_batch: posterior mean, variance and covariance at the B rows of `thetas` (host, B x ntheta) and the P rows
+        of `xpred` (device, P x d) in one call.  vdiag / ymean as loglik_batch.  KV: (B, loglik_batch_dim(n, ncol) + P_chunk, ld) device
+        scratch, P_chunk (a multiple of 128) the prediction points per pass; mean_out (B, P, ncol), var_out (B, P) or None, S_out
+        (B, >= pad128(P), lds) or None: device tensors that receive V^T z (no prior mean), the unclipped variance and the full symmetric
+        covariance (S_out needs P <= P_chunk).  Returns (out, info): out the (B, 3) array loglik_batch returns (None unless want_loglik),
+        info (B,) ints; rows with info > 0 hold NaN."""
+        t = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+        if t.ndim != 2:
+            raise ValueError("posterior_batch: thetas must be (B, ntheta)")
+        B, nt = t.shape
+        n, d = x.shape
+        vd = vdiag.reshape(1, n) if vdiag.dim() == 1 else vdiag
+        ym = ymean.reshape(1, *ymean.shape) if ymean.dim() == 2 else ymean
+        ncol = ym.shape[2]
+        for name, a in (("vdiag", vd), ("ymean", ym)):
+            if a.shape[0] not in (1, B) or not a.is_contiguous():
+                raise ValueError(f"posterior_batch: {name} must be contiguous with a leading dimension of 1 or B = {B}, got {tuple(a.shape)}")
+        if xpred.dim() != 2 or xpred.shape[1] != d or not xpred.is_contiguous():
+            raise ValueError(f"posterior_batch: xpred must be a contiguous (P, {d}) tensor, got {tuple(xpred.shape)}")
+        P = xpred.shape[0]
+        if KV.dim() != 3 or KV.stride(2) != 1 or (B > 1 and KV.shape[0] < B):
+            raise ValueError(f"posterior_batch: KV must be a (B, rows, ld) tensor with unit column stride, got {tuple(KV.shape)}")
+        if not mean_out.is_contiguous() or mean_out.numel() < B * P * ncol:
+            raise ValueError(f"posterior_batch: mean_out must be a contiguous (B, P, ncol) tensor, got {tuple(mean_out.shape)}")
+        if var_out is not None and (not var_out.is_contiguous() or var_out.numel() < B * P):
+            raise ValueError(f"posterior_batch: var_out must be a contiguous (B, P) tensor, got {tuple(var_out.shape)}")
+        if S_out is not None and (S_out.dim() != 3 or S_out.stride(2) != 1 or S_out.shape[1] < pad128(P) or (B > 1 and S_out.shape[0] < B)):
+            raise ValueError(f"posterior_batch: S_out must be a (B, >= {pad128(P)}, lds) tensor with unit column stride, got {tuple(S_out.shape)}")
+        out = np.empty((B, 3), dtype=np.float64) if want_loglik else None
+        info = np.zeros(B, dtype=np.int32)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _check(lib().fvgp_hip_posterior_batch(self._h, int(kernel_id), _ptr(x), n, d, t.ctypes.data_as(dp), nt, B,
+                                              _ptr(vd), n if vd.shape[0] > 1 else 0, _ptr(ym), n * ncol if ym.shape[0] > 1 else 0, ncol,
+                                              _ptr(xpred), P, _ptr(KV), KV.shape[1], KV.stride(1), KV.stride(0),
+                                              _ptr(mean_out), _ptr(var_out), _ptr(S_out),
+                                              0 if S_out is None else S_out.stride(1), 0 if S_out is None else S_out.stride(0),
+                                              None if out is None else out.ctypes.data_as(dp), info.ctypes.data_as(ctypes.POINTER(ctypes.c_int))),
+               "fvgp_hip_posterior_batch")
+        return out, info
 
     def loglik_grad(self, kernel_id, x, theta, alpha, ncol, component, KV, work):
         t, tp, nt = _theta(theta)

@@ -68,6 +68,14 @@ int64_t fvgp_hip_loglik_grad_batch_workspace_bytes(int64_t n, int ncol, int64_t 
     return B * ((dim / TILE) * LEAF_DOUBLES + dim + TW + 2 * np + T * (T + 1) / 2 * TW + 2 + TW) * (int64_t)sizeof(double) + B * (int64_t)sizeof(int);
 }
 
+// per problem: every leaf's block inverse (dim / 128 of them), the reciprocal pivots, the theta table row, two reductions, the info word
+// (fvgp_hip_posterior_batch's layout, in this order; the prediction rows live in the caller's scratch, so P_chunk adds nothing here)
+int64_t fvgp_hip_posterior_batch_workspace_bytes(int64_t n, int ncol, int64_t B, int64_t P_chunk) {
+    const int64_t dim = fvgp_hip_loglik_batch_dim(n, ncol);
+    if (dim <= 0 || B < 1 || P_chunk < TILE || P_chunk % TILE) return -1;
+    return B * ((dim / TILE) * LEAF_DOUBLES + dim + (1 + FVGP_MAX_DIM) + 2) * (int64_t)sizeof(double) + B * (int64_t)sizeof(int);
+}
+
 int fvgp_hip_create(fvgp_handle **out, int device, void *stream) {
     if (!out) return -1;
     int ndev = 0;
@@ -1322,23 +1330,26 @@ static int batch_workspace(fvgp_handle *h, size_t ws) {
     return 0;
 }
 
-// the batched evaluation of Bs problems whose squares start at K0 (stride apart; stride 0 for one): assembly, appended rows, the
-// factorisation by recursive halving, tail -> red (2 per problem).  The leaf of block column k0 of problem b writes its block inverse to
-// linv + b * linv_stride + (k0 / 128) * leaf_step (leaf_step 0: one slot per problem, overwritten step by step).  Every GEMM carries an
-// explicit K range, so that it takes the 128-tile kernel whatever Bs is (a plain one-problem launch of a few tiles would take the
-// 64-tile kernel: other bits).
-static int batch_factor(fvgp_handle *h, int kind, const double *x, int64_t n, int d, const double *tab, const double *vdiag, int64_t vdiag_stride,
-                        const double *ymean, int64_t ymean_stride, int ncol, double *K0, int64_t ld, int64_t stride, int64_t dim,
-                        double *linv, int64_t linv_stride, int64_t leaf_step, double *logdet, int *info, double *red, int64_t Bs) {
-    int rc = launch_kmat_batch(h, kind, x, n, d, tab, vdiag, vdiag_stride, K0, ld, stride, dim, Bs); if (rc) return rc;
-    rc = launch_rhs_rows_batch(h, K0, stride, n, ld, ymean, ymean_stride, ncol, vdiag, vdiag_stride, Bs); if (rc) return rc;
+// the factorisation of Bs problems whose squares start at K0 (stride apart; stride 0 for one) by recursive halving over the block
+// columns, with `rows` >= dim rows per problem: the rows dim .. rows - 1 under a square (fvgp_hip_posterior_batch's prediction rows) ride
+// along in the panel TRSM and in the update between two halves -- their tiles lie below the diagonal, ordinary tiles of the same launches,
+// and a tile's bits do not depend on how many tile rows its launch has.  The leaf of block column k0 of problem b writes its block
+// inverse to linv + b * linv_stride + (k0 / 128) * leaf_step (leaf_step 0: one slot per problem, overwritten step by step).  solve_only:
+// the square is factored already and every leaf inverse kept (leaf_step > 0): no leaves, the TRSM and the updates on the rows from dim
+// on only -- tile for tile the operations the full pass applies to those rows.  Every GEMM carries an explicit K range, so that it takes
+// the 128-tile kernel whatever Bs is (a plain one-problem launch of a few tiles would take the 64-tile kernel: other bits).
+static int batch_recursion(fvgp_handle *h, int64_t n, double *K0, int64_t ld, int64_t stride, int64_t dim, int64_t rows, double *linv,
+                           int64_t linv_stride, int64_t leaf_step, double *logdet, int *info, int64_t Bs, bool solve_only) {
     // one 128-column step: leaf, then the TRSM of every row below by the block inverse
     auto step = [&](int64_t k0) -> int {
-        const int64_t nv = n - k0, r0 = k0 + TILE, R = dim - r0;
+        const int64_t nv = n - k0, r0 = solve_only ? dim : k0 + TILE, R = rows - r0;
         double *li = linv + (k0 / TILE) * leaf_step;
-        int r = launch_leaf_batch(h, K0 + k0 * ld + k0, ld, stride, li, logdet + k0, dim, info, (int)k0,
-                                  nv >= TILE ? TILE : (nv > 0 ? (int)nv : 0), Bs, linv_stride);
-        if (r || R <= 0) return r;
+        if (!solve_only) {
+            int r = launch_leaf_batch(h, K0 + k0 * ld + k0, ld, stride, li, logdet + k0, dim, info, (int)k0,
+                                      nv >= TILE ? TILE : (nv > 0 ? (int)nv : 0), Bs, linv_stride);
+            if (r) return r;
+        }
+        if (R <= 0) return 0;
         GemmDesc t{};          // rows below <- rows below * inv(L_kk)^T, in place
         t.a_kmajor = 0; t.b_nmajor = 0; t.lower = 0; t.M = R; t.N = TILE; t.K = TILE; t.ke0 = TILE;
         t.alpha = 1.0; t.beta = 0.0;
@@ -1355,15 +1366,29 @@ static int batch_factor(fvgp_handle *h, int kind, const double *x, int64_t n, in
         if (blocks <= 1) return step(J0);
         const int64_t mid = J0 + (blocks / 2) * TILE;
         int r = factor(J0, mid); if (r) return r;
-        GemmDesc u{};          // rows [mid, dim) x columns [mid, Jend) -= L[mid:, J0:mid] L[mid:Jend, J0:mid]^T, lower tiles
-        u.a_kmajor = 0; u.b_nmajor = 0; u.lower = 1; u.M = dim - mid; u.N = Jend - mid; u.K = mid - J0; u.ke0 = mid - J0;
+        GemmDesc u{};          // rows [mid, rows) x columns [mid, Jend) -= L[mid:, J0:mid] L[mid:Jend, J0:mid]^T, lower tiles
+        u.a_kmajor = 0; u.b_nmajor = 0; u.lower = 1; u.M = rows - mid; u.N = Jend - mid; u.K = mid - J0; u.ke0 = mid - J0;
         u.alpha = -1.0; u.beta = 1.0;
         u.A = K0 + mid * ld + J0; u.lda = ld; u.B = u.A; u.ldb = ld; u.C = K0 + mid * ld + mid; u.ldc = ld;
+        if (solve_only) {      // the rows from dim on only: all their tiles (they lie below every diagonal tile)
+            u.lower = 0; u.M = rows - dim;
+            u.A = K0 + dim * ld + J0; u.B = K0 + mid * ld + J0; u.C = K0 + dim * ld + mid;
+        }
         u.batch_z = (int)Bs; u.a_bz = stride; u.b_bz = stride; u.c_bz = stride;
         r = launch_gemm(h, u); if (r) return r;
         return factor(mid, Jend);
     };
-    rc = factor(0, dim); if (rc) return rc;
+    return factor(0, dim);
+}
+
+// the batched evaluation of Bs problems whose squares start at K0 (stride apart; stride 0 for one): assembly, appended rows, the
+// factorisation by recursive halving (batch_recursion over the square alone), tail -> red (2 per problem)
+static int batch_factor(fvgp_handle *h, int kind, const double *x, int64_t n, int d, const double *tab, const double *vdiag, int64_t vdiag_stride,
+                        const double *ymean, int64_t ymean_stride, int ncol, double *K0, int64_t ld, int64_t stride, int64_t dim,
+                        double *linv, int64_t linv_stride, int64_t leaf_step, double *logdet, int *info, double *red, int64_t Bs) {
+    int rc = launch_kmat_batch(h, kind, x, n, d, tab, vdiag, vdiag_stride, K0, ld, stride, dim, Bs); if (rc) return rc;
+    rc = launch_rhs_rows_batch(h, K0, stride, n, ld, ymean, ymean_stride, ncol, vdiag, vdiag_stride, Bs); if (rc) return rc;
+    rc = batch_recursion(h, n, K0, ld, stride, dim, dim, linv, linv_stride, leaf_step, logdet, info, Bs, false); if (rc) return rc;
     return launch_loglik_tail_batch(h, logdet, dim, K0, stride, ld, n, ncol, red, Bs);
 }
 
@@ -1547,6 +1572,108 @@ int fvgp_hip_loglik_grad_batch(fvgp_handle *h, int kernel_id, const double *x, i
         const bool bad = inf[b] != 0 && inf[b] <= n;
         for (int i = 0; i < ntheta; ++i) grad_host[b * ntheta + i] = bad ? NAN : (i < nk ? g[b * TW + i] : 0.0);
     }
+    return 0;
+}
+
+// the posterior mean, variance and covariance at B hyperparameter vectors (posterior_batch.hip): the factorisation of fvgp_hip_loglik_batch
+// (the same launches on the same data for the top squares, every leaf inverse kept) with one chunk of prediction rows k(x*, x; theta_b)
+// under each square, which leaves it as V^T; an epilogue per chunk; further chunks by a solve-only pass; S from one strided-batch GEMM
+int fvgp_hip_posterior_batch(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
+                             const double *thetas, int ntheta, int64_t B,
+                             const double *vdiag, int64_t vdiag_stride, const double *ymean, int64_t ymean_stride, int ncol,
+                             const double *xpred, int64_t P,
+                             double *KV, int64_t kv_rows, int64_t ld, int64_t kv_stride,
+                             double *mean_out, double *var_out, double *S_out, int64_t lds, int64_t s_stride,
+                             double *out_host, int *info_host) {
+    if (!h) return -1;
+    if (!x) return -3;
+    if (n <= 0) return -4;
+    if (n > FVGP_BATCH_MAX_DIM) { fvgp_set_error("posterior_batch: n exceeds FVGP_BATCH_MAX_DIM"); return -4; }
+    if (!thetas) return -6;
+    if (B < 1) { fvgp_set_error("posterior_batch: B >= 1"); return -8; }
+    KmatDesc k0d{};
+    int rc = kmat_desc_from_theta(kernel_id, d, thetas, ntheta, &k0d);
+    if (rc) return rc == -7 ? -5 : rc == -9 ? -7 : rc;
+    if (!vdiag) { fvgp_set_error("posterior_batch needs the noise variances (vdiag)"); return -9; }
+    if (vdiag_stride < 0) return -10;
+    if (!ymean) return -11;
+    if (ymean_stride < 0) return -12;
+    if (ncol < 1 || ncol > FVGP_MAX_RHS_VEC) { fvgp_set_error("1 <= ncol <= 8"); return -13; }
+    const int64_t dim = fvgp_hip_loglik_batch_dim(n, ncol), np = pad128(n);
+    if (dim <= 0) { fvgp_set_error("posterior_batch: fvgp_hip_loglik_batch_dim(n, ncol) exceeds FVGP_BATCH_MAX_DIM"); return -4; }
+    if (!xpred) { fvgp_set_error("posterior_batch needs the prediction points (xpred)"); return -14; }
+    if (P < 1) { fvgp_set_error("posterior_batch: P >= 1"); return -15; }
+    if (!KV || ((uintptr_t)KV & 15)) { fvgp_set_error("posterior_batch: KV must be 16-byte aligned"); return -16; }
+    const int64_t P_chunk = kv_rows - dim;
+    if (P_chunk < TILE || P_chunk % TILE) {
+        fvgp_set_error("posterior_batch: kv_rows must be fvgp_hip_loglik_batch_dim(n, ncol) plus a multiple of 128 (>= 128) prediction rows"); return -17;
+    }
+    if (ld < dim || (ld & 1)) { fvgp_set_error("posterior_batch: the leading dimension must be even and >= fvgp_hip_loglik_batch_dim(n, ncol)"); return -18; }
+    if (B > 1 && (kv_stride < kv_rows * ld || (kv_stride & 1))) { fvgp_set_error("posterior_batch: kv_stride must be even and >= kv_rows * ld"); return -19; }
+    if (!mean_out) { fvgp_set_error("posterior_batch needs mean_out"); return -20; }
+    const int64_t Pp = pad128(P);
+    if (S_out) {
+        if (P > P_chunk) { fvgp_set_error("posterior_batch: S_out needs all prediction points in one chunk (P <= kv_rows - dim)"); return -22; }
+        if ((uintptr_t)S_out & 15) { fvgp_set_error("posterior_batch: S_out must be 16-byte aligned"); return -22; }
+        if (lds < Pp || (lds & 1)) { fvgp_set_error("posterior_batch: lds must be even and >= padded_dim(P)"); return -23; }
+        if (B > 1 && (s_stride < Pp * lds || (s_stride & 1))) { fvgp_set_error("posterior_batch: s_stride must be even and >= padded_dim(P) * lds"); return -24; }
+    }
+    HIPCHK(hipSetDevice(h->device));
+    rc = batch_workspace(h, (size_t)fvgp_hip_posterior_batch_workspace_bytes(n, ncol, B, P_chunk)); if (rc) return rc;
+    constexpr int TW = 1 + FVGP_MAX_DIM;
+    const int64_t lstride = (dim / TILE) * LEAF_DOUBLES;
+    // workspace layout (fvgp_hip_posterior_batch_workspace_bytes): every leaf inverse, reciprocal pivots, theta table, then {reductions,
+    // info words} -- the block the host copies back
+    double *linv = reinterpret_cast<double *>(h->bat_ws);
+    double *logdet = linv + B * lstride;
+    double *tab = logdet + B * dim;
+    double *red = tab + B * TW;
+    int *info = reinterpret_cast<int *>(red + 2 * B);
+    rc = batch_theta_table(h, kernel_id, d, thetas, ntheta, B, tab); if (rc) return rc;
+    HIPCHK(hipMemsetAsync(info, 0, (size_t)B * sizeof(int), h->stream));
+    const int kind = k0d.kind;
+    const int64_t stride = B > 1 ? kv_stride : 0, sstride = B > 1 ? s_stride : 0;
+    constexpr int64_t GROUP = 65535;
+    for (int64_t b0 = 0; b0 < B; b0 += GROUP) {
+        const int64_t Bs = B - b0 < GROUP ? B - b0 : GROUP;
+        double *K0 = KV + b0 * stride, *li = linv + b0 * lstride;
+        const double *tb = tab + b0 * TW;
+        rc = launch_kmat_batch(h, kind, x, n, d, tb, vdiag + b0 * vdiag_stride, vdiag_stride, K0, ld, stride, dim, Bs); if (rc) return rc;
+        rc = launch_rhs_rows_batch(h, K0, stride, n, ld, ymean + b0 * ymean_stride, ymean_stride, ncol, vdiag + b0 * vdiag_stride, vdiag_stride, Bs);
+        if (rc) return rc;
+        for (int64_t p0 = 0; p0 < P; p0 += P_chunk) {
+            const int64_t pc = P - p0 < P_chunk ? P - p0 : P_chunk, prow = pad128(pc);
+            // the chunk's rows: k(x*_p, x_j; theta_b) for j < n, zeros in the columns n .. dim - 1 and in the rows past the last point
+            rc = launch_cross_batch(h, kind, xpred + p0 * d, pc, x, n, d, tb, K0 + dim * ld, ld, stride, prow, dim, 0, Bs); if (rc) return rc;
+            rc = batch_recursion(h, n, K0, ld, stride, dim, dim + prow, li, lstride, LEAF_DOUBLES, logdet + b0 * dim, info + b0, Bs, p0 > 0);
+            if (rc) return rc;
+            if (p0 == 0) { rc = launch_loglik_tail_batch(h, logdet + b0 * dim, dim, K0, stride, ld, n, ncol, red + 2 * b0, Bs); if (rc) return rc; }
+            rc = launch_post_epilogue_batch(h, kind, K0, stride, ld, n, dim, ncol, info + b0, tb, mean_out + b0 * P * ncol,
+                                            var_out ? var_out + b0 * P : nullptr, P, p0, pc, Bs);
+            if (rc) return rc;
+        }
+        if (S_out) {
+            // S = k(x*, x*) - V^T-rows V^T-rows^T on the lower tiles: K ends at padded n, where the epilogue has zeroed the columns from
+            // n on (the appended-rows columns do not enter); explicit K range: the 128-tile kernel whatever Bs and P are
+            double *S0 = S_out + b0 * sstride;
+            rc = launch_cross_batch(h, kind, xpred, P, xpred, P, d, tb, S0, lds, sstride, Pp, Pp, 1, Bs); if (rc) return rc;
+            GemmDesc g{};
+            g.a_kmajor = 0; g.b_nmajor = 0; g.lower = 1; g.M = Pp; g.N = Pp; g.K = np; g.ke0 = np; g.alpha = -1.0; g.beta = 1.0;
+            g.A = K0 + dim * ld; g.lda = ld; g.B = g.A; g.ldb = ld; g.C = S0; g.ldc = lds;
+            g.batch_z = (int)Bs; g.a_bz = stride; g.b_bz = stride; g.c_bz = sstride;
+            rc = launch_gemm(h, g); if (rc) return rc;
+            rc = launch_s_finish_batch(h, S0, sstride, lds, Pp, info + b0, n, Bs); if (rc) return rc;
+        }
+    }
+    // ONE host round trip: the B reductions and the B info words in one copy
+    const size_t rbytes = (size_t)B * (2 * sizeof(double) + sizeof(int));
+    h->bat_out_host.resize(rbytes);
+    HIPCHK(hipMemcpyAsync(h->bat_out_host.data(), red, rbytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const double *r = reinterpret_cast<const double *>(h->bat_out_host.data());
+    const int *inf = reinterpret_cast<const int *>(r + 2 * B);
+    if (out_host) batch_results(n, ncol, B, r, inf, out_host, info_host);
+    else if (info_host) for (int64_t b = 0; b < B; ++b) info_host[b] = inf[b] > n ? 0 : inf[b];
     return 0;
 }
 

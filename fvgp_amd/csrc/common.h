@@ -292,6 +292,12 @@ int launch_grad_trace_batch(fvgp_handle *h, int kind, int iso, const double *x, 
 int launch_grad_reduce_batch(fvgp_handle *h, const double *partial, int64_t p_stride, int64_t ntiles, int nk, double *grad, int64_t B);
 int launch_grad_outputs_batch(fvgp_handle *h, const double *bv, int64_t bv_stride, const double *KV, int64_t kv_stride, int64_t ld, int64_t n,
                               double *b_out, double *diag_out, int64_t B);
+// batched posterior (posterior_batch.hip)
+int launch_cross_batch(fvgp_handle *h, int kind, const double *xr, int64_t nr, const double *xc, int64_t nc, int d, const double *tab,
+                       double *K, int64_t ldk, int64_t k_stride, int64_t rows, int64_t cols, int lower, int64_t B);
+int launch_post_epilogue_batch(fvgp_handle *h, int kind, double *KV, int64_t kv_stride, int64_t ld, int64_t n, int64_t dim, int ncol,
+                               const int *info, const double *tab, double *mean, double *var, int64_t P, int64_t p0, int64_t pc, int64_t B);
+int launch_s_finish_batch(fvgp_handle *h, double *S, int64_t s_stride, int64_t lds, int64_t Pp, const int *info, int64_t n, int64_t B);
 
 int ensure_linv(fvgp_handle *h, const double *L, int64_t n, int64_t ldl);
 int ensure_scratch(fvgp_handle *h, int64_t np);

@@ -39,6 +39,45 @@ def _batch_chunks(B, per_problem_bytes, budget):
     return [(s, min(int(B), s + k)) for s in range(0, int(B), k)]
 
 
+def _posterior_batch_plan(B, P, dim, ncol, want_S, budget, max_chunk):
+    """How GP.posterior_*_batch walks B problems x P prediction points: (P_chunk, [(b0, b1)], [(p0, p1)]).  P_chunk (a multiple of 128)
+    prediction rows lie under each problem's dim x dim square in the tall scratch of fvgp_hip_posterior_batch, which walks the spans
+    [(p0, p1)] inside one call; the problems go in the spans [(b0, b1)], one call each, as many as fit `budget` bytes with the tall
+    scratch and the outputs counted (at least one).  Full S needs every point in one chunk (the caller checks P against its limit);
+    otherwise P_chunk is at most `max_chunk`, and shrinks towards 128 while one problem's scratch alone exceeds the budget."""
+    B, P, dim = int(B), int(P), int(dim)
+    Pp = _lib.pad128(P)
+    pc = Pp if want_S else min(Pp, max(128, _lib.pad128(max_chunk)))
+
+    def per_problem(c):
+        return 8 * ((dim + c) * dim + P * ncol + P + (Pp * Pp if want_S else 0))
+    while not want_S and pc > 128 and per_problem(pc) > budget:
+        pc = max(128, _lib.pad128(pc // 2))
+    return pc, _batch_chunks(B, per_problem(pc), budget), [(p0, min(P, p0 + pc)) for p0 in range(0, P, pc)]
+
+
+def _mixture_weights(weights, B):
+    """normalised non-negative weights of a B-member ensemble (None: uniform)"""
+    if weights is None:
+        return np.full(B, 1.0 / B)
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape != (B,):
+        raise ValueError(f"weights must have one entry per hyperparameter vector ({B}), got shape {w.shape}")
+    if not np.all(np.isfinite(w)) or np.any(w < 0.0) or not np.sum(w) > 0.0:
+        raise ValueError("weights must be finite and non-negative with a positive sum")
+    return w / np.sum(w)
+
+
+def _mixture_moments(m, v, w):
+    """moment-matched mean and variance of the mixture sum_b w_b N(m_b, v_b) over the leading axis (w normalised):
+    (mean, variance, v_within, v_between) with mean = sum w_b m_b, v_within = sum w_b v_b, v_between = sum w_b m_b^2 - mean^2"""
+    wb = w.reshape((-1,) + (1,) * (np.ndim(m) - 1))
+    mean = np.sum(wb * m, axis=0)
+    within = np.sum(wb * v, axis=0)
+    between = np.sum(wb * m * m, axis=0) - mean * mean
+    return mean, within + between, within, between
+
+
 class GP(ValidationMixin):
     def __init__(
         self,
@@ -1049,23 +1088,9 @@ class GP(ValidationMixin):
             return {"x": x_orig, "m(x)": posterior_mean_re, "m(x)_flat": np.squeeze(posterior_mean), "x_pred": x_pred}
         return {"x": x_orig, "m(x)": posterior_mean_re, "m(x)_flat": posterior_mean, "x_pred": x_pred}
 
-    def posterior_covariance(self, x_pred, x_out=None, variance_only=False, add_noise=False):
-        """fvgp/gp.py:1433-1480, gp_posterior.py:229-288 (Chol mode: S is always formed, :246)."""
-        if x_out is None:
-            x_out = self.x_out
-        self._perform_input_checks(x_pred, x_out)
-        x_orig = x_pred.copy()
-        if isinstance(x_out, np.ndarray):
-            x_pred = self.cartesian_product(x_pred, x_out)
-        assert x_pred.shape[1] == self.index_set_dim, "wrong number of columns in x_pred"
-        if self._KVinv is not None and variance_only and self.y_data.shape[1] == 1 and self._native is not None:
-            # gp_posterior.py:238-244: v = diag(kk) - einsum('ij,jk,ki->i', k^T, KVinv, k), S never formed
-            S = None
-            v = self._variance_from_inverse(x_pred)
-        else:
-            _, S = self._posterior_device(x_pred, self._hps, None if self._sharded else self._L,
-                                          None if self._sharded else self._alpha, want_cov=True)
-            v = np.array(np.diag(S))
+    def _finish_covariance(self, v, S, x_pred, x_orig, x_out, hps, variance_only, add_noise):
+        """what posterior_covariance does with the raw variances v and covariance S (or None) at hyperparameters hps: the warning, the
+        clipping (gp_posterior.py:248-259), the noise (:554-569) and the output shapes; returns (v(x), S, S_flat, v_flat)"""
         if np.any(v < -0.0001):
             warnings.warn("Negative variances encountered. That normally means that the model is unstable. "
                           "Rethink the kernel definition, add more noise to the data, "
@@ -1076,7 +1101,7 @@ class GP(ValidationMixin):
             if not variance_only:
                 np.fill_diagonal(S, v)
         if add_noise:
-            noise = self._noise(x_pred, self._hps)          # gp_posterior.py:554-569
+            noise = self._noise(x_pred, hps)          # gp_posterior.py:554-569
             if np.ndim(noise) == 2:
                 v = v + np.diag(noise)
                 if S is not None:
@@ -1094,7 +1119,167 @@ class GP(ValidationMixin):
             if self.y_data.shape[1] > 1:
                 v = np.tile(v[:, None], (1, self.y_data.shape[1]))
                 v_re = np.tile(v_re[:, None], (1, self.y_data.shape[1]))
+        return v_re, S_re, S, v
+
+    def posterior_covariance(self, x_pred, x_out=None, variance_only=False, add_noise=False):
+        """fvgp/gp.py:1433-1480, gp_posterior.py:229-288 (Chol mode: S is always formed, :246)."""
+        if x_out is None:
+            x_out = self.x_out
+        self._perform_input_checks(x_pred, x_out)
+        x_orig = x_pred.copy()
+        if isinstance(x_out, np.ndarray):
+            x_pred = self.cartesian_product(x_pred, x_out)
+        assert x_pred.shape[1] == self.index_set_dim, "wrong number of columns in x_pred"
+        if self._KVinv is not None and variance_only and self.y_data.shape[1] == 1 and self._native is not None:
+            # gp_posterior.py:238-244: v = diag(kk) - einsum('ij,jk,ki->i', k^T, KVinv, k), S never formed
+            S = None
+            v = self._variance_from_inverse(x_pred)
+        else:
+            _, S = self._posterior_device(x_pred, self._hps, None if self._sharded else self._L,
+                                          None if self._sharded else self._alpha, want_cov=True)
+            v = np.array(np.diag(S))
+        v_re, S_re, S, v = self._finish_covariance(v, S, x_pred, x_orig, x_out, self._hps, variance_only, add_noise)
         return {"x": x_orig, "x_pred": x_pred, "v(x)": v_re, "S": S_re, "S_flat": S, "v_flat": v}
+
+    # ------------------------------------------------------------------------------------------
+    # posterior over an ensemble of hyperparameter vectors (MCMC samples, multi-start end points, a grid)
+    # ------------------------------------------------------------------------------------------
+    def _posterior_scratch(self, x_pred, hps, want_cov):
+        """(k^T KVinvY, S or None) at hps from an evaluation into the scratch factor, as posterior_mean(hyperparameters=hps): no state touched"""
+        if self._sharded:
+            return self._posterior_device(x_pred, hps, self._evaluate_sharded(hps, state=False)[4], None, want_cov)
+        L, alpha = self._scratch()
+        self._evaluate(hps, L, alpha)
+        return self._posterior_device(x_pred, hps, L, alpha, want_cov)
+
+    def _posterior_batch_core(self, x_pred, hyperparameters, x_out, want_var, want_S):
+        """the raw posterior at each row of `hyperparameters` (B, ntheta): (hp, x_orig, x_pred, x_out, A (B, P, ncol) = k^T KVinvY
+        without the prior mean, v (B, P) unclipped or None, S (B, P, P) or None).  One fvgp_hip_posterior_batch call per chunk of rows
+        wherever the fused evaluation applies (built-in kernel, vector noise > 0 per row, ncol <= 8, no linalg_mode callables, not
+        sharded, loglik_batch_dim(n, ncol) > 0); every other configuration, and single rows whose noise is not such a vector, one by
+        one into the scratch factor.  No state is touched; the first non-positive-definite row raises what the single call raises."""
+        hp = np.asarray(hyperparameters, dtype=np.float64)
+        if hp.ndim != 2:
+            raise ValueError(f"the batched posterior takes a (B, ntheta) array of hyperparameters, got shape {hp.shape}")
+        if x_out is None:
+            x_out = self.x_out
+        self._perform_input_checks(x_pred, x_out)
+        x_orig = x_pred.copy()
+        if isinstance(x_out, np.ndarray):
+            x_pred = self.cartesian_product(x_pred, x_out)
+        assert x_pred.shape[1] == self.index_set_dim, "wrong number of columns in x_pred"
+        B, P, n, ncol = len(hp), len(x_pred), self.point_number, self.y_data.shape[1]
+        A = np.empty((B, P, ncol))
+        v = np.empty((B, P)) if (want_var or want_S) else None
+        S = np.empty((B, P, P)) if want_S else None
+        dim = _lib.loglik_batch_dim(n, ncol) if ncol <= _lib.MAX_RHS_VEC else 0
+        native = self._native is not None and not self._sharded and self._linalg_callables is None and dim > 0 and B > 0 and P > 0
+        if native and want_S and P > self._posterior_chunk:
+            raise NotImplementedError(f"the full covariance over an ensemble takes at most posterior_chunk = {self._posterior_chunk} "
+                                      f"prediction points in one call (got {P}); use variance_only=True or fewer points")
+        done = [None] * B                      # (info, min V) per natively evaluated row; None: one by one
+        if native:
+            H, kid = self._H, self._native.kernel_id
+            shared = self._mean_callable is None and self._noise_callable is None      # m and V do not depend on theta: uploaded once
+            xp = H.to_device(x_pred)
+            Pp = _lib.pad128(P)
+            budget = self.args.get("batch_max_bytes", BATCH_MAX_BYTES)
+            pc, spans, _ = _posterior_batch_plan(B, P, dim, ncol, want_S, budget, self._posterior_chunk)
+            for s0, s1 in spans:
+                idx, Vs, Ys = [], [], []
+                for b in range(s0, s1):
+                    if shared and idx:
+                        idx.append(b)
+                        continue
+                    m, V = self._mean(self.x_data, hp[b]), self._noise(self.x_data, hp[b])
+                    if np.ndim(V) == 1 and float(np.min(V)) > 0.0:             # what the fused single evaluation needs
+                        idx.append(b); Vs.append(np.ascontiguousarray(V, dtype=np.float64)); Ys.append(self.y_data - m[:, None])
+                    elif shared:
+                        break                                                     # the same V for every row: none qualifies
+                if not idx:
+                    continue
+                vd = H.to_device(Vs[0] if shared else np.stack(Vs))
+                ym = H.to_device(Ys[0] if shared else np.stack(Ys))
+                KV = H.empty(len(idx), dim + pc, dim)
+                mean_d = H.empty(len(idx), P, ncol)
+                var_d = H.empty(len(idx), P) if v is not None else None
+                S_d = H.empty(len(idx), Pp, Pp) if want_S else None
+                _, info = H.posterior_batch(kid, self._x_dev, hp[idx], vd, ym, xp, KV, mean_d, var_d, S_d)
+                del KV
+                A[idx] = mean_d.cpu().numpy()
+                if var_d is not None:
+                    v[idx] = var_d.cpu().numpy()
+                if S_d is not None:
+                    S[idx] = S_d[:, :P, :P].cpu().numpy()
+                    v[idx] = np.diagonal(S[idx], axis1=1, axis2=2)                # the single path's v = diag(S)
+                del mean_d, var_d, S_d
+                for j, b in enumerate(idx):
+                    done[b] = (int(info[j]), float(np.min(Vs[0 if shared else j])))
+        for b in range(B):
+            if done[b] is None:
+                Ab, Sb = self._posterior_scratch(x_pred, hp[b], v is not None)
+                A[b] = Ab
+                if v is not None:
+                    v[b] = np.diag(Sb)
+                if S is not None:
+                    S[b] = Sb
+            elif done[b][0] != 0:
+                raise NonPositiveDefiniteError(_non_pd_message(n, done[b][0], done[b][1], 0.0))
+        return hp, x_orig, x_pred, x_out, A, v, S
+
+    def _mean_rows(self, hp, x_orig, x_pred, x_out, A):
+        """posterior_mean's "m(x)" and "m(x)_flat" for every row: prior mean m(x*; theta_b) added, the same shape rules"""
+        ncol = self.y_data.shape[1]
+        flat = np.stack([self._mean(x_pred, hp[b])[:, None] + A[b] for b in range(len(hp))]) if len(hp) else A
+        if isinstance(x_out, np.ndarray):
+            re = np.stack([f.reshape(len(x_orig), len(x_out), order='F') for f in flat]) if len(hp) else flat
+        else:
+            re = flat
+        if ncol == 1:
+            flat = flat[:, :, 0]
+            if not isinstance(x_out, np.ndarray):
+                re = flat
+        return re, flat
+
+    def posterior_mean_batch(self, x_pred, hyperparameters, x_out=None):
+        """posterior_mean at each row of `hyperparameters` (B, ntheta): "m(x)"[b] is posterior_mean(x_pred, hyperparameters[b],
+        x_out)["m(x)"], "m(x)_flat"[b] its "m(x)_flat" -- no state is touched -- from one batched device call per chunk of rows
+        (fvgp_hip_posterior_batch) wherever the fused evaluation applies, one by one otherwise (see _posterior_batch_core).  Chunks of
+        rows and of prediction points are sized by args["batch_max_bytes"] (default BATCH_MAX_BYTES); the results do not depend on them."""
+        hp, x_orig, x_pred, x_out, A, _, _ = self._posterior_batch_core(x_pred, hyperparameters, x_out, False, False)
+        re, flat = self._mean_rows(hp, x_orig, x_pred, x_out, A)
+        return {"x": x_orig, "x_pred": x_pred, "hyperparameters": hp, "m(x)": re, "m(x)_flat": flat}
+
+    def _cov_rows(self, hp, x_orig, x_pred, x_out, v, S, variance_only, add_noise):
+        rows = [self._finish_covariance(v[b].copy(), None if S is None else S[b], x_pred, x_orig, x_out, hp[b], variance_only, add_noise)
+                for b in range(len(hp))]
+        v_re = np.stack([r[0] for r in rows]) if rows else v
+        S_re = None if S is None else (np.stack([r[1] for r in rows]) if rows else S)
+        return v_re, S_re
+
+    def posterior_covariance_batch(self, x_pred, hyperparameters, x_out=None, variance_only=False, add_noise=False):
+        """posterior_covariance at each row of `hyperparameters` (B, ntheta): row b of "v(x)" and "S" is what
+        set_hyperparameters(hyperparameters[b]); posterior_covariance(x_pred, x_out, variance_only, add_noise) returns -- clipping, the
+        warning, the diagonal written back into S and the noise as there -- WITHOUT touching the GP's state.  variance_only: "S" is None
+        and any number of prediction points goes through in chunks; the full covariance takes at most posterior_chunk points.  Routing
+        and chunking as posterior_mean_batch."""
+        hp, x_orig, x_pred, x_out, _, v, S = self._posterior_batch_core(x_pred, hyperparameters, x_out, True, not variance_only)
+        v_re, S_re = self._cov_rows(hp, x_orig, x_pred, x_out, v, S, variance_only, add_noise)
+        return {"x": x_orig, "x_pred": x_pred, "hyperparameters": hp, "v(x)": v_re, "S": S_re}
+
+    def posterior_mixture(self, x_pred, hyperparameters, weights=None, x_out=None, add_noise=False):
+        """The prediction with the hyperparameter uncertainty propagated: the moment-matched average of the posteriors at the rows of
+        `hyperparameters` (B, ntheta) -- e.g. gp.mcmc_info["x"] after train(method="mcmc") -- with `weights` (non-negative, normalised
+        here; default uniform), from ONE pass of the batched call:
+            "m(x)" = sum_b w_b m_b,   "v(x)" = "v_within" + "v_between" = sum_b w_b v_b + (sum_b w_b m_b^2 - m(x)^2)
+        with m_b / v_b the rows of posterior_mean_batch / posterior_covariance_batch(variance_only=True, add_noise=add_noise)."""
+        w = _mixture_weights(weights, len(np.asarray(hyperparameters)))
+        hp, x_orig, x_pred, x_out, A, v, _ = self._posterior_batch_core(x_pred, hyperparameters, x_out, True, False)
+        m_re, _ = self._mean_rows(hp, x_orig, x_pred, x_out, A)
+        v_re, _ = self._cov_rows(hp, x_orig, x_pred, x_out, v, None, True, add_noise)
+        mean, var, within, between = _mixture_moments(m_re, v_re, w)
+        return {"x": x_orig, "x_pred": x_pred, "hyperparameters": hp, "weights": w, "m(x)": mean, "v(x)": var,
+                "v_within": within, "v_between": between}
 
     # ------------------------------------------------------------------------------------------
     # derivatives built on the path -- finite differences of the same device evaluations, with the

@@ -368,6 +368,47 @@ int fvgp_hip_loglik_grad_batch(fvgp_handle *h, int kernel_id, const double *x, i
  * -1 for invalid arguments or where fvgp_hip_loglik_batch_dim(n, ncol) is 0 */
 int64_t fvgp_hip_loglik_grad_batch_workspace_bytes(int64_t n, int ncol, int64_t B);
 
+/* posterior_batch: GPposterior.posterior_mean / posterior_covariance (gp_posterior.py:139-182, 229-288, 120-136) at B hyperparameter
+ * vectors on the same resident x and the same P prediction points, in one call -- a prediction averaged over the theta samples of an
+ * MCMC run, the end points of a multi-start optimiser side by side, a theta grid.  With V = L^-1 k(x, x*) and z = L^-1 (y - m):
+ * mean = V^T z, var = k(x*, x*) - colsumsq(V), S = k(x*, x*) - V^T V, no backward solve (csrc/posterior_batch.hip: the prediction rows
+ * k(x*, x; theta_b) ride under each problem's square through the batched factorisation of fvgp_hip_loglik_batch, which leaves them as
+ * V^T; a streaming epilogue per chunk of points; every launch over all B problems).  Arguments 1-13 as fvgp_hip_loglik_batch, then:
+ *   xpred         (P, d) device, shared by all problems
+ *   KV            caller-owned tall scratch: problem b's at KV + b * kv_stride, kv_rows = fvgp_hip_loglik_batch_dim(n, ncol) + P_chunk rows
+ *                 at leading dimension ld (even, >= dim; kv_stride even and >= kv_rows * ld when B > 1; 16-byte aligned), P_chunk a
+ *                 multiple of 128 (>= 128) of the caller's choice.  The top dim rows are fvgp_hip_loglik_batch's square, the P_chunk rows
+ *                 below take the prediction rows: P > P_chunk points go through them chunk by chunk (the first rides in the
+ *                 factorisation, the others take a solve-only pass of the same recursion by the kept leaf inverses), with the same
+ *                 bits whatever P_chunk is.  Contents on return unspecified
+ *   mean_out      (B, P, ncol) device = V^T z (prior mean added by the caller, as fvgp_hip_posterior)
+ *   var_out       (B, P) device or NULL = k(x*, x*) - colsumsq(V), unclipped
+ *   S_out         NULL, or B squares of padded_dim(P) rows at leading dimension lds (even, >= padded_dim(P)), problem b's at
+ *                 S_out + b * s_stride (even, >= padded_dim(P) * lds when B > 1; 16-byte aligned): kk - k^T KV^-1 k, full and bitwise
+ *                 symmetric (the lower tiles are computed, with K ending at padded_dim(n) over prediction rows whose columns from n on
+ *                 the epilogue has zeroed, and mirrored).  Needs all points in one chunk: P <= P_chunk
+ *   out_host      NULL, or B x 3: bitwise what fvgp_hip_loglik_batch returns for the same arguments (the top squares see the same
+ *                 launches on the same data)
+ *   info_host     B dpotrf info words (may be NULL); a problem with info > 0 gets NaN in its mean_out / var_out / S_out (and out_host)
+ *                 rows and does not disturb its neighbours
+ * Errors (argument numbers): -4 n past FVGP_BATCH_MAX_DIM (or fvgp_hip_loglik_batch_dim(n, ncol) == 0), -8 B < 1, -13 ncol outside
+ * 1..8, -14 xpred, -15 P < 1, -16 KV, -17 kv_rows (dim + a multiple of 128 >= 128), -18 ld, -19 kv_stride, -20 mean_out, -22 S_out
+ * (P > P_chunk or alignment), -23 lds, -24 s_stride; nothing is launched then.  One host synchronisation per call.  Problem b's outputs
+ * are bitwise the same whatever B is, whatever position b holds and whatever else is in the batch (a failing theta included): every sum
+ * of a prediction row sees that row and its problem's factor only, in a fixed order; they agree with fvgp_hip_loglik + fvgp_hip_posterior
+ * to rounding (another schedule of the same sums). */
+int fvgp_hip_posterior_batch(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
+                             const double *thetas_host, int ntheta, int64_t B,
+                             const double *vdiag, int64_t vdiag_stride, const double *ymean, int64_t ymean_stride, int ncol,
+                             const double *xpred, int64_t P,
+                             double *KV, int64_t kv_rows, int64_t ld, int64_t kv_stride,
+                             double *mean_out, double *var_out, double *S_out, int64_t lds, int64_t s_stride,
+                             double *out_host, int *info_host);
+/* device bytes the HANDLE allocates for fvgp_hip_posterior_batch (per problem: every leaf inverse -- dim / 128 blocks of 128 x 128 --,
+ * dim reciprocal pivots, the theta table row of 1 + FVGP_MAX_DIM, two reductions, the info word; the prediction rows live in the
+ * caller's scratch, so P_chunk only has to be valid); -1 for invalid arguments or where fvgp_hip_loglik_batch_dim(n, ncol) is 0 */
+int64_t fvgp_hip_posterior_batch_workspace_bytes(int64_t n, int ncol, int64_t B, int64_t P_chunk);
+
 /* loglik_grad: GPMarginalLikelihood.neg_log_likelihood_gradient  gp_marginal_likelihood.py:224-309
  *   g_i = 1/2 sum_jk (KVinv_jk - b_j b_k) dK_jk/dtheta_i,  b = KVinvY[:,component];
  *   dK/dtheta re-evaluated on the fly (gp_prior.py:421-436, gp_bo.py:167-201).
