@@ -34,6 +34,7 @@ SYMBOLS = [
     "fvgp_hip_loglik_batch", "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes",
     "fvgp_hip_loglik_grad_batch", "fvgp_hip_loglik_grad_batch_workspace_bytes",
     "fvgp_hip_posterior_batch", "fvgp_hip_posterior_batch_workspace_bytes",
+    "fvgp_hip_posterior_grad", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_potrs_cols",
 ]
 BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
 
@@ -162,6 +163,11 @@ def posterior_batch_workspace_bytes(n, ncol, B, P_chunk):
     return int(lib().fvgp_hip_posterior_batch_workspace_bytes(int(n), int(ncol), int(B), int(P_chunk)))
 
 
+def posterior_grad_workspace_bytes(n, P, n_dirs):
+    """bytes of the caller-owned scratch of Handle.posterior_grad (fvgp_hip_posterior_grad_workspace_bytes); <= 0: invalid arguments"""
+    return int(lib().fvgp_hip_posterior_grad_workspace_bytes(int(n), int(P), int(n_dirs)))
+
+
 def lib():
     """Load (once) and return the ctypes library with argtypes set."""
     global _lib
@@ -224,6 +230,11 @@ def lib():
                                            c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_l, c_l, P_d, P_i]
     L.fvgp_hip_posterior_batch_workspace_bytes.argtypes = [c_l, c_i, c_l, c_l]
     L.fvgp_hip_posterior_batch_workspace_bytes.restype = c_l
+    L.fvgp_hip_posterior_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_i, c_p, c_l, c_i,
+                                          c_p, c_l, c_p, c_p, c_p, c_p]
+    L.fvgp_hip_posterior_grad_workspace_bytes.argtypes = [c_l, c_l, c_i]
+    L.fvgp_hip_posterior_grad_workspace_bytes.restype = c_l
+    L.fvgp_hip_potrs_cols.argtypes = [c_p, c_p, c_l, c_l, c_p, c_l, c_l]
     L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
     L.fvgp_hip_grad_trace.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, P_d]
     L.fvgp_hip_posterior.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_p, c_l,
@@ -254,7 +265,7 @@ def lib():
     for s in SYMBOLS:
         if s not in ("fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_workspace_bytes", "fvgp_hip_dist_scratch",
                      "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes", "fvgp_hip_loglik_grad_batch_workspace_bytes",
-                     "fvgp_hip_posterior_batch_workspace_bytes"):
+                     "fvgp_hip_posterior_batch_workspace_bytes", "fvgp_hip_posterior_grad_workspace_bytes"):
             getattr(L, s).restype = c_i
     _lib = L
     return L
@@ -645,6 +656,21 @@ class Handle(DistCalls):
                                         _ptr(alpha), int(ncol), _ptr(xpred), xpred.shape[0], _ptr(kx), kx.stride(0),
                                         _ptr(mean_out), _ptr(var_out), _ptr(S_out),
                                         0 if S_out is None else S_out.stride(0)), "fvgp_hip_posterior")
+
+    def posterior_grad(self, kernel_id, x, theta, xpred, alpha, ncol, component, W, n_dirs, work, A_out, q_out, dm_out, dv_out):
+        """fvgp_hip_posterior_grad: A = k^T alpha[:, component], q = sum_i k_i W_i and their exact derivatives dm, dv (P, n_dirs) in the
+        first n_dirs columns of the prediction points; W = KV^-1 k(x, xpred) (padded n x >= padded P) or None for the mean only;
+        work: a tensor of at least posterior_grad_workspace_bytes(n, P, n_dirs) bytes.  Asynchronous."""
+        t, tp, nt = _theta(theta)
+        n, d = x.shape
+        _check(lib().fvgp_hip_posterior_grad(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(xpred), xpred.shape[0],
+                                             _ptr(alpha), int(ncol), int(component), _ptr(W), 0 if W is None else W.stride(0),
+                                             int(n_dirs), _ptr(work), work.numel() * work.element_size(),
+                                             _ptr(A_out), _ptr(q_out), _ptr(dm_out), _ptr(dv_out)), "fvgp_hip_posterior_grad")
+
+    def potrs_cols(self, L, n, B, nrhs):
+        """Handle.potrs for nrhs % 128 == 0 columns whose bits do not depend on nrhs (fvgp_hip_potrs_cols)"""
+        _check(lib().fvgp_hip_potrs_cols(self._h, _ptr(L), n, L.stride(0), _ptr(B), nrhs, B.stride(0)), "fvgp_hip_potrs_cols")
 
     def posterior_prepare(self, L, n):
         """enqueue the inverted diagonal blocks the posterior's sweep substitutes with (fvgp_hip_posterior_prepare)"""

@@ -1038,6 +1038,25 @@ int fvgp_hip_potrs(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, doub
     return trsm_bwd_gemm(h, L, n, ldl, B, nrhs, ldb);
 }
 
+// potrs with the launch shape of every product fixed (the 128-tile kernel): a column's bits do not depend on nrhs
+int fvgp_hip_potrs_cols(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, double *B, int64_t nrhs, int64_t ldb) {
+    if (!h) return -1;
+    int rc = check_square(L, n, ldl, 2, 3, 4);
+    if (rc) return rc;
+    if (!B) return -5;
+    if (nrhs <= 0 || nrhs % 128 || (ldb & 1) || ((uintptr_t)B & 15)) { fvgp_set_error("potrs_cols needs nrhs % 128 == 0, even ldb, 16-byte aligned B"); return -6; }
+    if (ldb < nrhs) return -7;
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t np = pad128(n);
+    if (np > n) { rc = launch_copy_cols(h, B, ldb, B + n * ldb, ldb, 0, 0, np - n, nrhs); if (rc) return rc; }
+    const int64_t keep = h->small_tile_max;
+    h->small_tile_max = -1;
+    rc = trsm_fwd_gemm(h, L, n, ldl, B, nrhs, ldb);
+    if (!rc) rc = trsm_bwd_gemm(h, L, n, ldl, B, nrhs, ldb);
+    h->small_tile_max = keep;
+    return rc;
+}
+
 int fvgp_hip_trsm_lower(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, double *B, int64_t nrhs, int64_t ldb) {
     if (!h) return -1;
     int rc = check_square(L, n, ldl, 2, 3, 4);

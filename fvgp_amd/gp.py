@@ -1433,6 +1433,93 @@ class GP(ValidationMixin):
             grad_v = grad_v.reshape(len(x_orig), len(x_orig[0]), len(x_out), order='F')
         return {"x": x_orig, "dv/dx": grad_v}
 
+    def posterior_gradients(self, x_pred, hyperparameters=None, x_out=None, component=0, variance=True):
+        """Posterior mean and variance at x_pred together with their EXACT gradients in x_pred, in one device pass -- what the
+        optimiser of an acquisition function calls at every step.  posterior_mean_grad / posterior_covariance_grad restate the
+        reference's forward differences of the kernel (step 1e-8, about eight digits); for the named kernels the derivative is closed
+        form (kernels.kernel_dx), and with alpha = KVinvY[:, component], W = KV^-1 k(x_data, x_pred)
+            m = mu + k^T alpha,  v = k(x*, x*) - sum_i k_i W_i,  dm/dx = dmu/dx + dk/dx^T alpha,  dv/dx = -2 sum_i dk_i/dx W_i
+        come out of one pass over W (fvgp_hip_posterior_grad): no dk matrix, no P x P product.
+
+        Returns {"x", "m(x)", "v(x)", "dm/dx", "dv/dx"}: m(x) and v(x) of shape (P,) for column `component` of y, dm/dx and dv/dx of
+        shape (P, D); with x_out (P, No) and (P, D, No), by the reshapes of posterior_mean / posterior_mean_grad.  v(x) is clipped at
+        0 as posterior_covariance does; dv/dx is the derivative of the unclipped latent variance (no noise term, as in the reference).
+        variance=False skips the solve: "v(x)" and "dv/dx" are None.  `hyperparameters` evaluates into the scratch factor and leaves
+        the state untouched.  More than `posterior_chunk` (4096) points go through the device in chunks; a point's results have the
+        same bits however many points travel with it.  A user prior mean contributes its derivative by the reference's forward
+        difference (step 1e-6, gp_posterior.py:203-207), the default constant mean contributes 0."""
+        if self._sharded:
+            raise NotImplementedError("posterior_gradients runs on the single-GPU path only")
+        if self._native is None:
+            raise NotImplementedError("posterior_gradients needs a named kernel (no closed form is known for a host kernel callable); "
+                                      "use the finite-difference methods posterior_mean_grad / posterior_covariance_grad")
+        if self._linalg_callables is not None:
+            raise NotImplementedError("posterior_gradients does not run through linalg_mode callables; "
+                                      "use the finite-difference methods posterior_mean_grad / posterior_covariance_grad")
+        H, n, ncol = self._H, self.point_number, self.y_data.shape[1]
+        assert 0 <= int(component) < ncol, "component out of range"
+        L, alpha, hps = self._L, self._alpha, self._hps
+        if hyperparameters is not None:
+            hps = np.asarray(hyperparameters, dtype=np.float64)
+            L, alpha = self._scratch()
+            self._evaluate(hps, L, alpha)
+        if x_out is None:
+            x_out = self.x_out
+        self._perform_input_checks(x_pred, x_out)
+        x_orig = x_pred.copy()
+        if isinstance(x_out, np.ndarray):
+            x_pred = self.cartesian_product(x_pred, x_out)
+        assert x_pred.shape[1] == self.index_set_dim, "wrong number of columns in x_pred"
+        x_pred = np.ascontiguousarray(x_pred, dtype=np.float64)
+        P, D, kid = len(x_pred), x_orig.shape[1], self._native.kernel_id
+        C = int(self._posterior_chunk)
+        assert C % 128 == 0 and C >= 128, "posterior_chunk must be a multiple of 128"
+        pc = min(P, C)
+        work = H.empty(max(1, _lib.posterior_grad_workspace_bytes(n, pc, D) // 8))
+        A_d, dm_d = H.empty(pc), H.empty(pc, D)
+        q_d, dv_d, W = (H.empty(pc), H.empty(pc, D), H.empty(self._np, _lib.pad128(pc))) if variance else (None, None, None)
+        A, dm = np.empty(P), np.empty((P, D))
+        q, dv = (np.empty(P), np.empty((P, D))) if variance else (None, None)
+        for a in range(0, P, C):
+            b = min(a + C, P)
+            xp = H.to_device(x_pred[a:b])
+            Wc = None
+            if variance:
+                Pp = _lib.pad128(b - a)
+                Wc = W.view(-1)[:self._np * Pp].view(self._np, Pp)
+                H.kmat(kid, self._x_dev, xp, hps, Wc, pad=_lib.PAD_ZERO)
+                H.potrs_cols(L, n, Wc, Pp)                                  # KV^-1 k, a column's bits independent of the chunk
+            H.posterior_grad(kid, self._x_dev, hps, xp, alpha, ncol, component, Wc, D, work, A_d, q_d, dm_d, dv_d)
+            H.sync()
+            A[a:b], dm[a:b] = A_d[:b - a].cpu().numpy(), dm_d[:b - a].cpu().numpy()
+            if variance:
+                q[a:b], dv[a:b] = q_d[:b - a].cpu().numpy(), dv_d[:b - a].cpu().numpy()
+        f = self._mean(x_pred, hps)
+        m = f + A
+        if self._mean_callable is not None:
+            eps = 1e-6
+            for dd in range(D):
+                x1 = np.array(x_pred)
+                x1[:, dd] = x1[:, dd] + eps
+                dm[:, dd] += (self._mean(x1, hps) - f) / eps
+        v = None
+        if variance:
+            v = float(hps[0]) - q                                           # k(x*, x*) = the signal variance for every named kernel
+            if np.any(v < -0.0001):
+                warnings.warn("Negative variances encountered. That normally means that the model is unstable. "
+                              "Rethink the kernel definition, add more noise to the data, "
+                              "or double check the hyperparameter optimization bounds. This will not "
+                              "terminate the algorithm, but expect anomalies.")
+            v[v < 0.0] = 0.0
+        if isinstance(x_out, np.ndarray):
+            V, No = len(x_orig), len(x_out)
+            m = m.reshape(V, No, order='F')
+            dm = dm.reshape(V, D, No, order='F')
+            if variance:
+                v = v.reshape(V, No, order='F')
+                dv = dv.reshape(V, D, No, order='F')
+        return {"x": x_orig, "m(x)": m, "v(x)": v, "dm/dx": dm, "dv/dx": dv}
+
     # ------------------------------------------------------------------------------------------
     # training: the callers of the path (SURVEY 8f1) -- device-resident objective, host optimiser
     # ------------------------------------------------------------------------------------------

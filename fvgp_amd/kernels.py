@@ -65,6 +65,39 @@ def resolve(kernel_function):
     return None
 
 
+def kernel_dx(name, x_pred, x_data, hps):
+    """Closed-form derivative of a named kernel in its FIRST argument, on the host: out[k, p, i] = d k(x_pred_p, x_data_i) / d x_pred_pk,
+    shape (D, P, N).  With D_k = x_pred_pk - x_data_ik, l_k the length scale of dimension k (hps[1 + k], or hps[1] for the *_iso
+    kernels), r^2 = sum_k (D_k / l_k)^2 and s = hps[0]:
+
+        rbf       k = s exp(-r^2 / 2)                            dk/dx_k = -s exp(-r^2 / 2)                 D_k / l_k^2
+        matern32  k = s (1 + sqrt3 r) exp(-sqrt3 r)              dk/dx_k = -3 s exp(-sqrt3 r)               D_k / l_k^2
+        matern52  k = s (1 + sqrt5 r + 5 r^2 / 3) exp(-sqrt5 r)  dk/dx_k = -5/3 s (1 + sqrt5 r) exp(-sqrt5 r) D_k / l_k^2
+
+    (the 1 / r of dr/dx cancels: all three are finite at coincident points).  This is the formula fvgp_hip_posterior_grad evaluates
+    on the device (csrc/posterior_grad.hip, radial.h), written in numpy: its CPU comparator and its documentation."""
+    if isinstance(name, NativeKernel):
+        name = name.name
+    if name not in NATIVE:
+        raise ValueError(f"unknown native kernel {name!r}; choose from {sorted(NATIVE)}")
+    x_pred = np.asarray(x_pred, dtype=np.float64)
+    x_data = np.asarray(x_data, dtype=np.float64)
+    hps = np.asarray(hps, dtype=np.float64)
+    d = x_pred.shape[1]
+    ls = np.full(d, hps[1]) if name.endswith("_iso") else hps[1:1 + d]
+    delta = x_pred[:, None, :] - x_data[None, :, :]                    # (P, N, D)
+    e = delta / ls
+    r2 = np.einsum("pnd,pnd->pn", e, e)
+    if name.startswith("rbf"):
+        cf = hps[0] * np.exp(-0.5 * r2)
+    elif name.startswith("matern32"):
+        cf = 3.0 * hps[0] * np.exp(-np.sqrt(3.0) * np.sqrt(r2))
+    else:
+        a = np.sqrt(5.0) * np.sqrt(r2)
+        cf = (5.0 / 3.0) * hps[0] * (1.0 + a) * np.exp(-a)
+    return np.ascontiguousarray(np.transpose(-cf[:, :, None] * delta / ls ** 2, (2, 0, 1)))
+
+
 # ---------------------------------------------------------------------------------------------
 # Building blocks for USER-WRITTEN host callables (SURVEY Appendix D): code written against the reference's
 # `fvgp.kernels` helper names keeps working when its kernel is handed to fvgp_amd.GP as a Python callable (the host

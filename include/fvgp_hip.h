@@ -454,6 +454,38 @@ int fvgp_hip_posterior(fvgp_handle *h, int kernel_id, const double *x, int64_t n
                        const double *alpha, int ncol, const double *xpred, int64_t P,
                        double *kx, int64_t ldk, double *mean_out, double *var_out, double *S_out, int64_t lds);
 
+/* posterior_grad: the posterior mean and variance at P points TOGETHER WITH their exact gradients in the prediction points, for the
+ * optimiser of an acquisition function.  The reference takes these derivatives by a forward difference of the kernel with step 1e-8
+ * (gp_posterior.py:184-226, 290-331; gp_prior.py:402-409); for the stationary kernels here dk(x*, x_i)/dx*_k = -cf(r^2) (x*_k - x_ik) / l_k^2
+ * in closed form, so with alpha = KVinvY[:, component] and W = KV^-1 k(x, x*) one pass over W gives (csrc/posterior_grad.hip)
+ *     A_out[p] = sum_i k_ip alpha_i                          (prior mean added by the caller, as fvgp_hip_posterior)
+ *     q_out[p] = sum_i k_ip W_ip                             (the caller forms k(x*, x*) - q)
+ *     dm_out[p][k] = sum_i dk_ip/dx*_k alpha_i               (P, n_dirs)
+ *     dv_out[p][k] = -2 sum_i dk_ip/dx*_k W_ip               (P, n_dirs): the derivative of the unclipped latent variance
+ *   alpha     (padded_dim(n), ncol) device, column `component` is read
+ *   W         (padded_dim(n), ldw) device with ldw >= padded_dim(P): the first n rows of KV^-1 k(x, x*), prediction points contiguous
+ *             (what fvgp_hip_kmat with zero padding followed by fvgp_hip_potrs / fvgp_hip_potrs_cols leaves), or NULL: A_out and
+ *             dm_out only (q_out, dv_out may be NULL then)
+ *   n_dirs    1 .. d: the LEADING input columns to differentiate (a multi-task index set differentiates its spatial columns, not the
+ *             task column)
+ *   work      caller-owned device scratch of at least fvgp_hip_posterior_grad_workspace_bytes(n, P, n_dirs) bytes (the partial sums of
+ *             the slices of 256 data rows); work_bytes its size
+ * The data rows are split over workgroups by n alone and the partial sums added in a fixed order without atomics: a point's four
+ * results have the same bits whatever P is, whichever other points are in the call and wherever a caller cuts a list of points into
+ * calls.  Asynchronous on the handle's stream.  Errors (argument numbers): -3 x, -4 n, -6 theta, -8 xpred, -9 P, -10 alpha, -11 ncol,
+ * -12 component, -14 ldw, -15 n_dirs, -16 work, -17 work_bytes, -18 .. -21 an output that is needed is NULL; kernel id, d and ntheta
+ * as fvgp_hip_kmat. */
+int fvgp_hip_posterior_grad(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
+                            const double *theta_host, int ntheta, const double *xpred, int64_t P,
+                            const double *alpha, int ncol, int component, const double *W, int64_t ldw, int n_dirs,
+                            double *work, int64_t work_bytes, double *A_out, double *q_out, double *dm_out, double *dv_out);
+/* bytes of the caller-owned scratch of fvgp_hip_posterior_grad; -1 for invalid arguments */
+int64_t fvgp_hip_posterior_grad_workspace_bytes(int64_t n, int64_t P, int n_dirs);
+/* fvgp_hip_potrs for nrhs % 128 == 0 columns with every product on the 128-tile kernel, whatever nrhs is: fvgp_hip_potrs sends products
+ * of few tiles to the 64-tile kernel, which contracts k in another order, so that a column's bits there depend on how many columns
+ * travel with it.  Here a column of the solution has the same bits in every call (the results fvgp_hip_posterior_grad builds on). */
+int fvgp_hip_potrs_cols(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, double *B, int64_t nrhs, int64_t ldb);
+
 /* ---- building blocks exported for the parity tests --------------------------------------
  * C (M,N) = alpha * opA * opB + beta * C on fp64 MFMA.  M, N multiples of 128, K of 16.
  *   a_kmajor == 0: A stored (M,K) row-major;  != 0: A stored (K,M) row-major (A^T product)
