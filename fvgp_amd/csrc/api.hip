@@ -2,6 +2,7 @@
 // sequence the kernels on the handle's stream, and the fused log-likelihood / gradient /
 // posterior evaluations.  No torch types; plain pointers and sizes only.
 #include "common.h"
+#include "kernel_family.h"
 #include <math.h>
 #include <string.h>
 #include <functional>
@@ -929,9 +930,7 @@ static int grad_trace_host(fvgp_handle *h, int kernel_id, const double *x, int64
     g.col0 = col0; g.ncols = ncols;
     int rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &g.k); if (rc) return rc;
     g.k.x1 = x; g.k.n1 = n; g.k.x2 = x; g.k.n2 = n;
-    g.kernel_id = kernel_id;
-    const bool iso = kernel_id >= 3;
-    const int nk = iso ? 2 : d + 1;     // kernel-owned hyperparameters; the rest get a zero gradient
+    const int nk = kernel_param_count(kernel_id, d);     // kernel-owned hyperparameters; the rest get a zero gradient
     g.ntheta = nk;
     g.W = W; g.ldw = ldw; g.b = b; g.ldb = ldb;
     g.partial = partial;
@@ -1531,7 +1530,7 @@ int fvgp_hip_loglik_grad_batch(fvgp_handle *h, int kernel_id, const double *x, i
     int *info = reinterpret_cast<int *>(grad + B * TW);
     rc = batch_theta_table(h, kernel_id, d, thetas, ntheta, B, tab); if (rc) return rc;
     HIPCHK(hipMemsetAsync(info, 0, (size_t)B * sizeof(int), h->stream));
-    const int kind = k0d.kind, iso = kernel_id >= 3, nk = iso ? 2 : d + 1;
+    const int kind = k0d.kind, iso = k0d.iso, nk = kernel_param_count(kernel_id, d);
     const int64_t stride = B > 1 ? kv_stride : 0, wstride = B > 1 ? work_stride : 0;
     constexpr int64_t GROUP = 65535;
     for (int64_t b0 = 0; b0 < B; b0 += GROUP) {

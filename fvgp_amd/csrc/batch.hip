@@ -15,6 +15,7 @@
 // Results do not depend on the batch: every kernel variant is chosen from the per-problem shape only, each problem has its own
 // info word, log-det slots and fixed-order reductions, and no product splits K.
 #include "radial.h"
+#include "kernel_family.h"
 #include "leaf_body.h"
 
 namespace {
@@ -191,22 +192,9 @@ int launch_kmat_batch(fvgp_handle *h, int kind, const double *x, int64_t n, int 
     KBArgs a;
     a.x = x; a.vdiag = vdiag; a.K = KV; a.tab = tab; a.n = n; a.ldk = ld; a.kv_stride = kv_stride; a.vd_stride = vd_stride; a.d = d;
     const dim3 grid((unsigned)(dim / TILE), (unsigned)(dim / TILE), (unsigned)B), block(256);
-#define GO(KIND, D) hipLaunchKernelGGL((kmat_batch_kernel<KIND, D>), grid, block, 0, h->stream, a)
-#define GOD(KIND)                                   \
-    switch (d) {                                    \
-        case 1: GO(KIND, 1); break;                 \
-        case 2: GO(KIND, 2); break;                 \
-        case 3: GO(KIND, 3); break;                 \
-        case 4: GO(KIND, 4); break;                 \
-        default: GO(KIND, 0); break;                \
-    }
-    switch (kind) {
-        case 0: GOD(0); break;
-        case 1: GOD(1); break;
-        default: GOD(2); break;
-    }
-#undef GOD
-#undef GO
+    dispatch_kind_dim(kind, d, [&](auto KIND, auto D) {
+        hipLaunchKernelGGL((kmat_batch_kernel<decltype(KIND)::value, decltype(D)::value>), grid, block, 0, h->stream, a);
+    });
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -198,6 +198,7 @@ long gemm_debug_tile_map(int tiles_m, int tiles_n, int lower, int ls, int lo, in
 
 struct KmatDesc {
     int kind;                 // 0 rbf, 1 matern 3/2, 2 matern 5/2
+    bool iso;                 // one length scale for every dimension (kernel_family.h)
     const double *x1; int64_t n1;
     const double *x2; int64_t n2;
     int d;
@@ -212,7 +213,6 @@ int kmat_desc_from_theta(int kernel_id, int d, const double *theta, int ntheta, 
 
 struct GradDesc {
     KmatDesc k;               // x1 == x2 == x, n1 == n2 == n
-    int kernel_id;
     int ntheta;
     const double *W; int64_t ldw;   // lower triangle of KV^-1
     const double *b; int64_t ldb;   // KVinvY column (stride ldb)

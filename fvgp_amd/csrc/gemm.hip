@@ -972,13 +972,13 @@ int launch_gemm(fvgp_handle *h, const GemmDesc &d) {
         HIPCHK(hipGetLastError());
         return 0;
     }
-#define GO(AK, BN) do { if (d.role == 1) hipLaunchKernelGGL((gemm_f64_kernel<AK, BN, 1>), grid, block, 0, h->stream, g); \
+#define LAUNCH(AK, BN) do { if (d.role == 1) hipLaunchKernelGGL((gemm_f64_kernel<AK, BN, 1>), grid, block, 0, h->stream, g); \
                         else hipLaunchKernelGGL((gemm_f64_kernel<AK, BN, 0>), grid, block, 0, h->stream, g); } while (0)
-    if (!d.a_kmajor && !d.b_nmajor) GO(0, 0);
-    else if (!d.a_kmajor && d.b_nmajor) GO(0, 1);
-    else if (d.a_kmajor && !d.b_nmajor) GO(1, 0);
-    else GO(1, 1);
-#undef GO
+    if (!d.a_kmajor && !d.b_nmajor) LAUNCH(0, 0);
+    else if (!d.a_kmajor && d.b_nmajor) LAUNCH(0, 1);
+    else if (d.a_kmajor && !d.b_nmajor) LAUNCH(1, 0);
+    else LAUNCH(1, 1);
+#undef LAUNCH
     HIPCHK(hipGetLastError());
     if (split) return launch_splitk_reduce(h, d.split_ws, d.split, d.M, d.N, d.lower, d.C, d.ldc, d.beta,
                                            d.split_out ? d.split_out : d.C, d.split_out ? d.split_ldo : d.ldc, g.tri ? g.ksplit : 0);

@@ -10,6 +10,7 @@
 //     fused trace (grad_trace_batch_kernel: grad_trace_kernel's arithmetic) -> per-problem fixed-order sum (grad_reduce_batch_kernel).
 // As in batch.hip every launch covers all B problems, nothing waits inside a launch, and no result depends on the batch.
 #include "radial.h"
+#include "kernel_family.h"
 
 namespace {
 
@@ -258,22 +259,9 @@ int launch_grad_trace_batch(fvgp_handle *h, int kind, int iso, const double *x, 
     a.n = n; a.ldw = ldw; a.w_stride = w_stride; a.b_stride = b_stride; a.p_stride = p_stride; a.d = d; a.iso = iso;
     const int64_t T = pad128(n) / TILE;
     const dim3 grid((unsigned)(T * (T + 1) / 2), (unsigned)B), block(256);
-#define GT(KIND, D) hipLaunchKernelGGL((grad_trace_batch_kernel<KIND, D>), grid, block, 0, h->stream, a)
-#define GTD(KIND)                                   \
-    switch (d) {                                    \
-        case 1: GT(KIND, 1); break;                 \
-        case 2: GT(KIND, 2); break;                 \
-        case 3: GT(KIND, 3); break;                 \
-        case 4: GT(KIND, 4); break;                 \
-        default: GT(KIND, 0); break;                \
-    }
-    switch (kind) {
-        case 0: GTD(0); break;
-        case 1: GTD(1); break;
-        default: GTD(2); break;
-    }
-#undef GTD
-#undef GT
+    dispatch_kind_dim(kind, d, [&](auto KIND, auto D) {
+        hipLaunchKernelGGL((grad_trace_batch_kernel<decltype(KIND)::value, decltype(D)::value>), grid, block, 0, h->stream, a);
+    });
     HIPCHK(hipGetLastError());
     return 0;
 }

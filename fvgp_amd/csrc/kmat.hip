@@ -16,6 +16,7 @@
 // the fly from x, replacing the (H,N,N) dK_dH tensor and the batched LU solve of
 // gp_marginal_likelihood.py:260-274.
 #include "radial.h"
+#include "kernel_family.h"
 
 namespace {
 
@@ -269,11 +270,12 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(GArgs a) {
 }  // namespace
 
 int kmat_desc_from_theta(int kernel_id, int d, const double *theta, int ntheta, KmatDesc *out) {
-    if (kernel_id < 0 || kernel_id > 5) { fvgp_set_error("unknown kernel id"); return -2; }
+    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
     if (d < 1 || d > FVGP_MAX_DIM) { fvgp_set_error("input dimension out of range"); return -7; }
-    const bool iso = kernel_id >= 3;
-    if (ntheta < (iso ? 2 : d + 1)) { fvgp_set_error("too few hyperparameters for this kernel"); return -9; }
-    out->kind = kernel_id % 3;
+    if (ntheta < kernel_param_count(kernel_id, d)) { fvgp_set_error("too few hyperparameters for this kernel"); return -9; }
+    const bool iso = KERNEL_FAMILY[kernel_id].iso;
+    out->kind = KERNEL_FAMILY[kernel_id].kind;
+    out->iso = iso;
     out->d = d;
     out->sig = theta[0];
     for (int k = 0; k < FVGP_MAX_DIM; ++k) out->invl[k] = 0.0;
@@ -290,22 +292,9 @@ int launch_kmat(fvgp_handle *h, const KmatDesc &k) {
     for (int i = 0; i < FVGP_MAX_DIM; ++i) a.invl[i] = k.invl[i];
     a.vec_ok = ((k.ldk & 1) == 0 && ((uintptr_t)k.K & 15) == 0) ? 1 : 0;
     dim3 grid((unsigned)((k.n2 + 127) / 128), (unsigned)((k.n1 + 127) / 128)), block(256);
-#define GO(KIND, D) hipLaunchKernelGGL((kmat_kernel<KIND, D>), grid, block, 0, h->stream, a)
-#define GOD(KIND)                                   \
-    switch (k.d) {                                  \
-        case 1: GO(KIND, 1); break;                 \
-        case 2: GO(KIND, 2); break;                 \
-        case 3: GO(KIND, 3); break;                 \
-        case 4: GO(KIND, 4); break;                 \
-        default: GO(KIND, 0); break;                \
-    }
-    switch (k.kind) {
-        case 0: GOD(0); break;
-        case 1: GOD(1); break;
-        default: GOD(2); break;
-    }
-#undef GOD
-#undef GO
+    dispatch_kind_dim(k.kind, k.d, [&](auto KIND, auto D) {
+        hipLaunchKernelGGL((kmat_kernel<decltype(KIND)::value, decltype(D)::value>), grid, block, 0, h->stream, a);
+    });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -313,7 +302,7 @@ int launch_kmat(fvgp_handle *h, const KmatDesc &k) {
 int launch_grad_trace(fvgp_handle *h, const GradDesc &g, int *nblocks_out) {
     GArgs a;
     a.x = g.k.x1; a.W = g.W; a.b = g.b; a.partial = g.partial;
-    a.n = g.k.n1; a.ldw = g.ldw; a.ldb = g.ldb; a.d = g.k.d; a.iso = g.kernel_id >= 3; a.ntheta = g.ntheta;
+    a.n = g.k.n1; a.ldw = g.ldw; a.ldb = g.ldb; a.d = g.k.d; a.iso = g.k.iso; a.ntheta = g.ntheta;
     a.sig = g.k.sig;
     for (int i = 0; i < FVGP_MAX_DIM; ++i) a.invl[i] = g.k.invl[i];
     const long T = (a.n + 127) / 128;
@@ -328,22 +317,9 @@ int launch_grad_trace(fvgp_handle *h, const GradDesc &g, int *nblocks_out) {
         nb = T * a.ntj;
     }
     *nblocks_out = (int)nb;
-#define GT(KIND, D) hipLaunchKernelGGL((grad_trace_kernel<KIND, D>), grid, block, 0, h->stream, a)
-#define GTD(KIND)                                   \
-    switch (a.d) {                                  \
-        case 1: GT(KIND, 1); break;                 \
-        case 2: GT(KIND, 2); break;                 \
-        case 3: GT(KIND, 3); break;                 \
-        case 4: GT(KIND, 4); break;                 \
-        default: GT(KIND, 0); break;                \
-    }
-    switch (g.k.kind) {
-        case 0: GTD(0); break;
-        case 1: GTD(1); break;
-        default: GTD(2); break;
-    }
-#undef GTD
-#undef GT
+    dispatch_kind_dim(g.k.kind, a.d, [&](auto KIND, auto D) {
+        hipLaunchKernelGGL((grad_trace_kernel<decltype(KIND)::value, decltype(D)::value>), grid, block, 0, h->stream, a);
+    });
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -16,6 +16,7 @@
 // As in batch.hip launch order is the only synchronisation and no result depends on the batch: every sum of a prediction row sees that
 // row and its problem's factor only, in a fixed order.
 #include "radial.h"
+#include "kernel_family.h"
 
 namespace {
 
@@ -210,22 +211,9 @@ int launch_cross_batch(fvgp_handle *h, int kind, const double *xr, int64_t nr, c
     CBArgs a;
     a.xr = xr; a.xc = xc; a.K = K; a.tab = tab; a.nr = nr; a.nc = nc; a.ldk = ldk; a.k_stride = k_stride; a.d = d; a.lower = lower;
     const dim3 grid((unsigned)(cols / TILE), (unsigned)(rows / TILE), (unsigned)B), block(256);
-#define GO(KIND, D) hipLaunchKernelGGL((cross_batch_kernel<KIND, D>), grid, block, 0, h->stream, a)
-#define GOD(KIND)                                   \
-    switch (d) {                                    \
-        case 1: GO(KIND, 1); break;                 \
-        case 2: GO(KIND, 2); break;                 \
-        case 3: GO(KIND, 3); break;                 \
-        case 4: GO(KIND, 4); break;                 \
-        default: GO(KIND, 0); break;                \
-    }
-    switch (kind) {
-        case 0: GOD(0); break;
-        case 1: GOD(1); break;
-        default: GOD(2); break;
-    }
-#undef GOD
-#undef GO
+    dispatch_kind_dim(kind, d, [&](auto KIND, auto D) {
+        hipLaunchKernelGGL((cross_batch_kernel<decltype(KIND)::value, decltype(D)::value>), grid, block, 0, h->stream, a);
+    });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -236,11 +224,9 @@ int launch_post_epilogue_batch(fvgp_handle *h, int kind, double *KV, int64_t kv_
     a.KV = KV; a.info = info; a.tab = tab; a.mean = mean; a.var = var;
     a.kv_stride = kv_stride; a.ld = ld; a.n = n; a.dim = dim; a.P = P; a.p0 = p0; a.pc = pc; a.ncol = ncol;
     const dim3 grid((unsigned)((pc + PE_ROWS - 1) / PE_ROWS), (unsigned)B), block(64 * PE_ROWS);
-    switch (kind) {
-        case 0: hipLaunchKernelGGL(post_epilogue_batch_kernel<0>, grid, block, 0, h->stream, a); break;
-        case 1: hipLaunchKernelGGL(post_epilogue_batch_kernel<1>, grid, block, 0, h->stream, a); break;
-        default: hipLaunchKernelGGL(post_epilogue_batch_kernel<2>, grid, block, 0, h->stream, a); break;
-    }
+    dispatch_kind(kind, [&](auto KIND) {
+        hipLaunchKernelGGL(post_epilogue_batch_kernel<decltype(KIND)::value>, grid, block, 0, h->stream, a);
+    });
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -15,6 +15,7 @@
 // P is, whichever points share the call and wherever the caller cuts a long list of points into calls.
 // Per entry: one exp, one rsq (radial_grad), d subtractions and 2 d + 2 n_dirs + 2 (+ 2 n_dirs + 2 with W) fused multiply-adds.
 #include "radial.h"
+#include "kernel_family.h"
 
 namespace {
 
@@ -181,26 +182,11 @@ int fvgp_hip_posterior_grad(fvgp_handle *h, int kernel_id, const double *x, int6
     const int64_t S = pg_slices(n);
     if (S > 65535) { fvgp_set_error("posterior_grad: n too large"); return -4; }
     const dim3 grid((unsigned)((P + 63) / 64), (unsigned)S), block(256);
-#define GO(KIND, D)                                                                                               \
-    do {                                                                                                          \
-        if (W) hipLaunchKernelGGL((posterior_grad_kernel<KIND, D, true>), grid, block, 0, h->stream, a);          \
-        else hipLaunchKernelGGL((posterior_grad_kernel<KIND, D, false>), grid, block, 0, h->stream, a);           \
-    } while (0)
-#define GOD(KIND)                                   \
-    switch (d) {                                    \
-        case 1: GO(KIND, 1); break;                 \
-        case 2: GO(KIND, 2); break;                 \
-        case 3: GO(KIND, 3); break;                 \
-        case 4: GO(KIND, 4); break;                 \
-        default: GO(KIND, 0); break;                \
-    }
-    switch (k.kind) {
-        case 0: GOD(0); break;
-        case 1: GOD(1); break;
-        default: GOD(2); break;
-    }
-#undef GOD
-#undef GO
+    dispatch_kind_dim(k.kind, d, [&](auto KIND, auto D) {
+        constexpr int KD = decltype(KIND)::value, DIM = decltype(D)::value;
+        if (W) hipLaunchKernelGGL((posterior_grad_kernel<KD, DIM, true>), grid, block, 0, h->stream, a);
+        else hipLaunchKernelGGL((posterior_grad_kernel<KD, DIM, false>), grid, block, 0, h->stream, a);
+    });
     HIPCHK(hipGetLastError());
     const int64_t total = (2 + 2 * (int64_t)n_dirs) * P;
     hipLaunchKernelGGL(posterior_grad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,

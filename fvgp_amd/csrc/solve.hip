@@ -958,9 +958,9 @@ int launch_rows_dot(fvgp_handle *h, const double *KT, int64_t ldk, const double 
     if ((ldk & 1) || ((uintptr_t)KT & 15)) return -2;
     const int C = ncol <= 1 ? 1 : ncol <= 2 ? 2 : ncol <= 4 ? 4 : 8;
     dim3 grid((unsigned)P), block(256);
-#define GO(CC) hipLaunchKernelGGL((rows_dot_kernel<CC>), grid, block, 0, h->stream, KT, (long)ldk, alpha, (long)lda, ncol, (long)n, out, (long)ldo)
-    if (C == 1) GO(1); else if (C == 2) GO(2); else if (C == 4) GO(4); else GO(8);
-#undef GO
+#define LAUNCH(CC) hipLaunchKernelGGL((rows_dot_kernel<CC>), grid, block, 0, h->stream, KT, (long)ldk, alpha, (long)lda, ncol, (long)n, out, (long)ldo)
+    if (C == 1) LAUNCH(1); else if (C == 2) LAUNCH(2); else if (C == 4) LAUNCH(4); else LAUNCH(8);
+#undef LAUNCH
     HIPCHK(hipGetLastError());
     return 0;
 }

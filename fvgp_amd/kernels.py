@@ -18,14 +18,20 @@ from . import _lib
 class NativeKernel:
     """A stationary kernel the HIP assembly kernel implements (fvgp_hip_kmat)."""
 
-    def __init__(self, name, doc):
+    def __init__(self, name, kind, isotropic, doc):
         self.name = name
         self.kernel_id = _lib.KERNEL_IDS[name]
-        self.isotropic = name.endswith("_iso")
+        self.kind = kind                # the radial function: "rbf", "matern32" or "matern52"
+        self.isotropic = isotropic      # one length scale (hps[1]) for every dimension
         self.__doc__ = doc
 
     def n_hyperparameters(self, dim):
         return 2 if self.isotropic else dim + 1
+
+    def length_scales(self, hps, d):
+        """the length scale of each of the d dimensions, from a hyperparameter vector in this kernel's layout"""
+        hps = np.asarray(hps, dtype=np.float64)
+        return np.full(d, hps[1]) if self.isotropic else hps[1:1 + d]
 
     def __call__(self, x1, x2, hps, args=None):
         from .device import default_handle
@@ -41,12 +47,12 @@ class NativeKernel:
         return f"<fvgp_amd native kernel {self.name}>"
 
 
-rbf_ard = NativeKernel("rbf_ard", "hps[0] * exp(-r^2/2), r = anisotropic distance with hps[1:]")
-matern32_ard = NativeKernel("matern32_ard", "the reference default kernel: hps[0] * (1+sqrt3 r) exp(-sqrt3 r)")
-matern52_ard = NativeKernel("matern52_ard", "hps[0] * (1 + sqrt5 r + 5 r^2/3) exp(-sqrt5 r)")
-rbf_iso = NativeKernel("rbf_iso", "hps[0] * exp(-|x-x'|^2 / (2 hps[1]^2))")
-matern32_iso = NativeKernel("matern32_iso", "hps[0] * (1+sqrt3 d/l) exp(-sqrt3 d/l), l = hps[1]")
-matern52_iso = NativeKernel("matern52_iso", "hps[0] * (1 + sqrt5 d/l + 5 d^2/(3 l^2)) exp(-sqrt5 d/l), l = hps[1]")
+rbf_ard = NativeKernel("rbf_ard", "rbf", False, "hps[0] * exp(-r^2/2), r = anisotropic distance with hps[1:]")
+matern32_ard = NativeKernel("matern32_ard", "matern32", False, "the reference default kernel: hps[0] * (1+sqrt3 r) exp(-sqrt3 r)")
+matern52_ard = NativeKernel("matern52_ard", "matern52", False, "hps[0] * (1 + sqrt5 r + 5 r^2/3) exp(-sqrt5 r)")
+rbf_iso = NativeKernel("rbf_iso", "rbf", True, "hps[0] * exp(-|x-x'|^2 / (2 hps[1]^2))")
+matern32_iso = NativeKernel("matern32_iso", "matern32", True, "hps[0] * (1+sqrt3 d/l) exp(-sqrt3 d/l), l = hps[1]")
+matern52_iso = NativeKernel("matern52_iso", "matern52", True, "hps[0] * (1 + sqrt5 d/l + 5 d^2/(3 l^2)) exp(-sqrt5 d/l), l = hps[1]")
 
 NATIVE = {k.name: k for k in (rbf_ard, matern32_ard, matern52_ard, rbf_iso, matern32_iso, matern52_iso)}
 
@@ -76,21 +82,20 @@ def kernel_dx(name, x_pred, x_data, hps):
 
     (the 1 / r of dr/dx cancels: all three are finite at coincident points).  This is the formula fvgp_hip_posterior_grad evaluates
     on the device (csrc/posterior_grad.hip, radial.h), written in numpy: its CPU comparator and its documentation."""
-    if isinstance(name, NativeKernel):
-        name = name.name
-    if name not in NATIVE:
+    kernel = name if isinstance(name, NativeKernel) else NATIVE.get(name)
+    if kernel is None:
         raise ValueError(f"unknown native kernel {name!r}; choose from {sorted(NATIVE)}")
     x_pred = np.asarray(x_pred, dtype=np.float64)
     x_data = np.asarray(x_data, dtype=np.float64)
     hps = np.asarray(hps, dtype=np.float64)
     d = x_pred.shape[1]
-    ls = np.full(d, hps[1]) if name.endswith("_iso") else hps[1:1 + d]
+    ls = kernel.length_scales(hps, d)
     delta = x_pred[:, None, :] - x_data[None, :, :]                    # (P, N, D)
     e = delta / ls
     r2 = np.einsum("pnd,pnd->pn", e, e)
-    if name.startswith("rbf"):
+    if kernel.kind == "rbf":
         cf = hps[0] * np.exp(-0.5 * r2)
-    elif name.startswith("matern32"):
+    elif kernel.kind == "matern32":
         cf = 3.0 * hps[0] * np.exp(-np.sqrt(3.0) * np.sqrt(r2))
     else:
         a = np.sqrt(5.0) * np.sqrt(r2)

@@ -19,7 +19,7 @@ import torch
 from fvgp_amd import _lib
 from oracle import fvgp_oracle as orc
 
-NAMES = {0: "rbf_ard", 1: "matern32_ard", 2: "matern52_ard", 3: "rbf_iso", 4: "matern32_iso", 5: "matern52_iso"}
+NAMES = {kid: name for name, kid in _lib.KERNEL_IDS.items()}
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _CPU = None
 
