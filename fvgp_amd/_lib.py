@@ -566,7 +566,9 @@ class Handle(DistCalls):
         return np.array(g[:], dtype=np.float64)
 
     def grad_trace(self, kernel_id, x, theta, W, b, partial):
-        """1/2 sum_jk (W_jk - b_j b_k) dK_jk/dtheta_i over the symmetric W (lower triangle read); b a 1-d view or None."""
+        """1/2 sum_jk (W_jk - b_j b_k) dK_jk/dtheta_i over the symmetric W (lower triangle read); b a 1-d view or None.
+        W: 16-byte aligned with an even row stride >= pad128(n) (status -9 otherwise): the pass loads whole 128-column tile rows.
+        partial: device scratch of T (T + 1) / 2 * ntheta doubles, T = ceil(n / 128)."""
         t, tp, nt = _theta(theta)
         g = (ctypes.c_double * nt)()
         n, d = x.shape
@@ -575,7 +577,8 @@ class Handle(DistCalls):
         return np.array(g[:], dtype=np.float64)
 
     def grad_trace_cols(self, kernel_id, x, theta, W, col0, ncols, b, partial):
-        """the same pass over the slab W (n, >= ncols) of columns [col0, col0 + ncols) of the symmetric matrix"""
+        """the same pass over the slab W (n, >= pad128(ncols)) of columns [col0, col0 + ncols) of the symmetric matrix (col0 % 128 == 0;
+        a row stride below pad128(ncols): status -9); partial: ceil(n / 128) * ceil(ncols / 128) * ntheta doubles"""
         t, tp, nt = _theta(theta)
         g = (ctypes.c_double * nt)()
         n, d = x.shape

@@ -1721,7 +1721,8 @@ int fvgp_hip_grad_trace(fvgp_handle *h, int kernel_id, const double *x, int64_t 
     if (n <= 0) return -4;
     if (!theta) return -6;
     if (!W) return -8;
-    if (ldw < n || (ldw & 1) || ((uintptr_t)W & 15)) return -9;
+    // a wave loads whole 128-column tile rows of W before it tests the column: every row must own its tile columns
+    if (ldw < pad128(n) || (ldw & 1) || ((uintptr_t)W & 15)) { fvgp_set_error("grad_trace needs ldw >= padded_dim(n), even, 16-byte aligned W"); return -9; }
     if (b && ldb < 1) return -11;
     if (!partial) return -12;
     if (!grad_host) return -13;
@@ -1739,7 +1740,7 @@ int fvgp_hip_grad_trace_cols(fvgp_handle *h, int kernel_id, const double *x, int
     if (!W) return -8;
     if (col0 < 0 || col0 % TILE || col0 >= n) return -10;
     if (ncols <= 0) return -11;
-    if (ldw < ncols || (ldw & 1) || ((uintptr_t)W & 15)) return -9;
+    if (ldw < pad128(ncols) || (ldw & 1) || ((uintptr_t)W & 15)) { fvgp_set_error("grad_trace_cols needs ldw >= 128 * ceil(ncols / 128), even, 16-byte aligned W"); return -9; }
     if (b && ldb < 1) return -13;
     if (!partial) return -14;
     if (!grad_host) return -15;

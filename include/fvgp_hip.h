@@ -421,6 +421,8 @@ int fvgp_hip_loglik_grad(fvgp_handle *h, int kernel_id, const double *x, int64_t
 /* the trace part of the gradient on its own: grad_host[i] = 1/2 sum_jk (W_jk - b_j b_k) dK_jk/dtheta_i over the
  * n x n symmetric W (lower triangle read; b with stride ldb, or NULL for the pure trace 1/2 tr(W dK_i)).  The row-sharded
  * gradient calls it on each rank's partial Gram matrix inv(L)_p^T inv(L)_p (gp_marginal_likelihood.py:262-300).
+ * W: 16-byte aligned, ldw even and >= padded_dim(n) (-9 otherwise, before anything is launched): the pass loads whole
+ * 128-column tile rows, so every row of W owns the columns up to the end of its last tile (their values are never used).
  * partial: device scratch of T(T+1)/2 * ntheta doubles, T = ceil(n/128).  Synchronises. */
 int fvgp_hip_grad_trace(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
                         const double *theta_host, int ntheta, const double *W, int64_t ldw,
@@ -428,6 +430,7 @@ int fvgp_hip_grad_trace(fvgp_handle *h, int kernel_id, const double *x, int64_t 
 /* the same pass over a SLAB of columns [col0, col0 + ncols) of the symmetric matrix (col0 % 128 == 0): W (n, ldw) holds those
  * columns only, entries with row >= column are read.  The row-sharded gradient walks its partial Gram matrix of inv(L) slab by
  * slab, so that no rank ever holds an N x N buffer; the slabs' results add up to fvgp_hip_grad_trace's.
+ * W: 16-byte aligned, ldw even and >= 128 * ceil(ncols/128) (-9 otherwise, before anything is launched), for the same reason.
  * partial: ceil(n/128) * ceil(ncols/128) * ntheta doubles (device scratch). */
 int fvgp_hip_grad_trace_cols(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
                              const double *theta_host, int ntheta, const double *W, int64_t ldw, int64_t col0, int64_t ncols,

@@ -249,7 +249,7 @@ int fvgp_hip_grad_trace(fvgp_handle *h, int kernel_id, const double *x, int64_t 
     if (n <= 0) return -4;
     if (!theta) return -6;
     if (!W) return -8;
-    if (ldw < n) return -9;
+    if (ldw < pad128(n) || (ldw & 1)) return -9;           /* the device pass loads whole tile rows: include/fvgp_hip.h */
     if (!grad_host) return -13;
     return grad_trace(kernel_id, x, n, d, theta, ntheta, W, ldw, b, ldb, grad_host);
 }
@@ -417,6 +417,9 @@ int fvgp_hip_grad_trace_cols(fvgp_handle *h, int kernel_id, const double *x, int
     if (!x) return -3;
     if (!theta) return -6;
     if (!W) return -8;
+    if (col0 < 0 || col0 % 128 || col0 >= n) return -10;
+    if (ncols <= 0) return -11;
+    if (ldw < pad128(ncols) || (ldw & 1)) return -9;       /* 128 * ceil(ncols / 128), as the device pass needs */
     if (!grad) return -15;
     kdesc k;
     int rc = kdesc_from_theta(kernel_id, d, theta, ntheta, &k);

@@ -125,6 +125,29 @@ def test_cpu_twin_error_codes(cpu):
     assert L.fvgp_hip_loglik(h, 0, ptr(x), c_l(4), 2, dbl(th), 3, None, ptr(x), 1, ptr(A), c_l(128), ptr(x), out, None) == -8
 
 
+def test_cpu_twin_checks_the_gradient_trace_leading_dimension(cpu):
+    """include/fvgp_hip.h: fvgp_hip_grad_trace wants ldw >= padded_dim(n), fvgp_hip_grad_trace_cols ldw >= 128 ceil(ncols / 128) (the
+    device pass loads whole tile rows); both answer -9 before they compute anything, and take the smallest allowed value"""
+    L, h = cpu
+    n = 300
+    x = np.random.default_rng(0).random((n, 2))
+    th = np.array([1.0, 0.3, 0.4])
+    W = np.zeros((384, 384))
+    g = (c_d * 3)(*([np.nan] * 3))
+
+    def full(ldw):
+        return L.fvgp_hip_grad_trace(h, 0, ptr(x), c_l(n), 2, dbl(th), 3, ptr(W), c_l(ldw), None, c_l(1), None, g)
+
+    def cols(ldw, col0, ncols):
+        return L.fvgp_hip_grad_trace_cols(h, 0, ptr(x), c_l(n), 2, dbl(th), 3, ptr(W), c_l(ldw), c_l(col0), c_l(ncols), None, c_l(1), None, g)
+    assert full(300) == -9 and full(382) == -9 and full(385) == -9
+    assert cols(200, 128, 200) == -9 and cols(128, 128, 129) == -9 and cols(254, 128, 172) == -9
+    assert cols(128, 64, 128) == -10 and cols(128, 384, 128) == -10 and cols(128, 128, 0) == -11
+    assert all(np.isnan(v) for v in g)
+    assert full(384) == 0 and list(g) == [0.0, 0.0, 0.0]
+    assert cols(256, 128, 172) == 0 and cols(128, 256, 44) == 0 and cols(256, 256, 256) == 0
+
+
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "fvgp")), reason="the reference tree only exists in the build container")
 @pytest.mark.parametrize("name", ["G2_rbf_n512_d3.npz", "G3_matern52_n512_d3.npz"])
 def test_the_reference_drives_the_abi_through_its_plug_points(cpu, name):
