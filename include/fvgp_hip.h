@@ -493,7 +493,11 @@ int fvgp_hip_potrs_cols(fvgp_handle *h, const double *L, int64_t n, int64_t ldl,
  * C (M,N) = alpha * opA * opB + beta * C on fp64 MFMA.  M, N multiples of 128, K of 16.
  *   a_kmajor == 0: A stored (M,K) row-major;  != 0: A stored (K,M) row-major (A^T product)
  *   b_nmajor == 0: B stored (N,K) row-major (C = A B^T); != 0: B stored (K,N) row-major
- *   lower != 0: only 128x128 tiles with row-tile >= col-tile are computed (SYRK-style)
+ *   lower != 0: only 128x128 tiles with row-tile >= col-tile are computed (SYRK-style); every non-zero value means the same, and the
+ *     tiles above the diagonal keep their bits
+ *   K == 0 is valid (A and B are not read): every computed tile becomes beta * C, and with beta == 0 it becomes zero without C being read
+ * Returns -5 for M, N not multiples of 128 or K not a multiple of 16, -9 for A or B not 16-byte aligned or a leading dimension of
+ * theirs that is odd or not below 2^21, -9 / -11 / -14 for a NULL A / B / C; nothing is launched and C is untouched then.
  * With fewer than 256 output tiles and K >= 1024 the K range is split over workgroups and the partial tiles added in a fixed
  * order (handle scratch, at most 64 MB): same result on every run, another rounding than the unsplit product.  The split needs
  * C 16-byte aligned with an even ldc; a C that is not takes the unsplit product (state it if rounding must not depend on where a
