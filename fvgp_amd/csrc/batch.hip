@@ -1,10 +1,10 @@
 // Batched log-likelihood: GPMarginalLikelihood.log_likelihood (gp_marginal_likelihood.py:137-179) at B hyperparameter vectors on
-// the same x, in one call (fvgp_hip_loglik_batch, api.hip).  The callers are population-based optimisers -- the reference's
+// the same x, in one call (fvgp_hip_loglik_batch, batch_api.hip).  The callers are population-based optimisers -- the reference's
 // differential_evolution (fvgp/gp_training.py:66-76) scores a whole population per generation -- and grid scans.
 //
 // At the sizes training runs at one evaluation leaves most of the chip idle: a padded 512 x 512 factor is four latency-bound
 // 128-column steps.  B independent factorisations side by side fill it.  Every launch here covers all B problems (one more grid
-// dimension for the problem index), sequenced by fvgp_hip_loglik_batch (api.hip):
+// dimension for the problem index), sequenced by fvgp_hip_loglik_batch (batch_api.hip):
 //     assembly (kmat_batch_kernel) -> appended rows (rhs_rows_batch_kernel) ->
 //     factorisation by recursive halving over the block columns: per 128 columns a leaf (leaf_batch_kernel) and a panel TRSM
 //     (strided-batch GEMM by the block inverse), between two halves ONE update of the trailing lower tiles (strided-batch GEMM,

@@ -116,7 +116,7 @@ struct fvgp_handle {
     // followed by one K = 4096 update with nothing beside it, beat look-ahead at every size measured (N=2000 0.95 -> 0.75 ms,
     // 8000 5.7 -> 5.1, 20000 46.9 -> 45.6, 50000 620 -> 595 on the same box); `lookahead_min` = 4608 restores the old schedule
     int64_t lookahead_min = (int64_t)1 << 40;
-    int posterior_halves = 1;         // posterior covariance at >= 512 points: two halves of the points side by side on two streams (api.hip)
+    int posterior_halves = 1;         // posterior covariance at >= 512 points: two halves of the points side by side on two streams (tri_solve.hip)
     int64_t outer_block_small = 512, small_threshold = 12288;   // panel width for the last `small_threshold` rows (potrf_driver)
     int lookahead = 1;
     double *tr_ws = nullptr; size_t tr_ws_cap = 0;    // trsm_lower with few columns: the right-hand sides transposed
@@ -189,7 +189,27 @@ struct GemmDesc {
     // (elements).  Excludes split-K.
     int batch_y = 1, batch_z = 1;
     int64_t a_by = 0, a_bz = 0, b_by = 0, b_bz = 0, c_by = 0, c_bz = 0;
+
+    // what is special about a product, chained behind gemm_desc(); anything used at a site or two (rev_m, bc_*, split*) is assigned
+    GemmDesc &lower_tiles() { lower = 1; return *this; }
+    GemmDesc &lower_rowshard(int scale, int off) { lower = 2; lower_scale = scale; lower_off = off; return *this; }
+    GemmDesc &with_role(int r) { role = r; return *this; }
+    GemmDesc &k_begin(int64_t b0, int64_t bi, int64_t bj) { kb0 = b0; kbi = bi; kbj = bj; return *this; }
+    // k_end(K), the "explicit K range": the product is the same, but a launch with one takes the 128-tile kernel whatever its shape
+    // or batch (gemm_takes_small_tiles) -- the batched evaluations say it on every product, so that a problem's bits do not depend
+    // on how many problems ride in the launch
+    GemmDesc &k_end(int64_t e0, int64_t ei = 0, int64_t ej = 0) { ke0 = e0; kei = ei; kej = ej; return *this; }
+    GemmDesc &batched(int64_t nz, int64_t az, int64_t bz, int64_t cz) { batch_z = (int)nz; a_bz = az; b_bz = bz; c_bz = cz; return *this; }
+    GemmDesc &batched_y(int64_t ny, int64_t ay, int64_t by, int64_t cy) { batch_y = (int)ny; a_by = ay; b_by = by; c_by = cy; return *this; }
 };
+// C = alpha op(A) op(B) + beta C over every tile and the whole of K, one problem: the part every product states
+inline GemmDesc gemm_desc(int a_kmajor, int b_nmajor, int64_t M, int64_t N, int64_t K, double alpha, const double *A, int64_t lda,
+                          const double *B, int64_t ldb, double beta, double *C, int64_t ldc) {
+    GemmDesc d{};
+    d.a_kmajor = a_kmajor; d.b_nmajor = b_nmajor; d.M = M; d.N = N; d.K = K; d.alpha = alpha; d.beta = beta;
+    d.A = A; d.lda = lda; d.B = B; d.ldb = ldb; d.C = C; d.ldc = ldc;
+    return d;
+}
 int launch_gemm(fvgp_handle *h, const GemmDesc &g);
 bool gemm_takes_small_tiles(const fvgp_handle *h, const GemmDesc &g);   // the launch runs gemm_f64_small_kernel, not gemm_f64_kernel
 void gemm_release_tables(fvgp_handle *h);
@@ -299,9 +319,16 @@ int launch_post_epilogue_batch(fvgp_handle *h, int kind, double *KV, int64_t kv_
                                const int *info, const double *tab, double *mean, double *var, int64_t P, int64_t p0, int64_t pc, int64_t B);
 int launch_s_finish_batch(fvgp_handle *h, double *S, int64_t s_stride, int64_t lds, int64_t Pp, const int *info, int64_t n, int64_t B);
 
+// host helpers shared by the units of the C ABI (api.hip unless noted)
+int check_square(const void *A, int64_t n, int64_t ld, int argA, int argn, int argld);
 int ensure_linv(fvgp_handle *h, const double *L, int64_t n, int64_t ldl);
+int ensure_winv(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, int64_t WB = 1024, int64_t upto = 0);
 int ensure_scratch(fvgp_handle *h, int64_t np);
 int fvgp_ensure_side(fvgp_handle *h);
+int potrf_driver(fvgp_handle *h, double *A, int64_t n, int64_t lda, int *info_host, int *info_dev = nullptr, bool enqueue_only = false,
+                 int64_t np_force = 0, bool skip_inverses = false);
+int potrs_vec(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, double *B, int64_t nrhs, int64_t ldb, bool backward);               // tri_solve.hip
+int trsm_fwd_gemm_t(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, double *BT, int64_t rows, int64_t ldbt, int64_t block = 0);   // tri_solve.hip
 void fvgp_ipc_destroy(fvgp_handle *h);
 int fvgp_ipc_check(fvgp_handle *h);      // 2200 once a poll of the direct collectives has given up (ask AFTER synchronising), else 0
 int fvgp_read_back(fvgp_handle *h, const double *dev, double *host, int count);

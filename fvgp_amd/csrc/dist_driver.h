@@ -8,7 +8,7 @@
 // The driver below sequences that evaluation -- assembly of the rank's rows, per panel: gather of the diagonal block,
 // factorisation of the tall panel, all-gather of the panel factor, trailing update of the rank's block rows -- over a
 // backend that supplies the operations:
-//   * libfvgp_hip.so instantiates it with its HIP kernels, two streams and RCCL (api.hip: fvgp_hip_loglik_dist);
+//   * libfvgp_hip.so instantiates it with its HIP kernels, two streams and RCCL (dist.hip: fvgp_hip_loglik_dist);
 //   * the CPU twin of the ABI (oracle/cpu_abi, test infrastructure) instantiates it with host loops, so the partition
 //     and collective logic runs under gloo in the build container, without a GPU -- the analogue of the reference's
 //     in-process Dask cluster fixture (tests/test_fvgp.py:20).

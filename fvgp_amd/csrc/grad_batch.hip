@@ -1,10 +1,10 @@
 // Batched log-likelihood gradient: GPMarginalLikelihood.neg_log_likelihood_gradient's kernel part (gp_marginal_likelihood.py:224-309)
-// at B hyperparameter vectors on the same x, in one call (fvgp_hip_loglik_grad_batch, api.hip) -- what a multi-start gradient
+// at B hyperparameter vectors on the same x, in one call (fvgp_hip_loglik_grad_batch, batch_api.hip) -- what a multi-start gradient
 // optimiser asks for at every step.  After the batched factorisation of batch.hip (every leaf's block inverse kept), per problem on
 // its own square:
 //     z from the appended rows, identity padding back, the leaf inverses into the diagonal tiles (grad_init_batch_kernel) ->
 //     W = L^-1 in place by recursive halving over the block columns, inv([[A,0],[C,D]]) = [[A^-1,0],[-D^-1 C A^-1, D^-1]]
-//     (two strided-batch GEMMs per halving, api.hip) ->
+//     (two strided-batch GEMMs per halving, batch_api.hip) ->
 //     b = W^T z = KV^-1 (y - m) (wtz_batch_kernel) ->
 //     W^T into the second square (transpose_lower_batch_kernel), KV^-1 = W^T W over W (one strided-batch GEMM, potri_kminor's layout) ->
 //     fused trace (grad_trace_batch_kernel: grad_trace_kernel's arithmetic) -> per-problem fixed-order sum (grad_reduce_batch_kernel).

@@ -1,5 +1,5 @@
 // Batched posterior: GPposterior.posterior_mean / posterior_covariance (gp_posterior.py:139-182, 229-288, 120-136) at B hyperparameter
-// vectors on the same x and the same prediction points, in one call (fvgp_hip_posterior_batch, api.hip) -- what averaging a prediction
+// vectors on the same x and the same prediction points, in one call (fvgp_hip_posterior_batch, batch_api.hip) -- what averaging a prediction
 // over the theta samples of an MCMC run, comparing the end points of a multi-start optimiser or scanning a theta grid ask for.
 //
 // With V = L^-1 k(x, x*) and z = L^-1 (y - m):   mean = V^T z,   var = k(x*, x*) - colsumsq(V),   S = k(x*, x*) - V^T V
@@ -7,7 +7,7 @@
 // more appended rows: k(x*, x; theta_b) placed UNDER each problem's square leaves the factorisation as V^T.  Per problem the scratch is
 //     rows 0 .. dim - 1            the square of fvgp_hip_loglik_batch (z^T in rows n .. n + ncol - 1, columns 0 .. n - 1)
 //     rows dim .. dim + chunk - 1  one chunk of prediction rows, columns 0 .. n - 1 = V^T after the factorisation
-// and the launches, each over all B problems (sequenced in api.hip), are
+// and the launches, each over all B problems (sequenced in batch_api.hip), are
 //     cross assembly (cross_batch_kernel) -> the recursion of batch.hip over rows >= dim (or, for a later chunk of points, its
 //     solve-only pass by the kept leaf inverses) -> epilogue (post_epilogue_batch_kernel): per prediction row the mean per y column and
 //     the variance, then the row's columns n .. dim - 1 zeroed (after the factorisation column n + c holds -mean_c / L_jj: no part of

@@ -117,7 +117,9 @@ int fvgp_hip_stream_destroy(void *stream);
  *       (2048 / 1024: width of those blocks up to 1024 prediction points; 1024 beyond) ("order"), "posterior_halves" (1: 512-1024
  *       points as two halves on two streams) ("order"), "potri_kminor" (1: POTRI on (M,K) x (N,K) products only) ("order");
  *   diagnostics: "chain_stamps" / "leaf_stamps" (device pointers, 0 = off: in-kernel timestamps of the panel kernel's hand-offs /
- *       the leaf's phases). */
+ *       the leaf's phases).
+ * The library reads no environment variable.  The Python binding (fvgp_amd/_lib.py, Handle) applies FVGP_<KEY>=<integer> for the keys
+ * it lists -- every key above but "profile" and the two diagnostics pointers -- once, when it creates a handle. */
 int fvgp_hip_set_option(fvgp_handle *h, const char *key, int64_t value);
 /* Option "chain_verify" (0/1, default 0): every in-launch hand-off of the resident panel kernel (csrc/chain.hip: a solved block row,
  * a factored diagonal block with its tile inverses) carries a checksum of its payload, taken by the producer from what it stores and
