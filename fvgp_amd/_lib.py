@@ -35,6 +35,7 @@ SYMBOLS = [
     "fvgp_hip_loglik_grad_batch", "fvgp_hip_loglik_grad_batch_workspace_bytes",
     "fvgp_hip_posterior_batch", "fvgp_hip_posterior_batch_workspace_bytes",
     "fvgp_hip_posterior_grad", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_potrs_cols",
+    "fvgp_hip_loo", "fvgp_hip_loo_workspace_bytes",
 ]
 BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
 
@@ -168,6 +169,11 @@ def posterior_grad_workspace_bytes(n, P, n_dirs):
     return int(lib().fvgp_hip_posterior_grad_workspace_bytes(int(n), int(P), int(n_dirs)))
 
 
+def loo_workspace_bytes(n):
+    """bytes of the caller-owned vector scratch of Handle.loo (fvgp_hip_loo_workspace_bytes); -1 for n < 1"""
+    return int(lib().fvgp_hip_loo_workspace_bytes(int(n)))
+
+
 def lib():
     """Load (once) and return the ctypes library with argtypes set."""
     global _lib
@@ -235,6 +241,10 @@ def lib():
     L.fvgp_hip_posterior_grad_workspace_bytes.argtypes = [c_l, c_l, c_i]
     L.fvgp_hip_posterior_grad_workspace_bytes.restype = c_l
     L.fvgp_hip_potrs_cols.argtypes = [c_p, c_p, c_l, c_l, c_p, c_l, c_l]
+    L.fvgp_hip_loo.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, c_p, c_l,
+                               P_d, c_p, c_p, P_d, c_p, c_p]
+    L.fvgp_hip_loo_workspace_bytes.argtypes = [c_l]
+    L.fvgp_hip_loo_workspace_bytes.restype = c_l
     L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
     L.fvgp_hip_grad_trace.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, P_d]
     L.fvgp_hip_posterior.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_p, c_l,
@@ -265,7 +275,7 @@ def lib():
     for s in SYMBOLS:
         if s not in ("fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_workspace_bytes", "fvgp_hip_dist_scratch",
                      "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes", "fvgp_hip_loglik_grad_batch_workspace_bytes",
-                     "fvgp_hip_posterior_batch_workspace_bytes", "fvgp_hip_posterior_grad_workspace_bytes"):
+                     "fvgp_hip_posterior_batch_workspace_bytes", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_loo_workspace_bytes"):
             getattr(L, s).restype = c_i
     _lib = L
     return L
@@ -670,6 +680,25 @@ class Handle(DistCalls):
                                              _ptr(alpha), int(ncol), int(component), _ptr(W), 0 if W is None else W.stride(0),
                                              int(n_dirs), _ptr(work), work.numel() * work.element_size(),
                                              _ptr(A_out), _ptr(q_out), _ptr(dm_out), _ptr(dv_out)), "fvgp_hip_posterior_grad")
+
+    def loo(self, kernel_id, x, theta, alpha, ncol, component, KV, work, ws, resid_out, var_out, u_out=None, mdiag_out=None, n=None):
+        """fvgp_hip_loo on the factor in KV (destroyed, as `work`): returns (out, grad) with out = [L_LOO, sum resid^2, sum log q_i,
+        number of q_i that are not positive and finite] and grad = dL_LOO/dtheta (kernel-owned entries, the rest 0).  u_out and
+        mdiag_out None: values only, grad is None and kernel_id, x, theta may be None (pass n then).  ws: a tensor of at least
+        loo_workspace_bytes(n) bytes; resid_out, var_out, u_out, mdiag_out: device n-vectors.  One synchronisation."""
+        want_grad = u_out is not None or mdiag_out is not None
+        if want_grad:
+            t, tp, nt = _theta(theta)
+            g = (ctypes.c_double * nt)()
+            n, d = x.shape
+        else:
+            tp, nt, g, d = None, 0, None, 0 if x is None else x.shape[1]
+            n = int(x.shape[0] if n is None else n)
+        out = (ctypes.c_double * 4)()
+        _check(lib().fvgp_hip_loo(self._h, int(kernel_id or 0), _ptr(x), n, d, tp, nt, _ptr(alpha), int(ncol), int(component),
+                                  _ptr(KV), KV.stride(0), _ptr(work), work.stride(0), _ptr(ws), ws.numel() * ws.element_size(),
+                                  out, _ptr(resid_out), _ptr(var_out), g, _ptr(u_out), _ptr(mdiag_out)), "fvgp_hip_loo")
+        return np.array(out[:], dtype=np.float64), (None if g is None else np.array(g[:], dtype=np.float64))
 
     def potrs_cols(self, L, n, B, nrhs):
         """Handle.potrs for nrhs % 128 == 0 columns whose bits do not depend on nrhs (fvgp_hip_potrs_cols)"""

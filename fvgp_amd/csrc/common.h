@@ -236,6 +236,7 @@ struct GradDesc {
     int ntheta;
     const double *W; int64_t ldw;   // lower triangle of KV^-1
     const double *b; int64_t ldb;   // KVinvY column (stride ldb)
+    const double *b2 = nullptr; int64_t ldb2 = 1;   // a second vector: the rank-one term becomes (b_j b2_k + b2_j b_k) / 2 (loo.hip)
     double *partial;                // device, nblocks x ntheta
     int64_t col0 = 0, ncols = 0;    // ncols > 0: W is the slab of columns [col0, col0 + ncols) (col0 % 128 == 0), its column 0 = matrix column col0
 };
@@ -332,3 +333,10 @@ int trsm_fwd_gemm_t(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, dou
 void fvgp_ipc_destroy(fvgp_handle *h);
 int fvgp_ipc_check(fvgp_handle *h);      // 2200 once a poll of the direct collectives has given up (ask AFTER synchronising), else 0
 int fvgp_read_back(fvgp_handle *h, const double *dev, double *host, int count);
+
+// leave-one-out cross-validation (loo.hip)
+int launch_loo_stats(fvgp_handle *h, const double *Q, int64_t ld, const double *alpha, int ncol, int component, int64_t n, int64_t np,
+                     double *resid, double *var, double *w, double *c, double *sc, double *part);
+int launch_symv_lower(fvgp_handle *h, const double *Q, int64_t ld, int64_t np, const double *w, double *part, int64_t ldp, int64_t n, double *u);
+int launch_mirror_scale(fvgp_handle *h, double *Q, int64_t ld, int64_t np, const double *sc);
+int launch_diag_copy(fvgp_handle *h, const double *M, int64_t ldm, int64_t n, double *out);

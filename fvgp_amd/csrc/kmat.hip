@@ -16,6 +16,7 @@
 // the fly from x, replacing the (H,N,N) dK_dH tensor and the batched LU solve of
 // gp_marginal_likelihood.py:260-274.
 #include "radial.h"
+#include <type_traits>
 #include "kernel_family.h"
 
 namespace {
@@ -131,6 +132,8 @@ __global__ __launch_bounds__(256) void kmat_kernel(KArgs a) {
 // fused gradient trace:  partial[block][i] = sum over the block's tile of
 //      w_jk * (W_jk - b_j b_k) * dK_jk/dtheta_i ,   w = 1 on the diagonal, 2 below it
 // (W symmetric, only its lower triangle is read).  theta = [sig, l_1..l_d] or [sig, l].
+// TWO (compile time): the rank-one term is symmetric in two vectors, W_jk - (b_j b2_k + b2_j b_k) / 2 -- the leave-one-out gradient
+// (loo.hip), u^T dK alpha = sum_jk (u_j alpha_k + alpha_j u_k) / 2 dK_jk for symmetric dK.  TWO = false is the kernel as it always was.
 //   d/dsig = phi(r)                                       (all kinds)
 //   rbf   : d/dl_i = k * D_i^2 / l_i^3                    (derived)
 //   m32   : d/dl_i = sig * 3 * D_i^2 / l_i^3 * exp(-sqrt3 r)   (gp_prior.py:421-436, kernels.py:121-141)
@@ -145,9 +148,10 @@ struct GArgs {
     int ntj, tj0;             // column-slab mode (ntj > 0): W holds the tile columns tj0 .. tj0 + ntj - 1 only (its column 0 is
     long wcol0;               //   matrix column wcol0); grid = (tile rows, ntj)
 };
+struct GArgs2 : GArgs { const double *b2; long ldb2; };    // TWO: the second vector (the one-vector kernels keep their argument block)
 
-template <int KIND, int D>   // D == 0: runtime dimension (<= FVGP_MAX_DIM); a 16-deep predicated loop per entry made d = 3 run at a tenth of the memory rate
-__global__ __launch_bounds__(256) void grad_trace_kernel(GArgs a) {
+template <int KIND, int D, bool TWO = false>   // D == 0: runtime dimension (<= FVGP_MAX_DIM); a 16-deep predicated loop per entry made d = 3 run at a tenth of the memory rate
+__global__ __launch_bounds__(256) void grad_trace_kernel(std::conditional_t<TWO, GArgs2, GArgs> a) {
     int ti, tj;
     long pidx = blockIdx.x;
     if (a.ntj > 0) {          // slab: one block per (tile row, tile column of the window); tiles above the diagonal hold nothing
@@ -169,6 +173,7 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(GArgs a) {
     const int d = D ? D : a.d;
     __shared__ double sx[128 * DD];
     __shared__ double sb[128];
+    __shared__ double sb2[TWO ? 128 : 1];
     __shared__ double sred[4][DD + 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long row0 = (long)ti * 128, col0 = (long)tj * 128;
@@ -178,6 +183,7 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(GArgs a) {
         sx[rr * DD + kk] = a.x[gr * d + kk];
     }
     if (tid < 128) { long gr = row0 + tid; sb[tid] = (a.b && gr < a.n) ? a.b[gr * a.ldb] : 0.0; }
+    if constexpr (TWO) { if (tid < 128) { long gr = row0 + tid; sb2[tid] = gr < a.n ? a.b2[gr * a.ldb2] : 0.0; } }
     const long c0 = col0 + 2 * lane, c1 = c0 + 1;
     double u0[DD], u1[DD], il[DD];
     const long g0 = c0 < a.n ? c0 : a.n - 1, g1 = c1 < a.n ? c1 : a.n - 1;
@@ -187,6 +193,13 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(GArgs a) {
         else { u0[k] = 0.0; u1[k] = 0.0; il[k] = 0.0; }
     }
     const double bc0 = (a.b && c0 < a.n) ? a.b[c0 * a.ldb] : 0.0, bc1 = (a.b && c1 < a.n) ? a.b[c1 * a.ldb] : 0.0;
+    double b2c0 = 0.0, b2c1 = 0.0;
+    if constexpr (TWO) { b2c0 = c0 < a.n ? a.b2[c0 * a.ldb2] : 0.0; b2c1 = c1 < a.n ? a.b2[c1 * a.ldb2] : 0.0; }
+    // the rank-one term of row point rr and column point h (br = sb[rr])
+    auto rank1 = [&](const int rr, const int h, const double br) {
+        if constexpr (TWO) return 0.5 * (br * (h ? b2c1 : b2c0) + sb2[rr] * (h ? bc1 : bc0));
+        else return br * (h ? bc1 : bc0);
+    };
     __syncthreads();
 
     double gs = 0.0;          // d/dsig accumulator
@@ -219,10 +232,10 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(GArgs a) {
         for (int rr = wave; rr < 128; rr += 8, Wp += 8 * a.ldw) {
             const double2_t wa = *reinterpret_cast<const double2_t *>(Wp), wb = *reinterpret_cast<const double2_t *>(Wp + 4 * a.ldw);
             const double bra = sb[rr], brb = sb[rr + 4];
-            entry(rr, 0, 2.0 * (wa[0] - bra * bc0));
-            entry(rr, 1, 2.0 * (wa[1] - bra * bc1));
-            entry(rr + 4, 0, 2.0 * (wb[0] - brb * bc0));
-            entry(rr + 4, 1, 2.0 * (wb[1] - brb * bc1));
+            entry(rr, 0, 2.0 * (wa[0] - rank1(rr, 0, bra)));
+            entry(rr, 1, 2.0 * (wa[1] - rank1(rr, 1, bra)));
+            entry(rr + 4, 0, 2.0 * (wb[0] - rank1(rr + 4, 0, brb)));
+            entry(rr + 4, 1, 2.0 * (wb[1] - rank1(rr + 4, 1, brb)));
         }
     } else {
         for (int rr = wave; rr < 128; rr += 4, Wp += 4 * a.ldw) {
@@ -234,7 +247,7 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(GArgs a) {
             for (int h = 0; h < 2; ++h) {
                 const long c = h ? c1 : c0;
                 if (c > row || c >= a.n) continue;
-                entry(rr, h, (c == row ? 1.0 : 2.0) * ((h ? w2[1] : w2[0]) - br * (h ? bc1 : bc0)));
+                entry(rr, h, (c == row ? 1.0 : 2.0) * ((h ? w2[1] : w2[0]) - rank1(rr, h, br)));
             }
         }
     }
@@ -300,8 +313,10 @@ int launch_kmat(fvgp_handle *h, const KmatDesc &k) {
 }
 
 int launch_grad_trace(fvgp_handle *h, const GradDesc &g, int *nblocks_out) {
-    GArgs a;
+    GArgs2 a;
     a.x = g.k.x1; a.W = g.W; a.b = g.b; a.partial = g.partial;
+    a.b2 = g.b2; a.ldb2 = g.ldb2;
+    if (g.b2 && !g.b) { fvgp_set_error("grad trace: a second vector needs the first"); return -1; }
     a.n = g.k.n1; a.ldw = g.ldw; a.ldb = g.ldb; a.d = g.k.d; a.iso = g.k.iso; a.ntheta = g.ntheta;
     a.sig = g.k.sig;
     for (int i = 0; i < FVGP_MAX_DIM; ++i) a.invl[i] = g.k.invl[i];
@@ -318,7 +333,8 @@ int launch_grad_trace(fvgp_handle *h, const GradDesc &g, int *nblocks_out) {
     }
     *nblocks_out = (int)nb;
     dispatch_kind_dim(g.k.kind, a.d, [&](auto KIND, auto D) {
-        hipLaunchKernelGGL((grad_trace_kernel<decltype(KIND)::value, decltype(D)::value>), grid, block, 0, h->stream, a);
+        if (g.b2) hipLaunchKernelGGL((grad_trace_kernel<decltype(KIND)::value, decltype(D)::value, true>), grid, block, 0, h->stream, a);
+        else hipLaunchKernelGGL((grad_trace_kernel<decltype(KIND)::value, decltype(D)::value>), grid, block, 0, h->stream, (GArgs)a);
     });
     HIPCHK(hipGetLastError());
     return 0;

@@ -26,6 +26,7 @@ from . import _lib
 from . import kernels as _kernels
 from .device import default_handle
 from .gp_lin_alg import NonPositiveDefiniteError, _non_pd_message
+from .gp_loo import LOOMixin
 from .gp_validation import ValidationMixin
 
 # device-memory budget of the B squares one batched evaluation factors at once (GP.log_likelihood_batch; args["batch_max_bytes"]
@@ -78,7 +79,7 @@ def _mixture_moments(m, v, w):
     return mean, within + between, within, between
 
 
-class GP(ValidationMixin):
+class GP(ValidationMixin, LOOMixin):
     def __init__(
         self,
         x_data,
@@ -1586,7 +1587,10 @@ class GP(ValidationMixin):
         guarded = (accept_only_if_improved and not user_objective and
                    (callable(method) or method in ("local", "hgdl", "adam")))
         incumbent = self._hps.copy() if guarded else None
-        ll_incumbent = self.log_likelihood() if guarded else None
+        # what "improved" means follows the objective that was trained (args["training_objective"], gp_training.train)
+        loo = self.args.get("training_objective") == "loo"
+        score, score_name = (self.loo_log_predictive, "LOO log predictive probability") if loo else (self.log_likelihood, "log marginal likelihood")
+        ll_incumbent = score() if guarded else None
         hps = gp_training.train(self, hyperparameter_bounds, init_hyperparameters, method=method,
                                 pop_size=pop_size, tolerance=tolerance, max_iter=max_iter,
                                 local_optimizer=local_optimizer, constraints=constraints, info=info, seed=seed,
@@ -1596,9 +1600,9 @@ class GP(ValidationMixin):
                                 mcmc_prior=mcmc_prior, mcmc_args={} if mcmc_args is None else mcmc_args,
                                 mcmc_prop_distrs=mcmc_prop_distrs)
         self.set_hyperparameters(np.asarray(hps, dtype=np.float64))
-        if guarded and not self.log_likelihood() >= ll_incumbent:          # exact mode: strict comparison (gp.py:1158-1160)
-            warnings.warn(f"Training with method=`{method}` returned hyperparameters with a lower log marginal likelihood "
-                          f"({self.log_likelihood()} vs. {ll_incumbent}); they were rejected and the previous hyperparameters "
+        if guarded and not score() >= ll_incumbent:          # exact mode: strict comparison (gp.py:1158-1160)
+            warnings.warn(f"Training with method=`{method}` returned hyperparameters with a lower {score_name} "
+                          f"({score()} vs. {ll_incumbent}); they were rejected and the previous hyperparameters "
                           "kept. Pass `accept_only_if_improved=False` to accept them anyway.")
             self.set_hyperparameters(incumbent)
         return self._hps

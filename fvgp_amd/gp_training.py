@@ -282,8 +282,22 @@ def train(gp, bounds, init_hyperparameters, method="mcmc", pop_size=20, toleranc
     adam_starts = 0
     if objective_function is None and objective_function_gradient is None and method == "adam":
         adam_starts = int(getattr(gp, "args", {}).get("adam_starts", 0) or 0)
+    # GP(..., args={"training_objective": "loo"}): the leave-one-out log predictive probability (gp_loo.py) takes the marginal
+    # likelihood's place wherever the caller hands in no objective; the batched evaluations have no LOO twin
+    objective = getattr(gp, "args", {}).get("training_objective", "marginal_likelihood")
+    if objective not in ("marginal_likelihood", "loo"):
+        raise ValueError(f"args['training_objective'] must be 'marginal_likelihood' or 'loo', got {objective!r}")
+    loo = objective == "loo"
+    if loo and (batch_population or adam_starts >= 2):
+        raise ValueError("args['training_objective'] = 'loo' cannot be combined with 'batch_population' or 'adam_starts': "
+                         "there is no batched LOO evaluation")
     if objective_function is None and method in ("mcmc", "global", "local", "adam"):
-        objective_function = gp.log_likelihood if method == "mcmc" else gp.neg_log_likelihood
+        if loo:
+            objective_function = gp.loo_log_predictive if method == "mcmc" else gp.neg_loo_log_predictive
+            if objective_function_gradient is None and method in ("local", "adam"):
+                objective_function_gradient = gp.neg_loo_log_predictive_gradient
+        else:
+            objective_function = gp.log_likelihood if method == "mcmc" else gp.neg_log_likelihood
     if objective_function_gradient is None and method in ("local", "adam"):
         objective_function_gradient = gp.neg_log_likelihood_gradient
     if method == "mcmc":

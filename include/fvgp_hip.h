@@ -491,6 +491,37 @@ int64_t fvgp_hip_posterior_grad_workspace_bytes(int64_t n, int64_t P, int n_dirs
  * travel with it.  Here a column of the solution has the same bits in every call (the results fvgp_hip_posterior_grad builds on). */
 int fvgp_hip_potrs_cols(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, double *B, int64_t nrhs, int64_t ldb);
 
+/* loo: leave-one-out cross-validation in closed form, with the exact gradient of the LOO log predictive probability in the kernel's
+ * hyperparameters (csrc/loo.hip; Rasmussen & Williams 5.4.2).  With Q = KV^-1, q_i = Q_ii and alpha = Q (y - m)[:, component]:
+ *     resid_out[i] = y_i - mu_i = alpha_i / q_i        var_out[i] = sigma^2_i = 1 / q_i   (of the NOISY observation)
+ *     L_LOO = sum_i (log q_i - alpha_i^2 / q_i) / 2 - n / 2 log 2 pi                      (sum_i log p(y_i | y_-i))
+ * and with w = alpha / q, c_i = (1 + alpha_i^2 / q_i) / (2 q_i), u = Q w, M = Q diag(c) Q:
+ *     grad_host[j] = dL_LOO/dtheta_j = sum_kl ((u_k alpha_l + alpha_k u_l) / 2 - M_kl) dK_kl/dtheta_j
+ * -- one symmetric N^3 product for all hyperparameters and one pass of the fused trace kernel; the derivative of the quantity to be
+ * MAXIMISED, 0 for hyperparameters the kernel does not own.  A caller adds the terms of a diagonal noise derivative dV,
+ * sum_k dV_k (u_k alpha_k - M_kk), and of a mean derivative, u^T dm, from u_out and mdiag_out.
+ *   KV        the factor L as fvgp_hip_loglik / fvgp_hip_potrf leave it (padded); destroyed
+ *   work      a second padded square; destroyed
+ *   alpha     (padded_dim(n), ncol) device, column `component` is read
+ *   ws        caller-owned device scratch of at least fvgp_hip_loo_workspace_bytes(n) bytes (vectors only), ws_bytes its size
+ *   out_host  4 doubles: L_LOO, sum resid^2, sum log q_i, the number of q_i that are not positive and finite (non-zero: the first
+ *             three, and the gradient, are NaN)
+ *   resid_out, var_out   device n-vectors
+ *   grad_host NULL: values only -- the call is POTRI and one pass over the diagonal, KV holds exactly what fvgp_hip_potri leaves, and
+ *             kernel_id, x, d, theta are not read (the path of kernel callables).  Else ntheta doubles, and
+ *   u_out, mdiag_out     device n-vectors u and diag(M), required with grad_host
+ * One host synchronisation per call; no atomics: the same inputs give the same bits on every run.  Flops: 2/3 n^3 (POTRI) + n^3.
+ * Errors (argument numbers, nothing is launched): -3 x, -4 n, -6 theta, -8 alpha, -9 ncol, -10 component, -11 / -12 KV / ld,
+ * -13 / -14 work / ldw, -15 ws, -16 ws_bytes, -17 .. -19 out_host, resid_out, var_out, -21 u_out, -22 mdiag_out; kernel id, d and
+ * ntheta as fvgp_hip_kmat. */
+int fvgp_hip_loo(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
+                 const double *theta_host, int ntheta, const double *alpha, int ncol, int component,
+                 double *KV, int64_t ld, double *work, int64_t ldw, double *ws, int64_t ws_bytes,
+                 double *out_host, double *resid_out, double *var_out,
+                 double *grad_host, double *u_out, double *mdiag_out);
+/* bytes of the caller-owned scratch of fvgp_hip_loo: (3 padded_dim(n) + 4 padded_dim(n) / 128) doubles; -1 for n < 1 */
+int64_t fvgp_hip_loo_workspace_bytes(int64_t n);
+
 /* ---- building blocks exported for the parity tests --------------------------------------
  * C (M,N) = alpha * opA * opB + beta * C on fp64 MFMA.  M, N multiples of 128, K of 16.
  *   a_kmajor == 0: A stored (M,K) row-major;  != 0: A stored (K,M) row-major (A^T product)
