@@ -36,6 +36,7 @@ SYMBOLS = [
     "fvgp_hip_posterior_batch", "fvgp_hip_posterior_batch_workspace_bytes",
     "fvgp_hip_posterior_grad", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_potrs_cols",
     "fvgp_hip_loo", "fvgp_hip_loo_workspace_bytes",
+    "fvgp_hip_normal_fill", "fvgp_hip_mvn_sample", "fvgp_hip_mvn_sample_workspace_bytes",
 ]
 BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
 
@@ -174,6 +175,11 @@ def loo_workspace_bytes(n):
     return int(lib().fvgp_hip_loo_workspace_bytes(int(n)))
 
 
+def mvn_sample_workspace_bytes(n, nsamp):
+    """bytes of the caller-owned scratch of Handle.mvn_sample (fvgp_hip_mvn_sample_workspace_bytes); -1 for n < 1 or nsamp < 1"""
+    return int(lib().fvgp_hip_mvn_sample_workspace_bytes(int(n), int(nsamp)))
+
+
 def lib():
     """Load (once) and return the ctypes library with argtypes set."""
     global _lib
@@ -245,6 +251,11 @@ def lib():
                                P_d, c_p, c_p, P_d, c_p, c_p]
     L.fvgp_hip_loo_workspace_bytes.argtypes = [c_l]
     L.fvgp_hip_loo_workspace_bytes.restype = c_l
+    c_u = ctypes.c_uint64
+    L.fvgp_hip_normal_fill.argtypes = [c_p, c_u, c_u, c_l, c_l, c_p, c_l, c_l, c_l]
+    L.fvgp_hip_mvn_sample.argtypes = [c_p, c_p, c_l, c_l, c_p, c_u, c_u, c_l, c_l, c_p, c_l, c_p, c_l, c_p, c_l]
+    L.fvgp_hip_mvn_sample_workspace_bytes.argtypes = [c_l, c_l]
+    L.fvgp_hip_mvn_sample_workspace_bytes.restype = c_l
     L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
     L.fvgp_hip_grad_trace.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, P_d]
     L.fvgp_hip_posterior.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_p, c_l,
@@ -275,7 +286,8 @@ def lib():
     for s in SYMBOLS:
         if s not in ("fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_workspace_bytes", "fvgp_hip_dist_scratch",
                      "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes", "fvgp_hip_loglik_grad_batch_workspace_bytes",
-                     "fvgp_hip_posterior_batch_workspace_bytes", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_loo_workspace_bytes"):
+                     "fvgp_hip_posterior_batch_workspace_bytes", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_loo_workspace_bytes",
+                     "fvgp_hip_mvn_sample_workspace_bytes"):
             getattr(L, s).restype = c_i
     _lib = L
     return L
@@ -699,6 +711,25 @@ class Handle(DistCalls):
                                   _ptr(KV), KV.stride(0), _ptr(work), work.stride(0), _ptr(ws), ws.numel() * ws.element_size(),
                                   out, _ptr(resid_out), _ptr(var_out), g, _ptr(u_out), _ptr(mdiag_out)), "fvgp_hip_loo")
         return np.array(out[:], dtype=np.float64), (None if g is None else np.array(g[:], dtype=np.float64))
+
+    def normal_fill(self, Z, seed=0, stream=0, row0=0, col0=0):
+        """fvgp_hip_normal_fill: Z[r][c] = z(seed, stream, row0 + r, col0 + c) over the whole 2-d device tensor Z (a view with a
+        larger row stride is fine: only its rows x cols entries are written).  Asynchronous."""
+        assert Z.dim() == 2 and Z.stride(1) == 1, "Z must be a 2-d tensor with contiguous rows"
+        _check(lib().fvgp_hip_normal_fill(self._h, int(seed), int(stream), int(row0), int(col0), _ptr(Z), Z.shape[0], Z.shape[1],
+                                          Z.stride(0)), "fvgp_hip_normal_fill")
+
+    def mvn_sample(self, L, n, Y, mean=None, seed=0, stream=0, samp0=0, Z_out=None, work=None):
+        """fvgp_hip_mvn_sample: Y[s] = mean + tril(L) z(seed, stream, :, samp0 + s) for the Y.shape[0] rows of the device tensor Y
+        (nsamp, >= n); L the padded factor of an n x n matrix, mean a device n-vector or None, Z_out None or a device (n, >= nsamp)
+        tensor that receives the normals, work None (allocated here) or a flat device tensor of mvn_sample_workspace_bytes(n, nsamp)
+        bytes.  Asynchronous; a sample's bits depend on (seed, stream, its index) and L only."""
+        nsamp = int(Y.shape[0])
+        if work is None:
+            work = self.empty(max(1, mvn_sample_workspace_bytes(n, nsamp)) // 8)
+        _check(lib().fvgp_hip_mvn_sample(self._h, _ptr(L), int(n), L.stride(0), _ptr(mean), int(seed), int(stream), int(samp0), nsamp,
+                                         _ptr(Y), Y.stride(0), _ptr(Z_out), 0 if Z_out is None else Z_out.stride(0),
+                                         _ptr(work), work.numel() * 8), "fvgp_hip_mvn_sample")
 
     def potrs_cols(self, L, n, B, nrhs):
         """Handle.potrs for nrhs % 128 == 0 columns whose bits do not depend on nrhs (fvgp_hip_potrs_cols)"""

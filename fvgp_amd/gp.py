@@ -27,6 +27,7 @@ from . import kernels as _kernels
 from .device import default_handle
 from .gp_lin_alg import NonPositiveDefiniteError, _non_pd_message
 from .gp_loo import LOOMixin
+from .gp_sampling import SamplingMixin
 from .gp_validation import ValidationMixin
 
 # device-memory budget of the B squares one batched evaluation factors at once (GP.log_likelihood_batch; args["batch_max_bytes"]
@@ -79,7 +80,7 @@ def _mixture_moments(m, v, w):
     return mean, within + between, within, between
 
 
-class GP(ValidationMixin, LOOMixin):
+class GP(ValidationMixin, LOOMixin, SamplingMixin):
     def __init__(
         self,
         x_data,
@@ -903,8 +904,10 @@ class GP(ValidationMixin, LOOMixin):
         if isinstance(x_out, np.ndarray):
             assert np.ndim(x_out) == 1, "wrong dim in x_out, has to be 1-d"
 
-    def _posterior_device(self, x_pred, hps, L, alpha, want_cov):
-        """k(x_data, x_pred) assembly, mean = k^T alpha, S = kk - k^T KV^-1 k on the device."""
+    def _posterior_device(self, x_pred, hps, L, alpha, want_cov, keep_device=False):
+        """k(x_data, x_pred) assembly, mean = k^T alpha, S = kk - k^T KV^-1 k on the device.  keep_device: where S is formed on this
+        device it is returned as the padded device square it was formed in (padded_dim(P) rows, the leading P x P valid) instead of a
+        host array (gp_sampling.py factors it in place); the branches that form S on the host return it as they always do."""
         if self._sharded:
             sh = self._sh if L is None else L
             return sh.posterior(x_pred, want_cov=want_cov)
@@ -926,13 +929,15 @@ class GP(ValidationMixin, LOOMixin):
                   else self._host_kernel(x_pred, x_pred, hps))
             return mean_h, kk - k.T @ np.asarray(self._linalg_callables[1](obj, k), dtype=np.float64).reshape(k.shape)
         if self._native is not None and want_cov and P > self._posterior_chunk:
-            return self._posterior_chunked(x_pred, hps, L, alpha)
+            return self._posterior_chunked(x_pred, hps, L, alpha, keep_device)
         mean = H.empty(P, ncol)
         kx = H.empty(self._np, Pp)
         if self._native is not None:
             S = H.empty(Pp, Pp) if want_cov else None
             H.posterior(self._native.kernel_id, self._x_dev, hps, L, alpha, ncol, xp, kx, mean, None, S)
             H.sync()
+            if keep_device and S is not None:
+                return mean.cpu().numpy(), S
             return mean.cpu().numpy(), (None if S is None else H.to_host(S[:P, :P]))
         # slow path: host cross-covariances, device solves
         kx.zero_()
@@ -949,9 +954,9 @@ class GP(ValidationMixin, LOOMixin):
         S[:P, :P] = H.to_device(self._host_kernel(x_pred, x_pred, hps))
         H.gemm(1, 1, 0, Pp, Pp, self._np, -1.0, kx, kx, 1.0, S)                            # kk - v^T v, v = L^-1 k
         H.sync()
-        return mean_h, S[:P, :P].cpu().numpy()
+        return mean_h, (S if keep_device else S[:P, :P].cpu().numpy())
 
-    def _posterior_chunked(self, x_pred, hps, L, alpha):
+    def _posterior_chunked(self, x_pred, hps, L, alpha, keep_device=False):
         """Posterior mean and covariance at MANY prediction points with bounded device memory (gp_posterior.py:120-136,229-288 form
         k (N x P), L^-1 k and the P x P result in one piece each).  The points go through the device in chunks of
         `posterior_chunk` (4096): fvgp_hip_posterior per chunk gives its mean, its diagonal block of S and leaves
@@ -1038,7 +1043,7 @@ class GP(ValidationMixin, LOOMixin):
         if on_device:
             H.symmetrize(S_dev, P)
             H.sync()
-            return mean_h, H.to_host(S_dev[:P, :P])
+            return mean_h, (S_dev if keep_device else H.to_host(S_dev[:P, :P]))
         H.sync()
         return mean_h, S_h
 

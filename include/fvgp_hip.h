@@ -522,6 +522,40 @@ int fvgp_hip_loo(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int 
 /* bytes of the caller-owned scratch of fvgp_hip_loo: (3 padded_dim(n) + 4 padded_dim(n) / 128) doubles; -1 for n < 1 */
 int64_t fvgp_hip_loo_workspace_bytes(int64_t n);
 
+/* ---- sampling ------------------------------------------------------------------------------
+ * Joint draws f ~ N(mean, L L^T) for Thompson sampling and Monte-Carlo acquisition functions (csrc/sample.hip).  The reference has no
+ * counterpart: its users take numpy.linalg.cholesky of the posterior_covariance result (gp_posterior.py:229-288) on the host.
+ *
+ * The generator is a pure function z(seed, stream, i, j) with no state: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key
+ * increments 0x9E3779B9 / 0xBB67AE85) on the counter (i, j, lo32(stream), hi32(stream)) with the key (lo32(seed), hi32(seed)); with its
+ * output words w0..w3: u1 = (((w0 | w1 << 32) >> 11) + 0.5) 2^-53, u2 the same from w2, w3, z = sqrt(-2 ln u1) cos(2 pi u2).  i is the
+ * point (row) index and j the sample index, both below 2^32.  One counter per element: z(seed, stream, i, j) never depends on its
+ * neighbours, on the launch shape or on how a caller cuts a request into calls (tests/samples_ref.py is the numpy twin).
+ *
+ * normal_fill: Z[r][c] = z(seed, stream, row0 + r, col0 + c); rows x cols doubles at leading dimension ldz; nothing outside that block
+ * is written; asynchronous.  Errors (argument numbers, nothing is launched): -6 Z NULL, -7 rows < 1, -8 cols < 1, -9 ldz < cols,
+ * -4 / -5 row0 + rows / col0 + cols past 2^32 (or a negative offset). */
+int fvgp_hip_normal_fill(fvgp_handle *h, uint64_t seed, uint64_t stream, int64_t row0, int64_t col0,
+                         double *Z, int64_t rows, int64_t cols, int64_t ldz);
+/* Y[s][p] = mean[p] + sum_{q <= p} L[p][q] * z(seed, stream, q, samp0 + s),  s < nsamp, p < n.
+ * L: factor as fvgp_hip_potrf leaves it (padded); its strict upper triangle is never read, and what its padding holds does not reach Y.
+ * Y (nsamp, ldy >= n) row-major device; mean (n) device or NULL; Z_out NULL or (n, ldz >= nsamp): the normals used.
+ * work: caller-owned scratch of fvgp_hip_mvn_sample_workspace_bytes(n, nsamp) bytes, 16-byte aligned.  Asynchronous.
+ * The product runs on the 128-tile GEMM kernel in its explicit-K-range form (whatever the shape, never the 64-tile kernel, never a
+ * split K): the diagonal 128-tiles of L, copied into `work` with their upper halves zeroed, times their block rows of Z, then the
+ * tiles below the diagonal with the K range of a tile row ending at its diagonal tile.  An entry of Y is a sum over its row of L and
+ * its column of Z in an order the row alone fixes, so A SAMPLE'S BITS DO NOT DEPEND ON nsamp, ON samp0 OR ON WHAT ELSE IS IN THE
+ * CALL: sample samp0 + s is the same whether it is drawn alone, as part of a longer call or in a call that starts elsewhere.
+ * Errors (argument numbers, nothing is launched): -2 .. -4 L, n, ldl as fvgp_hip_potrf (ldl below 2^21), -8 samp0 (samp0 + nsamp
+ * past 2^32), -9 nsamp (< 1, or padded_dim(nsamp) not below 2^21: draw more in several calls), -10 / -11 Y / ldy, -13 ldz,
+ * -14 / -15 work / work_bytes. */
+int fvgp_hip_mvn_sample(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, const double *mean,
+                        uint64_t seed, uint64_t stream, int64_t samp0, int64_t nsamp,
+                        double *Y, int64_t ldy, double *Z_out, int64_t ldz, double *work, int64_t work_bytes);
+/* bytes of the caller-owned scratch of fvgp_hip_mvn_sample: (2 padded_dim(n) padded_dim(nsamp) + 128 padded_dim(n)) doubles -- the
+ * normals, the product and the masked diagonal tiles; -1 for n < 1 or nsamp < 1 */
+int64_t fvgp_hip_mvn_sample_workspace_bytes(int64_t n, int64_t nsamp);
+
 /* ---- building blocks exported for the parity tests --------------------------------------
  * C (M,N) = alpha * opA * opB + beta * C on fp64 MFMA.  M, N multiples of 128, K of 16.
  *   a_kmajor == 0: A stored (M,K) row-major;  != 0: A stored (K,M) row-major (A^T product)
