@@ -37,6 +37,7 @@ SYMBOLS = [
     "fvgp_hip_posterior_grad", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_potrs_cols",
     "fvgp_hip_loo", "fvgp_hip_loo_workspace_bytes",
     "fvgp_hip_normal_fill", "fvgp_hip_mvn_sample", "fvgp_hip_mvn_sample_workspace_bytes",
+    "fvgp_hip_select_batch", "fvgp_hip_select_workspace_bytes",
 ]
 BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
 
@@ -180,6 +181,11 @@ def mvn_sample_workspace_bytes(n, nsamp):
     return int(lib().fvgp_hip_mvn_sample_workspace_bytes(int(n), int(nsamp)))
 
 
+def select_workspace_bytes(n, P, q):
+    """bytes of the caller-owned workspace of Handle.select_batch (fvgp_hip_select_workspace_bytes); -1 for n, P or q < 1"""
+    return int(lib().fvgp_hip_select_workspace_bytes(int(n), int(P), int(q)))
+
+
 def lib():
     """Load (once) and return the ctypes library with argtypes set."""
     global _lib
@@ -256,6 +262,10 @@ def lib():
     L.fvgp_hip_mvn_sample.argtypes = [c_p, c_p, c_l, c_l, c_p, c_u, c_u, c_l, c_l, c_p, c_l, c_p, c_l, c_p, c_l]
     L.fvgp_hip_mvn_sample_workspace_bytes.argtypes = [c_l, c_l]
     L.fvgp_hip_mvn_sample_workspace_bytes.restype = c_l
+    L.fvgp_hip_select_batch.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_d,
+                                        c_p, c_l, c_p, c_p, c_p, c_l]
+    L.fvgp_hip_select_workspace_bytes.argtypes = [c_l, c_l, c_i]
+    L.fvgp_hip_select_workspace_bytes.restype = c_l
     L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
     L.fvgp_hip_grad_trace.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, P_d]
     L.fvgp_hip_posterior.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_p, c_l,
@@ -287,7 +297,7 @@ def lib():
         if s not in ("fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_workspace_bytes", "fvgp_hip_dist_scratch",
                      "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes", "fvgp_hip_loglik_grad_batch_workspace_bytes",
                      "fvgp_hip_posterior_batch_workspace_bytes", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_loo_workspace_bytes",
-                     "fvgp_hip_mvn_sample_workspace_bytes"):
+                     "fvgp_hip_mvn_sample_workspace_bytes", "fvgp_hip_select_workspace_bytes"):
             getattr(L, s).restype = c_i
     _lib = L
     return L
@@ -350,7 +360,7 @@ class Handle(DistCalls):
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         _check(lib().fvgp_hip_create(ctypes.byref(self._h), self.device, ctypes.c_void_p(stream)), "fvgp_hip_create")
-        for key in ("schedule", "lookahead", "outer_block", "outer_block_big", "big_threshold", "inner_block", "small_tile_max", "small_tile_max_update", "tile_tables", "block_inverses", "k128_kernels", "leaf_tiles", "leaf_tiles_rows", "panel_recursive", "potri_kminor", "leaf_yield", "chain_yield", "lookahead_min", "posterior_halves", "posterior_block", "outer_block_small", "small_threshold", "panel_chain", "panel_chain_min", "cols_split", "cols_split_rows", "bwd_sweep", "fwd_sweep", "chain_verify", "chain_wide", "wide_block", "wide_block_big", "wide_threshold", "wide_inner", "wide_inner_rows", "chain_sleep_rows", "chain_single_rows", "chain_ahead"):        # tuning overrides, e.g. FVGP_OUTER_BLOCK=512
+        for key in ("schedule", "lookahead", "outer_block", "outer_block_big", "big_threshold", "inner_block", "small_tile_max", "small_tile_max_update", "tile_tables", "block_inverses", "k128_kernels", "leaf_tiles", "leaf_tiles_rows", "panel_recursive", "potri_kminor", "leaf_yield", "chain_yield", "lookahead_min", "posterior_halves", "posterior_block", "outer_block_small", "small_threshold", "panel_chain", "panel_chain_min", "cols_split", "cols_split_rows", "bwd_sweep", "fwd_sweep", "chain_verify", "chain_wide", "wide_block", "wide_block_big", "wide_threshold", "wide_inner", "wide_inner_rows", "chain_sleep_rows", "chain_single_rows", "chain_ahead", "select_block"):        # tuning overrides, e.g. FVGP_OUTER_BLOCK=512
             val = os.environ.get("FVGP_" + key.upper())
             if val is not None:
                 self.set_option(key, int(val))
@@ -730,6 +740,23 @@ class Handle(DistCalls):
         _check(lib().fvgp_hip_mvn_sample(self._h, _ptr(L), int(n), L.stride(0), _ptr(mean), int(seed), int(stream), int(samp0), nsamp,
                                          _ptr(Y), Y.stride(0), _ptr(Z_out), 0 if Z_out is None else Z_out.stride(0),
                                          _ptr(work), work.numel() * 8), "fvgp_hip_mvn_sample")
+
+    def select_batch(self, kernel_id, x, theta, L, xcand, var, q, idx_out, pick_var_out, noise=None, criterion=0, allow_repeats=False,
+                     tol=1e-12, G_out=None, work=None):
+        """fvgp_hip_select_batch: the greedy batch of q of the xcand.shape[0] candidates on the factor L of K + V over x.  var (P): in
+        the candidates' posterior variances, out their variances after the batch; noise (P) device vector or None (= 0); idx_out an
+        int64 device (q,) tensor (-1 from the first exhausted step on), pick_var_out (q); G_out None or a device (q, >= P) tensor;
+        criterion 0 = variance, 1 = information (needs noise > 0); work None (allocated here) or a flat device tensor of
+        select_workspace_bytes(n, P, q) bytes.  Asynchronous."""
+        t, tp, nt = _theta(theta)
+        n, d = x.shape
+        P = int(xcand.shape[0])
+        if work is None:
+            work = self.empty(max(1, select_workspace_bytes(n, P, q)) // 8)
+        _check(lib().fvgp_hip_select_batch(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(L), L.stride(0), _ptr(xcand), P,
+                                           _ptr(noise), _ptr(var), int(q), int(criterion), int(bool(allow_repeats)), float(tol),
+                                           _ptr(work), work.numel() * 8, _ptr(idx_out), _ptr(pick_var_out), _ptr(G_out),
+                                           0 if G_out is None else G_out.stride(0)), "fvgp_hip_select_batch")
 
     def potrs_cols(self, L, n, B, nrhs):
         """Handle.potrs for nrhs % 128 == 0 columns whose bits do not depend on nrhs (fvgp_hip_potrs_cols)"""

@@ -184,6 +184,10 @@ int fvgp_hip_set_option(fvgp_handle *h, const char *key, int64_t value) {
     if (!strcmp(key, "fwd_sweep")) { h->fwd_sweep = (int)value; return 0; }
     if (!strcmp(key, "posterior_halves")) { h->posterior_halves = (int)value; return 0; }
     if (!strcmp(key, "posterior_block")) { if (value != 1024 && value != 2048) return -3; h->posterior_block = value; return 0; }
+    if (!strcmp(key, "select_block")) {
+        if (value < 64 || value % 64 || value > 65536) { fvgp_set_error("select_block: a multiple of 64, at most 65536"); return -3; }
+        h->select_block = value; return 0;
+    }
     if (!strcmp(key, "outer_block_small")) { if (value < 0 || value % TILE) return -3; h->outer_block_small = value; return 0; }
     if (!strcmp(key, "small_threshold")) { h->small_threshold = value; return 0; }
     fvgp_set_error(std::string("unknown option ") + key);

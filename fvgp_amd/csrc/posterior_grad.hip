@@ -16,11 +16,12 @@
 // Per entry: one exp, one rsq (radial_grad), d subtractions and 2 d + 2 n_dirs + 2 (+ 2 n_dirs + 2 with W) fused multiply-adds.
 #include "radial.h"
 #include "kernel_family.h"
+#include "slice_sum.h"
 
 namespace {
 
-constexpr int PG_ROWS = 256;      // data rows per workgroup (slice)
-constexpr int PG_WAVE_ROWS = 64;  // ... per wave
+constexpr int PG_ROWS = SLICE_ROWS;            // data rows per workgroup (slice_sum.h)
+constexpr int PG_WAVE_ROWS = SLICE_WAVE_ROWS;  // ... per wave
 
 struct PGArgs {
     const double *x, *xp, *alpha, *W;
@@ -44,15 +45,7 @@ __global__ __launch_bounds__(256) void posterior_grad_kernel(PGArgs a) {
     const long p = (long)blockIdx.x * 64 + lane;
     const long pc = p < a.P ? p : a.P - 1;
 
-    for (int e = tid; e < PG_ROWS * d; e += 256) {
-        const int rr = e / d, kk = e - rr * d;
-        long gr = row0 + rr; if (gr >= a.n) gr = a.n - 1;
-        sx[rr * DD + kk] = a.x[gr * d + kk];
-    }
-    {
-        const long gr = row0 + tid;
-        sa[tid] = gr < a.n ? a.alpha[gr * a.ncol + a.comp] : 0.0;
-    }
+    slice_stage<DD>(sx, sa, a.x, a.alpha + a.comp, a.ncol, a.n, d, row0, tid);
     double u[DD];
 #pragma unroll
     for (int k = 0; k < DD; ++k) u[k] = k < d ? a.xp[pc * d + k] : 0.0;
@@ -62,8 +55,7 @@ __global__ __launch_bounds__(256) void posterior_grad_kernel(PGArgs a) {
     __syncthreads();
 
     const int r0 = wave * PG_WAVE_ROWS;
-    long left = a.n - row0 - r0;                              // rows of this wave that exist (<= 0: none)
-    const int rows = left >= PG_WAVE_ROWS ? PG_WAVE_ROWS : (left > 0 ? (int)left : 0);
+    const int rows = slice_wave_rows(a.n, row0, wave);        // rows of this wave that exist
     // (p < 64 ceil(P / 64) <= padded P <= ldw: inside the row for every lane)
     const double *Wp = HASW ? a.W + (row0 + r0) * a.ldw + p : nullptr;
 #pragma unroll 4
@@ -93,7 +85,7 @@ __global__ __launch_bounds__(256) void posterior_grad_kernel(PGArgs a) {
 
     __syncthreads();                                          // every wave is done with the staged rows
     if (wave > 0) {
-        double *red = sm + (wave - 1) * NACC * 64 + lane;
+        double *red = slice_parked(sm, NACC, wave, lane);
         red[0] = sA; red[64] = sq;
 #pragma unroll
         for (int k = 0; k < DD; ++k)
@@ -105,7 +97,7 @@ __global__ __launch_bounds__(256) void posterior_grad_kernel(PGArgs a) {
     double *out = a.part + (long)blockIdx.y * nacc * a.P + p;
 #pragma unroll
     for (int ww = 0; ww < 3; ++ww) {                             // ((wave 0 + wave 1) + wave 2) + wave 3
-        const double *red = sm + ww * NACC * 64 + lane;
+        const double *red = slice_parked(sm, NACC, ww + 1, lane);
         sA += red[0]; sq += red[64];
 #pragma unroll
         for (int k = 0; k < DD; ++k)
@@ -139,7 +131,7 @@ __global__ __launch_bounds__(256) void posterior_grad_reduce_kernel(const double
     else dv[p * nd + (s - 2 - nd)] = 2.0 * t;
 }
 
-int64_t pg_slices(int64_t n) { return (n + PG_ROWS - 1) / PG_ROWS; }
+int64_t pg_slices(int64_t n) { return slice_count(n); }
 
 }  // namespace
 

@@ -25,6 +25,7 @@ import numpy as np
 from . import _lib
 from . import kernels as _kernels
 from .device import default_handle
+from .gp_design import DesignMixin
 from .gp_lin_alg import NonPositiveDefiniteError, _non_pd_message
 from .gp_loo import LOOMixin
 from .gp_sampling import SamplingMixin
@@ -80,7 +81,7 @@ def _mixture_moments(m, v, w):
     return mean, within + between, within, between
 
 
-class GP(ValidationMixin, LOOMixin, SamplingMixin):
+class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin):
     def __init__(
         self,
         x_data,

@@ -116,6 +116,8 @@ int fvgp_hip_stream_destroy(void *stream);
  *       one launch), "block_inverses" (1: the posterior substitutes with inverted diagonal blocks) ("order"), "posterior_block"
  *       (2048 / 1024: width of those blocks up to 1024 prediction points; 1024 beyond) ("order"), "posterior_halves" (1: 512-1024
  *       points as two halves on two streams) ("order"), "potri_kminor" (1: POTRI on (M,K) x (N,K) products only) ("order");
+ *   batch selection: "select_block" (65536: candidates per pair of launches of fvgp_hip_select_batch, a multiple of 64, at most 65536;
+ *       the results have the same bits for every value);
  *   diagnostics: "chain_stamps" / "leaf_stamps" (device pointers, 0 = off: in-kernel timestamps of the panel kernel's hand-offs /
  *       the leaf's phases).
  * The library reads no environment variable.  The Python binding (fvgp_amd/_lib.py, Handle) applies FVGP_<KEY>=<integer> for the keys
@@ -552,6 +554,42 @@ int fvgp_hip_normal_fill(fvgp_handle *h, uint64_t seed, uint64_t stream, int64_t
 int fvgp_hip_mvn_sample(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, const double *mean,
                         uint64_t seed, uint64_t stream, int64_t samp0, int64_t nsamp,
                         double *Y, int64_t ldy, double *Z_out, int64_t ldz, double *work, int64_t work_bytes);
+/* Greedy batch selection (csrc/select.hip): which q of P candidate positions to measure next -- the pivoted Cholesky of the
+ * candidates' posterior covariance, column by column from the factor L of K + V, without the P x P matrix.  d = var (P) holds the
+ * conditional latent variances (in: the posterior variances, e.g. var_out of fvgp_hip_posterior; entries below 0 are taken as 0),
+ * s = noise (P) the candidates' noise variances (NULL = 0).  Step t = 0 .. q-1:
+ *     score_i = d_i (criterion 0) or d_i / s_i (criterion 1: monotone in the information gain 1/2 log(1 + d_i / s_i); the CALLER
+ *         guarantees every s_i > 0 -- the values live on the device and are not checked: with an s_i <= 0 the picks are undefined);
+ *         candidates already picked do not score unless allow_repeats != 0; j = the largest score, ties to the lowest index;
+ *     if d_j <= tol * max_i d_i(in), or nothing scores: idx_out[t..q-1] = -1, pick_var_out[t..q-1] = 0, and the call ends there
+ *         (decided on the device: the remaining steps' kernels return at once; var keeps what step t-1 left);
+ *     idx_out[t] = j, pick_var_out[t] = d_j, p = d_j + s_j;
+ *     r_i = k(x_i, x_j) - sum_n k(x_i, X_n) w_n with w = (K + V)^-1 k(X, x_j)      (column j of the posterior covariance)
+ *     c_i = (r_i - sum_{s<t} G[s][i] G[s][j]) / sqrt(p);   G[t][i] = c_i;   d_i <- max(d_i - c_i^2, 0)
+ * so that on return var is the latent variance every candidate would have after the picked points are measured with their noise, and
+ * G (rows up to the last pick) is the pivoted factor: sum_t G[t][i] G[t][k] is the covariance the measurements remove.  Nothing depends
+ * on y.  Every sum has a fixed order and the split of the data rows is a function of n alone: r_i, row t of G at candidate i and d_i have
+ * the same bits whatever P is, whichever candidates share the call, and for every "select_block".
+ *   x (n, d), xcand (P, d), noise (P) or NULL, var (P): device, row-major;  theta_host: the kernel's hyperparameters (host);
+ *   L: the factor (padded_dim(n) rows, ldl) as fvgp_hip_potrf leaves it;  idx_out (q) int64, pick_var_out (q): device;
+ *   G_out: NULL, or device (q, ldg) with ldg >= P (rows from the first exhausted step on are not written);
+ *   work: device, 16-byte aligned, at least fvgp_hip_select_workspace_bytes(n, P, q) bytes.
+ * Asynchronous on the handle's stream: the q steps are enqueued by this one call and nothing is read back; the host waits only if the
+ * handle has to allocate its own vector scratch or the block inverses of a factor it has not solved with before (the first call).
+ * Returns, before anything is enqueued and with no buffer touched, -1 .. -23 by argument number: -1 h, -2 unknown kernel_id, -3 x,
+ * -4 n < 1 (or more than 65535 slices of 256 rows), -5 d outside 1 .. FVGP_MAX_DIM, -6 theta_host, -7 too few hyperparameters,
+ * -8 L NULL or not 16-byte aligned, -9 ldl odd or below padded_dim(n), -10 xcand, -11 P < 1, -12 criterion 1 without noise, -13 var,
+ * -14 q < 1, -15 criterion not 0 / 1, -17 tol negative or no number, -18 work NULL or misaligned, -19 work_bytes too small,
+ * -20 idx_out, -21 pick_var_out, -23 ldg < P with a G_out. */
+int fvgp_hip_select_batch(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
+                          const double *theta_host, int ntheta, const double *L, int64_t ldl,
+                          const double *xcand, int64_t P, const double *noise, double *var,
+                          int q, int criterion, int allow_repeats, double tol,
+                          double *work, int64_t work_bytes, int64_t *idx_out, double *pick_var_out, double *G_out, int64_t ldg);
+/* bytes of the caller-owned workspace of fvgp_hip_select_batch: the padded column (padded_dim(n) doubles), the slot and the state words,
+ * three doubles per 64 candidates, one byte per candidate, the factor G (q P doubles) and the slices' partial sums, ceil(n / 256) min(P, 65536) doubles whatever
+ * P is -- O(P q), never P x P; -1 for n, P or q < 1 */
+int64_t fvgp_hip_select_workspace_bytes(int64_t n, int64_t P, int q);
 /* bytes of the caller-owned scratch of fvgp_hip_mvn_sample: (2 padded_dim(n) padded_dim(nsamp) + 128 padded_dim(n)) doubles -- the
  * normals, the product and the masked diagonal tiles; -1 for n < 1 or nsamp < 1 */
 int64_t fvgp_hip_mvn_sample_workspace_bytes(int64_t n, int64_t nsamp);
