@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("FVGP_HIP_LIB", os.path.join(CSRC, "libfvgp_hip.so")) 
 
 KERNEL_IDS = {"rbf_ard": 0, "matern32_ard": 1, "matern52_ard": 2,
               "rbf_iso": 3, "matern32_iso": 4, "matern52_iso": 5}
+_ISO_IDS = frozenset(v for k, v in KERNEL_IDS.items() if k.endswith("_iso"))
 FULL, LOWER = 0, 1
 PAD_NONE, PAD_IDENTITY, PAD_ZERO = 0, 1, 2
 TILE = 128
@@ -38,6 +39,7 @@ SYMBOLS = [
     "fvgp_hip_loo", "fvgp_hip_loo_workspace_bytes",
     "fvgp_hip_normal_fill", "fvgp_hip_mvn_sample", "fvgp_hip_mvn_sample_workspace_bytes",
     "fvgp_hip_select_batch", "fvgp_hip_select_workspace_bytes",
+    "fvgp_hip_loglik_hess", "fvgp_hip_loglik_hess_workspace_bytes",
 ]
 BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
 
@@ -186,6 +188,11 @@ def select_workspace_bytes(n, P, q):
     return int(lib().fvgp_hip_select_workspace_bytes(int(n), int(P), int(q)))
 
 
+def loglik_hess_workspace_bytes(n, d):
+    """bytes of the caller-owned scratch of Handle.loglik_hess (fvgp_hip_loglik_hess_workspace_bytes); -1 for n < 1 or d outside 1..16"""
+    return int(lib().fvgp_hip_loglik_hess_workspace_bytes(int(n), int(d)))
+
+
 def lib():
     """Load (once) and return the ctypes library with argtypes set."""
     global _lib
@@ -267,6 +274,9 @@ def lib():
     L.fvgp_hip_select_workspace_bytes.argtypes = [c_l, c_l, c_i]
     L.fvgp_hip_select_workspace_bytes.restype = c_l
     L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
+    L.fvgp_hip_loglik_hess.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, P_d, P_d]
+    L.fvgp_hip_loglik_hess_workspace_bytes.argtypes = [c_l, c_i]
+    L.fvgp_hip_loglik_hess_workspace_bytes.restype = c_l
     L.fvgp_hip_grad_trace.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, P_d]
     L.fvgp_hip_posterior.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_p, c_l,
                                      c_p, c_l, c_p, c_p, c_p, c_l]
@@ -297,7 +307,7 @@ def lib():
         if s not in ("fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_workspace_bytes", "fvgp_hip_dist_scratch",
                      "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes", "fvgp_hip_loglik_grad_batch_workspace_bytes",
                      "fvgp_hip_posterior_batch_workspace_bytes", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_loo_workspace_bytes",
-                     "fvgp_hip_mvn_sample_workspace_bytes", "fvgp_hip_select_workspace_bytes"):
+                     "fvgp_hip_mvn_sample_workspace_bytes", "fvgp_hip_select_workspace_bytes", "fvgp_hip_loglik_hess_workspace_bytes"):
             getattr(L, s).restype = c_i
     _lib = L
     return L
@@ -596,6 +606,21 @@ class Handle(DistCalls):
                                           int(component), _ptr(KV), KV.stride(0), _ptr(work), work.stride(0), g),
                "fvgp_hip_loglik_grad")
         return np.array(g[:], dtype=np.float64)
+
+    def loglik_hess(self, kernel_id, x, theta, alpha, ncol, component, KV, work, work2, ws):
+        """fvgp_hip_loglik_hess on the factor in KV (destroyed, as `work` and `work2`, two more padded squares): returns (grad, raw)
+        with grad the kernel-owned gradient of the negative log-likelihood (the rest 0) and raw the (nk, nk) Hessian block as the
+        device computed it, row i from G_i = W K_i W -- NOT symmetrised.  ws: a tensor of at least loglik_hess_workspace_bytes(n, d)
+        bytes.  One synchronisation."""
+        t, tp, nt = _theta(theta)
+        n, d = x.shape
+        nk = 2 if int(kernel_id) in _ISO_IDS else d + 1
+        g = (ctypes.c_double * nt)()
+        hs = (ctypes.c_double * (nk * nk))()
+        _check(lib().fvgp_hip_loglik_hess(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(alpha), int(ncol), int(component),
+                                          _ptr(KV), KV.stride(0), _ptr(work), work.stride(0), _ptr(work2), work2.stride(0),
+                                          _ptr(ws), ws.numel() * ws.element_size(), g, hs), "fvgp_hip_loglik_hess")
+        return np.array(g[:], dtype=np.float64), np.array(hs[:], dtype=np.float64).reshape(nk, nk)
 
     def grad_trace(self, kernel_id, x, theta, W, b, partial):
         """1/2 sum_jk (W_jk - b_j b_k) dK_jk/dtheta_i over the symmetric W (lower triangle read); b a 1-d view or None.

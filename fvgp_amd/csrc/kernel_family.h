@@ -1,5 +1,5 @@
 // The family of named stationary kernels, host side: what an ABI kernel id means, and the one place a launch picks its
-// <KIND, D> instantiation.  The device side of the family is radial.h (radial<KIND>, radial_grad<KIND>).
+// <KIND, D> instantiation.  The device side of the family is radial.h (radial<KIND>, radial_grad<KIND>, radial_hess<KIND>).
 #pragma once
 #include <type_traits>
 #include "common.h"

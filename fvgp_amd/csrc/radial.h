@@ -71,4 +71,24 @@ __device__ __forceinline__ void radial_grad(const double r2, const double sig, d
     phi = fma(5.0 / 3.0, r2, t) * ea; cf = (5.0 / 3.0) * sig * t * ea;
 }
 
+// radial_grad's phi and cf, and c2 = -(1 / r) dcf/dr such that d2K/dl_k dl_m = c2 e2[k] e2[m] invl[k] invl[m] - 3 delta_km cf e2[k] invl[k]^2
+// (hessian.hip: the second-derivative trace), still one exp and one reciprocal square root per entry.  Matern 3/2's c2 carries 1 / r:
+// at r2 = 0 it is 3 sqrt3 sig 1e150, finite, and every product it enters has an e2 factor that is exactly 0 there.
+template <int KIND>
+__device__ __forceinline__ void radial_hess(const double r2, const double sig, double &phi, double &cf, double &c2) {
+    if (KIND == 0) { phi = exp_neg(0.5 * r2); cf = sig * phi; c2 = cf; return; }
+    const double r = sqrt_pos(r2);
+    if (KIND == 1) {
+        // 1 / r from the reciprocal square root sqrt_pos starts from (the same instruction on the same argument), two Newton steps
+        // against the corrected r
+        double y = __builtin_amdgcn_rsq(r2 < 1e-300 ? 1e-300 : r2);
+        y = fma(y, fma(-r, y, 1.0), y);
+        y = fma(y, fma(-r, y, 1.0), y);
+        const double ea = exp_neg(SQRT3 * r);
+        phi = fma(SQRT3, r, 1.0) * ea; cf = 3.0 * sig * ea; c2 = SQRT3 * cf * y; return;
+    }
+    const double ea = exp_neg(SQRT5 * r), t = fma(SQRT5, r, 1.0);
+    phi = fma(5.0 / 3.0, r2, t) * ea; cf = (5.0 / 3.0) * sig * t * ea; c2 = (25.0 / 3.0) * sig * ea;
+}
+
 }  // namespace

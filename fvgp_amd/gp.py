@@ -26,6 +26,7 @@ from . import _lib
 from . import kernels as _kernels
 from .device import default_handle
 from .gp_design import DesignMixin
+from .gp_hessian import HessianMixin
 from .gp_lin_alg import NonPositiveDefiniteError, _non_pd_message
 from .gp_loo import LOOMixin
 from .gp_sampling import SamplingMixin
@@ -81,7 +82,7 @@ def _mixture_moments(m, v, w):
     return mean, within + between, within, between
 
 
-class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin):
+class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin, HessianMixin):
     def __init__(
         self,
         x_data,
@@ -194,6 +195,7 @@ class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin):
             warnings.warn("Hyperparameters initialized to a vector of ones.")
         self._work = None      # scratch KV for evaluations at new theta (never the state)
         self._work2 = None
+        self._work3 = None     # third square, the exact Hessian's (gp_hessian.py)
         self._alpha_work = None
         self._K_host = None
         self.set_hyperparameters(np.array(init_hyperparameters, dtype=np.float64))
@@ -225,7 +227,7 @@ class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin):
         self._x_dev = H.to_device(self.x_data)
         self._L = H.empty(self._ld, self._ld)                     # state: factor of K+V at self.hyperparameters
         self._alpha = H.empty(self._np, self.y_data.shape[1])     # state: KVinvY
-        self._work = self._work2 = self._alpha_work = None
+        self._work = self._work2 = self._work3 = self._alpha_work = None
 
     @property
     def hyperparameters(self):
@@ -549,7 +551,7 @@ class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin):
         self.m, self.V = mean, V
         self._K_host = None
         if not (self._work is not None and self._work.shape[0] == self._eval_dim() and self._alpha_work.shape[0] == np_new):
-            self._work = self._work2 = self._alpha_work = None    # (kept when the sizes did not change: no reallocation per append)
+            self._work = self._work2 = self._work3 = self._alpha_work = None    # (kept when the sizes did not change: no reallocation per append)
         self._refresh_inverse()
 
     @property
@@ -1640,7 +1642,7 @@ class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin):
             return st
         self._H.sync()
         st = {k: v for k, v in self.__dict__.items()
-              if k not in ("_H", "_x_dev", "_L", "_alpha", "_work", "_work2", "_alpha_work", "_KVinv", "_custom_obj", "_custom_obj_work")}
+              if k not in ("_H", "_x_dev", "_L", "_alpha", "_work", "_work2", "_work3", "_alpha_work", "_KVinv", "_custom_obj", "_custom_obj_work")}
         n = self.point_number
         st["_L_host"] = np.tril(self._L[:n, :n].cpu().numpy())
         st["_alpha_host"] = self._alpha[:n].cpu().numpy()
@@ -1671,6 +1673,6 @@ class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin):
         self._alpha = H.zeros(self._np, self.y_data.shape[1])
         self._alpha[:n] = H.to_device(a_host)
         H.invalidate_factor()                                     # uploaded factor: no cached block inverses belong to it
-        self._work = self._work2 = self._alpha_work = None
+        self._work = self._work2 = self._work3 = self._alpha_work = None
         self._KVinv = None
         self._refresh_inverse()

@@ -291,6 +291,7 @@ def train(gp, bounds, init_hyperparameters, method="mcmc", pop_size=20, toleranc
     if loo and (batch_population or adam_starts >= 2):
         raise ValueError("args['training_objective'] = 'loo' cannot be combined with 'batch_population' or 'adam_starts': "
                          "there is no batched LOO evaluation")
+    own_objective = objective_function is None
     if objective_function is None and method in ("mcmc", "global", "local", "adam"):
         if loo:
             objective_function = gp.loo_log_predictive if method == "mcmc" else gp.neg_loo_log_predictive
@@ -298,6 +299,11 @@ def train(gp, bounds, init_hyperparameters, method="mcmc", pop_size=20, toleranc
                 objective_function_gradient = gp.neg_loo_log_predictive_gradient
         else:
             objective_function = gp.log_likelihood if method == "mcmc" else gp.neg_log_likelihood
+    # GP(..., args={"exact_hessian": True}): 'local' hands scipy the exact Hessian of the marginal likelihood (gp_hessian.py) for its
+    # Newton-type optimisers, wherever the objective is the engine's own and the caller gave no Hessian
+    if (own_objective and method == "local" and objective_function_hessian is None and objective_function_gradient is None and not loo
+            and bool(getattr(gp, "args", {}).get("exact_hessian", False))):
+        objective_function_hessian = gp.neg_log_likelihood_exact_hessian
     if objective_function_gradient is None and method in ("local", "adam"):
         objective_function_gradient = gp.neg_log_likelihood_gradient
     if method == "mcmc":

@@ -422,6 +422,23 @@ int fvgp_hip_loglik_grad(fvgp_handle *h, int kernel_id, const double *x, int64_t
                          const double *theta_host, int ntheta, const double *alpha, int ncol, int component,
                          double *KV, int64_t ld, double *work, int64_t ldw, double *grad_host);
 
+/* loglik_hess: the exact Hessian of the negative log marginal likelihood in the hyperparameters the named kernel owns, with the
+ * gradient of fvgp_hip_loglik_grad from the same call (no counterpart in the reference, whose gp_marginal_likelihood.py:312-336
+ * differences the gradient).  With W = KV^-1, b = KVinvY[:, component], K_i = dK/dtheta_i, G_i = W K_i W, w_i = W K_i b:
+ *   H_ij = 1/2 sum_ab (W - b b^T)_ab (d2K/dtheta_i dtheta_j)_ab - [ 1/2 tr(G_i K_j) - b^T K_j w_i ]
+ *   KV on entry: the factor L from fvgp_hip_loglik / potrf (its strict upper triangle is never read).  KV, work and work2 -- three
+ *   padded_dim(n)-row scratches, each 16-byte aligned with an even leading dimension >= padded_dim(n) -- are destroyed.
+ *   ws: device scratch of fvgp_hip_loglik_hess_workspace_bytes(n, d) bytes, 8-byte aligned.
+ *   grad_host: ntheta doubles (kernel-owned entries, the rest 0).
+ *   hess_host: nk x nk doubles, row-major, nk = the kernel's parameter count (d + 1, or 2 for an isotropic kernel): the RAW block --
+ *   row i comes from G_i, so H_ij and H_ji are two independent computations; a caller wanting a symmetric matrix averages them.
+ * A bad argument returns minus its position before anything is launched or written.  One synchronisation. */
+int64_t fvgp_hip_loglik_hess_workspace_bytes(int64_t n, int d);          /* -1 for n < 1 or d outside 1..FVGP_MAX_DIM */
+int fvgp_hip_loglik_hess(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
+                         const double *theta_host, int ntheta, const double *alpha, int ncol, int component,
+                         double *KV, int64_t ld, double *work, int64_t ldw, double *work2, int64_t ldw2,
+                         double *ws, int64_t ws_bytes, double *grad_host, double *hess_host);
+
 /* the trace part of the gradient on its own: grad_host[i] = 1/2 sum_jk (W_jk - b_j b_k) dK_jk/dtheta_i over the
  * n x n symmetric W (lower triangle read; b with stride ldb, or NULL for the pure trace 1/2 tr(W dK_i)).  The row-sharded
  * gradient calls it on each rank's partial Gram matrix inv(L)_p^T inv(L)_p (gp_marginal_likelihood.py:262-300).
