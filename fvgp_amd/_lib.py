@@ -40,7 +40,12 @@ SYMBOLS = [
     "fvgp_hip_normal_fill", "fvgp_hip_mvn_sample", "fvgp_hip_mvn_sample_workspace_bytes",
     "fvgp_hip_select_batch", "fvgp_hip_select_workspace_bytes",
     "fvgp_hip_loglik_hess", "fvgp_hip_loglik_hess_workspace_bytes",
+    "fvgp_hip_kmatvec", "fvgp_hip_kmatvec_workspace_bytes", "fvgp_hip_pchol", "fvgp_hip_pchol_workspace_bytes",
+    "fvgp_hip_precond_factor", "fvgp_hip_precond_workspace_bytes", "fvgp_hip_pcg", "fvgp_hip_pcg_workspace_bytes",
 ]
+MATVEC_CHUNK = 4096       # FVGP_MATVEC_CHUNK: rows of x2 per chunk sum of fvgp_hip_kmatvec
+PCG_MAX_RHS = 16          # FVGP_PCG_MAX_RHS
+PCG_MAX_RANK = 1024       # FVGP_PCG_MAX_RANK
 BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
 
 
@@ -188,6 +193,26 @@ def select_workspace_bytes(n, P, q):
     return int(lib().fvgp_hip_select_workspace_bytes(int(n), int(P), int(q)))
 
 
+def kmatvec_workspace_bytes(n1, n2, s):
+    """bytes of the split form's scratch of Handle.kmatvec (fvgp_hip_kmatvec_workspace_bytes); -1 for n1, n2 or s < 1"""
+    return int(lib().fvgp_hip_kmatvec_workspace_bytes(int(n1), int(n2), int(s)))
+
+
+def pchol_workspace_bytes(n, q):
+    """bytes of the caller-owned workspace of Handle.pchol (fvgp_hip_pchol_workspace_bytes); -1 for n or q < 1"""
+    return int(lib().fvgp_hip_pchol_workspace_bytes(int(n), int(q)))
+
+
+def precond_workspace_bytes(n, q):
+    """bytes of the caller-owned workspace of Handle.precond_factor (fvgp_hip_precond_workspace_bytes); -1 for n or q < 1"""
+    return int(lib().fvgp_hip_precond_workspace_bytes(int(n), int(q)))
+
+
+def pcg_workspace_bytes(n, q):
+    """bytes of the caller-owned workspace of Handle.pcg (fvgp_hip_pcg_workspace_bytes); -1 for n < 1 or q < 0"""
+    return int(lib().fvgp_hip_pcg_workspace_bytes(int(n), int(q)))
+
+
 def loglik_hess_workspace_bytes(n, d):
     """bytes of the caller-owned scratch of Handle.loglik_hess (fvgp_hip_loglik_hess_workspace_bytes); -1 for n < 1 or d outside 1..16"""
     return int(lib().fvgp_hip_loglik_hess_workspace_bytes(int(n), int(d)))
@@ -273,6 +298,18 @@ def lib():
                                         c_p, c_l, c_p, c_p, c_p, c_l]
     L.fvgp_hip_select_workspace_bytes.argtypes = [c_l, c_l, c_i]
     L.fvgp_hip_select_workspace_bytes.restype = c_l
+    L.fvgp_hip_kmatvec.argtypes = [c_p, c_i, c_p, c_l, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_l]
+    L.fvgp_hip_kmatvec_workspace_bytes.argtypes = [c_l, c_l, c_i]
+    L.fvgp_hip_pchol.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_i, c_d, c_p, c_l, c_p, c_p, c_p, c_l, P_i]
+    L.fvgp_hip_pchol_workspace_bytes.argtypes = [c_l, c_i]
+    L.fvgp_hip_precond_factor.argtypes = [c_p, c_p, c_l, c_i, c_l, c_p, c_p, c_l, c_p, c_l, P_i]
+    L.fvgp_hip_precond_workspace_bytes.argtypes = [c_l, c_i]
+    L.fvgp_hip_pcg.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_i,
+                               c_d, c_i, c_i, c_i, c_p, c_l, P_i, P_d, P_i]
+    L.fvgp_hip_pcg_workspace_bytes.argtypes = [c_l, c_i]
+    for name in ("fvgp_hip_kmatvec_workspace_bytes", "fvgp_hip_pchol_workspace_bytes", "fvgp_hip_precond_workspace_bytes",
+                 "fvgp_hip_pcg_workspace_bytes"):
+        getattr(L, name).restype = c_l
     L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
     L.fvgp_hip_loglik_hess.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, P_d, P_d]
     L.fvgp_hip_loglik_hess_workspace_bytes.argtypes = [c_l, c_i]
@@ -307,7 +344,9 @@ def lib():
         if s not in ("fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_workspace_bytes", "fvgp_hip_dist_scratch",
                      "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes", "fvgp_hip_loglik_grad_batch_workspace_bytes",
                      "fvgp_hip_posterior_batch_workspace_bytes", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_loo_workspace_bytes",
-                     "fvgp_hip_mvn_sample_workspace_bytes", "fvgp_hip_select_workspace_bytes", "fvgp_hip_loglik_hess_workspace_bytes"):
+                     "fvgp_hip_mvn_sample_workspace_bytes", "fvgp_hip_select_workspace_bytes", "fvgp_hip_loglik_hess_workspace_bytes",
+                     "fvgp_hip_kmatvec_workspace_bytes", "fvgp_hip_pchol_workspace_bytes", "fvgp_hip_precond_workspace_bytes",
+                     "fvgp_hip_pcg_workspace_bytes"):
             getattr(L, s).restype = c_i
     _lib = L
     return L
@@ -370,7 +409,7 @@ class Handle(DistCalls):
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         _check(lib().fvgp_hip_create(ctypes.byref(self._h), self.device, ctypes.c_void_p(stream)), "fvgp_hip_create")
-        for key in ("schedule", "lookahead", "outer_block", "outer_block_big", "big_threshold", "inner_block", "small_tile_max", "small_tile_max_update", "tile_tables", "block_inverses", "k128_kernels", "leaf_tiles", "leaf_tiles_rows", "panel_recursive", "potri_kminor", "leaf_yield", "chain_yield", "lookahead_min", "posterior_halves", "posterior_block", "outer_block_small", "small_threshold", "panel_chain", "panel_chain_min", "cols_split", "cols_split_rows", "bwd_sweep", "fwd_sweep", "chain_verify", "chain_wide", "wide_block", "wide_block_big", "wide_threshold", "wide_inner", "wide_inner_rows", "chain_sleep_rows", "chain_single_rows", "chain_ahead", "select_block"):        # tuning overrides, e.g. FVGP_OUTER_BLOCK=512
+        for key in ("schedule", "lookahead", "outer_block", "outer_block_big", "big_threshold", "inner_block", "small_tile_max", "small_tile_max_update", "tile_tables", "block_inverses", "k128_kernels", "leaf_tiles", "leaf_tiles_rows", "panel_recursive", "potri_kminor", "leaf_yield", "chain_yield", "lookahead_min", "posterior_halves", "posterior_block", "outer_block_small", "small_threshold", "panel_chain", "panel_chain_min", "cols_split", "cols_split_rows", "bwd_sweep", "fwd_sweep", "chain_verify", "chain_wide", "wide_block", "wide_block_big", "wide_threshold", "wide_inner", "wide_inner_rows", "chain_sleep_rows", "chain_single_rows", "chain_ahead", "select_block", "matvec_split"):        # tuning overrides, e.g. FVGP_OUTER_BLOCK=512
             val = os.environ.get("FVGP_" + key.upper())
             if val is not None:
                 self.set_option(key, int(val))
@@ -782,6 +821,61 @@ class Handle(DistCalls):
                                            _ptr(noise), _ptr(var), int(q), int(criterion), int(bool(allow_repeats)), float(tol),
                                            _ptr(work), work.numel() * 8, _ptr(idx_out), _ptr(pick_var_out), _ptr(G_out),
                                            0 if G_out is None else G_out.stride(0)), "fvgp_hip_select_batch")
+
+    def kmatvec(self, kernel_id, x1, x2, theta, B, Y, vdiag=None, s=None, work=None):
+        """fvgp_hip_kmatvec: Y[:, :s] = K(x1, x2) B[:, :s] + diag(vdiag) B[:, :s] without K.  B (n2, >= s), Y (n1, >= s) device
+        tensors (strided views are fine), vdiag (n1) or None (needs n1 == n2); work None or a flat device tensor for the split form
+        (kmatvec_workspace_bytes).  Asynchronous."""
+        t, tp, nt = _theta(theta)
+        s = int(B.shape[1] if s is None else s)
+        _check(lib().fvgp_hip_kmatvec(self._h, int(kernel_id), _ptr(x1), x1.shape[0], _ptr(x2), x2.shape[0], x1.shape[1], tp, nt,
+                                      _ptr(vdiag), _ptr(B), B.stride(0), s, _ptr(Y), Y.stride(0), _ptr(work),
+                                      0 if work is None else work.numel() * 8), "fvgp_hip_kmatvec")
+
+    def pchol(self, kernel_id, x, theta, q, G, piv_out, tol=0.0, resid_diag_out=None, work=None):
+        """fvgp_hip_pchol: the greedy pivoted Cholesky of K(x, x), rank <= q, into G (q, >= n); piv_out an int64 device (q,) tensor
+        (-1 from the achieved rank on, the rows of G there are zero); returns the achieved rank (synchronises)."""
+        t, tp, nt = _theta(theta)
+        n, d = x.shape
+        if work is None:
+            work = self.empty(max(1, pchol_workspace_bytes(n, q)) // 8)
+        rank = ctypes.c_int(0)
+        _check(lib().fvgp_hip_pchol(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, int(q), float(tol), _ptr(G), G.stride(0),
+                                    _ptr(piv_out), _ptr(resid_diag_out), _ptr(work), work.numel() * 8, ctypes.byref(rank)),
+               "fvgp_hip_pchol")
+        return int(rank.value)
+
+    def precond_factor(self, G, q, n, vdiag, C, work=None):
+        """fvgp_hip_precond_factor: C (padded_dim(q) square) <- the factor of I + G D^-1 G^T; returns info (0 = factored)"""
+        if work is None:
+            work = self.empty(max(1, precond_workspace_bytes(n, q)) // 8)
+        info = ctypes.c_int(0)
+        _check(lib().fvgp_hip_precond_factor(self._h, _ptr(G), G.stride(0), int(q), int(n), _ptr(vdiag), _ptr(C), C.stride(0),
+                                             _ptr(work), work.numel() * 8, ctypes.byref(info)), "fvgp_hip_precond_factor")
+        return int(info.value)
+
+    def pcg(self, kernel_id, x, theta, vdiag, B, X, G=None, q=0, C=None, s=None, warm=False, tol=1e-10, max_iter=1000, check_every=8,
+            max_restarts=3, work=None):
+        """fvgp_hip_pcg: (K(x, x) + diag(vdiag)) X[:, :s] = B[:, :s], s <= PCG_MAX_RHS, preconditioned by (G, C) of pchol /
+        precond_factor (G None or q == 0: Jacobi).  Returns (iters, relres, status) as numpy arrays of s entries: status 0 converged,
+        1 not converged, 2 breakdown; relres is the true relative residual.  Synchronous."""
+        t, tp, nt = _theta(theta)
+        n, d = x.shape
+        s = int(B.shape[1] if s is None else s)
+        q = 0 if G is None else int(q)
+        if work is None:
+            work = self.empty(max(1, pcg_workspace_bytes(n, q)) // 8)
+        iters = np.zeros(max(s, 1), dtype=np.int32)
+        status = np.zeros(max(s, 1), dtype=np.int32)
+        relres = np.zeros(max(s, 1), dtype=np.float64)
+        _check(lib().fvgp_hip_pcg(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(vdiag), _ptr(G),
+                                  0 if G is None else G.stride(0), q, _ptr(C), 0 if C is None else C.stride(0),
+                                  _ptr(B), B.stride(0), s, _ptr(X), X.stride(0), int(bool(warm)), float(tol), int(max_iter),
+                                  int(check_every), int(max_restarts), _ptr(work), work.numel() * 8,
+                                  iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                  relres.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                  status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))), "fvgp_hip_pcg")
+        return iters[:s], relres[:s], status[:s]
 
     def potrs_cols(self, L, n, B, nrhs):
         """Handle.potrs for nrhs % 128 == 0 columns whose bits do not depend on nrhs (fvgp_hip_potrs_cols)"""

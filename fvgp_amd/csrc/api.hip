@@ -188,6 +188,10 @@ int fvgp_hip_set_option(fvgp_handle *h, const char *key, int64_t value) {
         if (value < 64 || value % 64 || value > 65536) { fvgp_set_error("select_block: a multiple of 64, at most 65536"); return -3; }
         h->select_block = value; return 0;
     }
+    if (!strcmp(key, "matvec_split")) {
+        if (value < 0 || value > 65535) { fvgp_set_error("matvec_split: 0 (by the shape), 1 (never) or the number of chunk ranges, at most 65535"); return -3; }
+        h->matvec_split = value; return 0;
+    }
     if (!strcmp(key, "outer_block_small")) { if (value < 0 || value % TILE) return -3; h->outer_block_small = value; return 0; }
     if (!strcmp(key, "small_threshold")) { h->small_threshold = value; return 0; }
     fvgp_set_error(std::string("unknown option ") + key);

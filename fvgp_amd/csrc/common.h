@@ -117,6 +117,7 @@ struct fvgp_handle {
     // 8000 5.7 -> 5.1, 20000 46.9 -> 45.6, 50000 620 -> 595 on the same box); `lookahead_min` = 4608 restores the old schedule
     int64_t lookahead_min = (int64_t)1 << 40;
     int64_t select_block = 65536;     // measurement only: candidates per launch pair of the batch selection (select.hip; a multiple of 64, at most 65536)
+    int64_t matvec_split = 0;         // fvgp_hip_kmatvec's gridDim.y: 0 by the shape, 1 never split, k chunk ranges dealt over k workgroups (same bits; matrix_free.hip)
     int posterior_halves = 1;         // posterior covariance at >= 512 points: two halves of the points side by side on two streams (tri_solve.hip)
     int64_t outer_block_small = 512, small_threshold = 12288;   // panel width for the last `small_threshold` rows (potrf_driver)
     int lookahead = 1;

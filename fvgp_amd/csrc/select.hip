@@ -16,6 +16,7 @@
 #include "radial.h"
 #include "kernel_family.h"
 #include "slice_sum.h"
+#include "argmax.h"
 #include <math.h>
 
 namespace {
@@ -43,21 +44,6 @@ struct SelArgs {
     double sig, tol;
     double il[FVGP_MAX_DIM];
 };
-
-struct Best { double score; long idx; };     // idx < 0: none
-__device__ __forceinline__ bool better(const Best a, const Best b) {
-    return a.idx >= 0 && (b.idx < 0 || a.score > b.score || (a.score == b.score && a.idx < b.idx));
-}
-__device__ __forceinline__ Best wave_best(Best b) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        Best o;
-        o.score = __shfl_down(b.score, off, 64);
-        o.idx = __shfl_down(b.idx, off, 64);
-        if (better(o, b)) b = o;
-    }
-    return b;
-}
 
 // what candidate i offers the next pick: d, or d / s; nothing if it is taken (and repeats are off) or its score is no number
 __device__ __forceinline__ Best candidate(const SelArgs &a, long i, double dv, bool taken) {

@@ -29,6 +29,7 @@ from .gp_design import DesignMixin
 from .gp_hessian import HessianMixin
 from .gp_lin_alg import NonPositiveDefiniteError, _non_pd_message
 from .gp_loo import LOOMixin
+from .gp_matrix_free import MatrixFreeMixin
 from .gp_sampling import SamplingMixin
 from .gp_validation import ValidationMixin
 
@@ -82,7 +83,7 @@ def _mixture_moments(m, v, w):
     return mean, within + between, within, between
 
 
-class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin, HessianMixin):
+class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin, HessianMixin, MatrixFreeMixin):
     def __init__(
         self,
         x_data,

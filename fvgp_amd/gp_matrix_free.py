@@ -1,0 +1,298 @@
+"""Prediction with ALL the data at sizes where no N x N factor fits: (K(theta) + V) X = B by preconditioned conjugate gradients.
+
+K is never stored.  Every product with K evaluates the kernel on the fly (fvgp_hip_kmatvec), the preconditioner is the rank-q
+pivoted Cholesky G^T G + V of K + V applied through Woodbury (fvgp_hip_pchol, fvgp_hip_precond_factor), the recurrences' scalars live
+on the device (fvgp_hip_pcg).  Memory is O(N (q + 16)): N = 10^6 at rank 256 holds about 2 GB of preconditioner.
+
+The intended use: train on a subset with the dense fvgp_amd.GP, then predict with everything --
+
+    gp = GP(x_sub, y_sub, ...); gp.train(...)
+    big = gp.matrix_free(x_all, y_all, noise_all)
+    big.posterior_mean(x_pred); big.posterior_covariance(x_pred, variance_only=True)
+
+With alpha = (K + V)^-1 (y - m) and Z = (K + V)^-1 k(X, x*):   m(x*) = m + k(x*, X) alpha,   v = k** - sum k o Z,
+S = k** - k(x*, X) Z.  The likelihood, its gradient and train() need a stochastic log-determinant and trace on this path; they
+are not here (use the dense GP).
+"""
+import warnings
+
+import numpy as np
+
+from . import _lib
+from . import kernels as _kernels
+from .device import default_handle
+from .gp_lin_alg import NonPositiveDefiniteError
+
+# device bytes the solved columns Z = (K + V)^-1 k(X, x*) of one posterior_covariance call may take (n x P doubles);
+# args["z_max_bytes"] overrides it per object
+Z_MAX_BYTES = 2 << 30
+_DENSE = "the dense fvgp_amd.GP has it (train on a subset there, then GP.matrix_free(...) predicts with all the data)"
+
+
+class MatrixFreeGP:
+    """Posterior mean, variance and small joint covariances of an exact GP whose covariance matrix is never formed.
+
+    x_data (N, D), y_data (N,), hyperparameters in the named kernel's layout, noise_variances (N,) or None (the rule and the warning
+    of GP: (0.01 mean|y|)^2).  The prior mean is mean(y).  args: "precond_rank" (128; 0 = Jacobi), "tol" (1e-10, relative
+    residual), "max_iter" (1000), "check_every" (8), "max_restarts" (3), "pchol_tol" (1e-12), "z_max_bytes"."""
+
+    def __init__(self, x_data, y_data, hyperparameters, noise_variances=None, kernel_function="matern32_ard", args=None):
+        native = _kernels.resolve(kernel_function) if not callable(kernel_function) or isinstance(kernel_function, _kernels.NativeKernel) \
+            else None
+        if native is None:
+            raise NotImplementedError("MatrixFreeGP evaluates the kernel on the device inside every product: only the named kernels of "
+                                      "fvgp_amd.kernels run here; a kernel callable belongs to the dense fvgp_amd.GP")
+        assert isinstance(x_data, np.ndarray) and np.ndim(x_data) == 2, "x_data must be 2-d (n_points x input_dim)"
+        assert isinstance(y_data, np.ndarray) and np.ndim(y_data) == 1, "y_data must be a 1-d np.ndarray (fvGP / x_out: " + _DENSE + ")"
+        assert len(x_data) == len(y_data), "x_data and y_data do not have the same lengths."
+        self._native = native
+        self.args = {} if args is None else dict(args)
+        self.precond_rank = int(self.args.get("precond_rank", 128))
+        assert 0 <= self.precond_rank <= _lib.PCG_MAX_RANK, f"precond_rank must lie in 0 .. {_lib.PCG_MAX_RANK}"
+        self.tol = float(self.args.get("tol", 1e-10))
+        self.max_iter = int(self.args.get("max_iter", 1000))
+        self.check_every = int(self.args.get("check_every", 8))
+        self.max_restarts = int(self.args.get("max_restarts", 3))
+        self._H = default_handle()
+        if noise_variances is None:
+            warnings.warn("No noise function or measurement noise provided. "
+                          "Noise variances will be set to (0.01 * mean(|y_data|))^2.", stacklevel=2)
+        self._set_data(x_data, y_data, noise_variances)
+        self._alpha = None                  # device (n, 1): (K + V)^-1 (y - m) at self._hps
+        self._alpha_info = None
+        self.set_hyperparameters(hyperparameters)
+
+    # ---- state -----------------------------------------------------------------------------------------------------------
+    def _set_data(self, x_data, y_data, noise_variances):
+        H = self._H
+        self.x_data = np.ascontiguousarray(x_data, dtype=np.float64)
+        self.y_data = np.ascontiguousarray(y_data, dtype=np.float64)
+        self.point_number, self.index_set_dim = self.x_data.shape
+        if self.index_set_dim > 16:
+            raise NotImplementedError("the device kernels take input dimension <= 16")
+        if noise_variances is None:
+            V = np.ones(self.point_number) * (np.mean(abs(self.y_data)) / 100.0) ** 2
+        else:
+            V = np.asarray(noise_variances, dtype=np.float64)
+            assert V.shape == (self.point_number,), "noise_variances must be 1-d, one per data point"
+            assert np.all(V > 0.0), "all noise_variances must be positive"
+        self.noise_variances = noise_variances
+        self._V = np.ascontiguousarray(V)
+        self._m = float(np.mean(self.y_data))
+        self._x_dev, self._V_dev = H.to_device(self.x_data), H.to_device(self._V)
+        self._ym_dev = H.to_device((self.y_data - self._m)[:, None])
+        self._G = self._C = self._work = None
+        self._rank = 0
+
+    @property
+    def hyperparameters(self):
+        return self._hps
+
+    def get_hyperparameters(self):
+        return self._hps
+
+    def set_hyperparameters(self, hps):
+        hps = np.array(hps, dtype=np.float64)
+        assert hps.shape == (self._native.n_hyperparameters(self.index_set_dim),), "wrong number of hyperparameters for this kernel"
+        self._hps = hps
+        self._alpha = self._alpha_info = None
+        self._G = self._C = None
+
+    def _preconditioner(self):
+        """(G, q, C) at the current hyperparameters, built once: the pivoted Cholesky of K and the factor of I + G V^-1 G^T"""
+        if self.precond_rank == 0:
+            return None, 0, None
+        if self._G is None:
+            H, n = self._H, self.point_number
+            q = min(self.precond_rank, n)
+            G = H.empty(q, n)
+            piv = H.torch.empty(q, dtype=H.torch.int64, device=G.device)
+            self._rank = H.pchol(self._native.kernel_id, self._x_dev, self._hps, q, G, piv, tol=float(self.args.get("pchol_tol", 1e-12)))
+            qp = _lib.pad128(q)
+            C = H.empty(qp, qp)
+            info = H.precond_factor(G, q, n, self._V_dev, C)
+            if info != 0:
+                raise NonPositiveDefiniteError(f"the preconditioner's {q} x {q} system I + G V^-1 G^T is not positive definite "
+                                               f"(pivot {info}): the noise variances or the hyperparameters are no numbers")
+            self._G, self._C, self._q = G, C, q
+        return self._G, self._q, self._C
+
+    def _pcg(self, B, X, s, warm=False):
+        H, n = self._H, self.point_number
+        G, q, C = self._preconditioner()
+        need = _lib.pcg_workspace_bytes(n, q) // 8
+        if self._work is None or self._work.numel() < need:
+            self._work = H.empty(max(1, need))
+        return H.pcg(self._native.kernel_id, self._x_dev, self._hps, self._V_dev, B, X, G=G, q=q, C=C, s=s, warm=warm, tol=self.tol,
+                     max_iter=self.max_iter, check_every=self.check_every, max_restarts=self.max_restarts, work=self._work)
+
+    def _solve_device(self, B, X, warm=False):
+        """X (n, c) <- (K + V)^-1 B (n, c) on the device in blocks of 16 columns; (iterations, residuals, converged) per column"""
+        c = B.shape[1]
+        its, res, ok = np.zeros(c, dtype=np.int64), np.zeros(c), np.zeros(c, dtype=bool)
+        for a in range(0, c, _lib.PCG_MAX_RHS):
+            b = min(a + _lib.PCG_MAX_RHS, c)
+            it, rr, st = self._pcg(B[:, a:b], X[:, a:b], b - a, warm=warm)
+            if np.any(st == 2):
+                raise NonPositiveDefiniteError(
+                    f"conjugate gradients broke down on K + V ({self.point_number} points, smallest noise variance "
+                    f"{float(np.min(self._V)):.3e}): p^T (K + V) p or r^T M^-1 r was not positive -- the matrix is not positive "
+                    "definite in double precision; add noise or rethink the hyperparameters")
+            its[a:b], res[a:b], ok[a:b] = it, rr, st == 0
+        if not np.all(ok):
+            warnings.warn(f"conjugate gradients did not converge: relative residual {float(np.max(res)):.3e} reached, "
+                          f"tol = {self.tol:.1e} asked, after at most {int(np.max(its))} iterations (args: max_iter, "
+                          "precond_rank, tol)", stacklevel=3)
+        return its, res, ok
+
+    # ---- public ----------------------------------------------------------------------------------------------------------
+    def solve(self, b):
+        """(K + V)^-1 b for b (n,) or (n, c); the prediction state (alpha) is not touched"""
+        b = np.asarray(b, dtype=np.float64)
+        one = b.ndim == 1
+        B = self._H.to_device(b.reshape(self.point_number, -1))
+        X = self._H.empty(*B.shape)
+        its, res, ok = self._solve_device(B, X)
+        x = self._H.to_host(X)
+        return {"x": x[:, 0].copy() if one else x, "iterations": its, "relative_residual": res, "converged": bool(np.all(ok))}
+
+    def _ensure_alpha(self, warm_from=None):
+        if self._alpha is None:
+            X = self._H.zeros(self.point_number, 1)
+            if warm_from is not None:
+                X[:warm_from.shape[0]] = warm_from
+            its, res, ok = self._solve_device(self._ym_dev, X, warm=warm_from is not None)
+            self._alpha = X
+            self._alpha_info = {"iterations": int(its[0]), "relative_residual": float(res[0]), "converged": bool(ok[0])}
+        return self._alpha
+
+    def _check_pred(self, x_pred, x_out=None):
+        if x_out is not None:
+            raise NotImplementedError("x_out / fvGP outputs are not on the matrix-free path: " + _DENSE)
+        assert isinstance(x_pred, np.ndarray) and np.ndim(x_pred) == 2, "x_pred must be a 2-d np.ndarray"
+        assert x_pred.shape[1] == self.index_set_dim, "wrong number of columns in x_pred"
+        return self._H.to_device(x_pred)
+
+    def _cross(self, xp_dev, B, c):
+        """k(x_pred, X) B[:, :c] on the device: the rectangular product, split over chunk ranges when few points meet many rows"""
+        H, n, P = self._H, self.point_number, xp_dev.shape[0]
+        out = H.empty(P, c)
+        work = H.empty(max(1, _lib.kmatvec_workspace_bytes(P, n, c) // 8)) if P < 32768 else None
+        H.kmatvec(self._native.kernel_id, xp_dev, self._x_dev, self._hps, B, out, s=c, work=work)
+        return out
+
+    def posterior_mean(self, x_pred, hyperparameters=None, x_out=None):
+        if hyperparameters is not None:
+            raise NotImplementedError("posterior_mean(hyperparameters=...) would solve for a second alpha: call "
+                                      "set_hyperparameters first, or use the dense GP; " + _DENSE)
+        xp = self._check_pred(x_pred, x_out)
+        alpha = self._ensure_alpha()
+        mean = self._m + self._H.to_host(self._cross(xp, alpha, 1))[:, 0]
+        return {"x": x_pred.copy(), "m(x)": mean, "m(x)_flat": mean, "x_pred": x_pred, **self._alpha_info}
+
+    def posterior_covariance(self, x_pred, x_out=None, variance_only=False, add_noise=False):
+        xp = self._check_pred(x_pred, x_out)
+        H, n, P = self._H, self.point_number, len(x_pred)
+        budget = int(self.args.get("z_max_bytes", Z_MAX_BYTES))
+        if 2 * n * P * 8 > budget:
+            raise MemoryError(f"posterior_covariance at {P} points needs k(X, x*) and its solved columns, 2 x {n} x {P} doubles = "
+                              f"{2 * n * P * 8 / 2 ** 30:.2f} GiB, above the budget of {budget / 2 ** 30:.2f} GiB "
+                              "(args['z_max_bytes']): predict in smaller batches of points")
+        kid = self._native.kernel_id
+        Kx, Z = H.empty(n, P + (P & 1))[:, :P], H.empty(n, P)
+        H.kmat(kid, self._x_dev, xp, self._hps, Kx)                      # k(X, x*): the right-hand sides
+        self._solve_device(Kx, Z)
+        sig = float(self._hps[0])
+        # k(x*, X) Z through the product's bit contract: a point's variance does not depend on what else is in the call
+        v, S = np.empty(P), None
+        if not variance_only:
+            S = np.empty((P, P))
+        for a in range(0, P, _lib.PCG_MAX_RHS):
+            b = min(a + _lib.PCG_MAX_RHS, P)
+            if variance_only:
+                v[a:b] = sig - np.diag(H.to_host(self._cross(xp[a:b], Z[:, a:b], b - a)))
+            else:
+                S[:, a:b] = H.to_host(self._cross(xp, Z[:, a:b], b - a))
+        if S is not None:
+            kk = H.empty(P, P + (P & 1))
+            H.kmat(kid, xp, xp, self._hps, kk)
+            v = sig - np.diag(S)
+            S = H.to_host(kk)[:, :P] - S
+            S = 0.5 * (S + S.T)
+            np.fill_diagonal(S, v)
+        if np.any(v < -0.0001):
+            warnings.warn("Negative variances encountered. That normally means that the model is unstable. "
+                          "Rethink the kernel definition, add more noise to the data, "
+                          "or double check the hyperparameter optimization bounds. This will not "
+                          "terminate the algorithm, but expect anomalies.")
+        if np.any(v < 0.0):
+            v[v < 0.0] = 0.0
+            if S is not None:
+                np.fill_diagonal(S, v)
+        if add_noise:
+            noise = self._V if len(x_pred) == n else np.zeros(P) + np.mean(self._V)
+            v = v + noise
+            if S is not None:
+                S = S + np.diag(noise)
+        return {"x": x_pred.copy(), "x_pred": x_pred, "v(x)": v, "S": S, "S_flat": S, "v_flat": v}
+
+    def update_gp_data(self, x_new, y_new, noise_variances_new=None, append=True):
+        """new data (appended, or replacing everything): the preconditioner is rebuilt and alpha warm-starts from the old one padded
+        with zeros"""
+        assert isinstance(x_new, np.ndarray) and np.ndim(x_new) == 2 and isinstance(y_new, np.ndarray) and np.ndim(y_new) == 1
+        old = self._alpha if append else None
+        if append:
+            if (self.noise_variances is None) != (noise_variances_new is None):
+                raise Exception("noise_variances_new must be given exactly when the object was built with noise_variances")
+            x_new = np.vstack([self.x_data, x_new])
+            y_new = np.concatenate([self.y_data, y_new])
+            if noise_variances_new is not None:
+                noise_variances_new = np.concatenate([self.noise_variances, noise_variances_new])
+        self._set_data(x_new, y_new, noise_variances_new)
+        self._alpha = self._alpha_info = None
+        if old is not None:
+            # (the prior mean moved with the data: the old alpha still nearly solves the old rows, which is all a start needs)
+            self._ensure_alpha(warm_from=old)
+
+    # ---- what this path does not have ------------------------------------------------------------------------------------
+    def _dense_only(self, what):
+        raise NotImplementedError(f"{what} needs log det(K + V) or traces with (K + V)^-1, which the matrix-free path does not have yet "
+                                  "(a stochastic log-determinant and trace are the follow-up): " + _DENSE)
+
+    def log_likelihood(self, hyperparameters=None):
+        self._dense_only("log_likelihood")
+
+    def neg_log_likelihood(self, hyperparameters=None):
+        self._dense_only("neg_log_likelihood")
+
+    def neg_log_likelihood_gradient(self, hyperparameters=None, component=0):
+        self._dense_only("neg_log_likelihood_gradient")
+
+    def neg_log_likelihood_hessian(self, hyperparameters=None):
+        self._dense_only("neg_log_likelihood_hessian")
+
+    def train(self, *a, **kw):
+        self._dense_only("train")
+
+
+class MatrixFreeMixin:
+    """Mixed into fvgp_amd.GP: needs _native, _hps, _noise_callable, _mean_callable, x_data, y_data, noise_variances."""
+
+    def matrix_free(self, x_data=None, y_data=None, noise_variances=None, args=None):
+        """A MatrixFreeGP with this GP's kernel and CURRENT hyperparameters, over this GP's data or -- the point of it -- over MORE
+        data than a dense factor can hold (x_data, y_data, noise_variances)."""
+        if self._native is None:
+            raise NotImplementedError("matrix_free evaluates the kernel on the device: a kernel callable stays with the dense GP "
+                                      "(use one of the named kernels)")
+        if self._noise_callable is not None or self._mean_callable is not None:
+            raise NotImplementedError("matrix_free takes noise variances as numbers and the default prior mean: noise and mean "
+                                      "callables stay with the dense GP")
+        if self.y_data.shape[1] != 1:
+            raise NotImplementedError("matrix_free takes one column of y (fvGP / x_out: the dense GP has it)")
+        if (x_data is None) != (y_data is None):
+            raise Exception("x_data and y_data come together")
+        if x_data is None:
+            x_data, y_data = self.x_data, self.y_data[:, 0]
+            if noise_variances is None:
+                noise_variances = self.noise_variances
+        return MatrixFreeGP(x_data, y_data, self._hps.copy(), noise_variances=noise_variances, kernel_function=self._native, args=args)

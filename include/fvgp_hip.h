@@ -51,6 +51,9 @@ enum fvgp_uplo { FVGP_FULL = 0, FVGP_LOWER = 1 };
 
 #define FVGP_TILE 128
 #define FVGP_MAX_DIM 16     /* input dimension limit of the assembly kernels */
+#define FVGP_MATVEC_CHUNK 4096   /* rows of x2 per chunk sum of fvgp_hip_kmatvec (part of its bit contract) */
+#define FVGP_PCG_MAX_RHS 16      /* right-hand sides per call of fvgp_hip_pcg */
+#define FVGP_PCG_MAX_RANK 1024   /* largest rank of the pivoted-Cholesky preconditioner */
 #define FVGP_MAX_RHS_VEC 8  /* potrs switches from the GEMV path to the GEMM path above this */
 #define FVGP_CHAIN_MAX_BLOCKS 32   /* widest panel (in 128-column blocks) the resident panel kernel takes; wider ones use the launch-per-step chain */
 #define FVGP_BATCH_MAX_DIM 4096    /* largest per-problem square the batched evaluation takes (32 block columns) */
@@ -118,6 +121,8 @@ int fvgp_hip_stream_destroy(void *stream);
  *       points as two halves on two streams) ("order"), "potri_kminor" (1: POTRI on (M,K) x (N,K) products only) ("order");
  *   batch selection: "select_block" (65536: candidates per pair of launches of fvgp_hip_select_batch, a multiple of 64, at most 65536;
  *       the results have the same bits for every value);
+ *   matrix-free product: "matvec_split" (0: fvgp_hip_kmatvec deals chunk ranges of x2 over gridDim.y only while the 64-row blocks of
+ *       x1 cannot fill the chip; 1: never; k: over k workgroups per 64 rows; the results have the same bits for every value);
  *   diagnostics: "chain_stamps" / "leaf_stamps" (device pointers, 0 = off: in-kernel timestamps of the panel kernel's hand-offs /
  *       the leaf's phases).
  * The library reads no environment variable.  The Python binding (fvgp_amd/_lib.py, Handle) applies FVGP_<KEY>=<integer> for the keys
@@ -610,6 +615,80 @@ int64_t fvgp_hip_select_workspace_bytes(int64_t n, int64_t P, int q);
 /* bytes of the caller-owned scratch of fvgp_hip_mvn_sample: (2 padded_dim(n) padded_dim(nsamp) + 128 padded_dim(n)) doubles -- the
  * normals, the product and the masked diagonal tiles; -1 for n < 1 or nsamp < 1 */
 int64_t fvgp_hip_mvn_sample_workspace_bytes(int64_t n, int64_t nsamp);
+
+/* ---- matrix-free solves (csrc/matrix_free.hip) --------------------------------------
+ * (K(theta) + V) X = B without ever storing K: memory O(n (rank + s)).  What gp2Scale reaches with sparse kernels
+ * (fvgp/gp2Scale_covariance.py) is reached here for the dense stationary kernels by preconditioned conjugate gradients.
+ *
+ * fvgp_hip_kmatvec: Y = K(x1, x2; theta) B + diag(vdiag) B.  x1 (n1, d), x2 (n2, d), B (n2, ldb >= s), Y (n1, ldy >= s), vdiag (n1) or
+ * NULL (only with n1 == n2): device, row-major, fp64.  Y is written inside its n1 x s view only.  The columns go in groups of 16, 8, 4
+ * or 1 (the narrowest that holds what is left); each kernel entry is evaluated once per group.  Asynchronous.
+ * BIT CONTRACT: Y[i][c] is a function of (x1_i, x2, B[:, c], theta, vdiag_i) alone -- the same bits whatever n1 is, whichever rows and
+ * columns share the call, whatever the grouping and for every "matvec_split".  The order: x2 in chunks of FVGP_MATVEC_CHUNK rows, a
+ * chunk in slices of 256; wave w of four sums rows [64 w, 64 w + 64) of every slice of the chunk, even and odd rows apart; the chunk's sum
+ * is (((e0 + o0) + (e1 + o1)) + (e2 + o2)) + (e3 + o3); chunk sums are added to 0 in ascending order; vdiag_i B[i][c] enters as the last fused
+ * multiply-add.
+ * work: device scratch of fvgp_hip_kmatvec_workspace_bytes(n1, n2, s) bytes for the split form (per-chunk sums); NULL or less is fine
+ * unless "matvec_split" > 1 forces a split (option 0 then simply does not split).
+ * Errors (argument numbers, nothing is launched): -1 h, -2 unknown kernel_id, -3 x1, -4 n1 < 1, -5 x2, -6 n2 < 1, -7 d outside
+ * 1 .. FVGP_MAX_DIM, -8 theta_host, -9 too few hyperparameters, -10 vdiag with n1 != n2, -11 B, -12 ldb < s, -13 s < 1, -14 Y,
+ * -15 ldy < s, -16 work not 8-byte aligned, -17 work_bytes negative, or too small for a forced split. */
+int fvgp_hip_kmatvec(fvgp_handle *h, int kernel_id, const double *x1, int64_t n1, const double *x2, int64_t n2, int d,
+                     const double *theta_host, int ntheta, const double *vdiag_or_null, const double *B, int64_t ldb, int s,
+                     double *Y, int64_t ldy, double *work, int64_t work_bytes);
+/* bytes of the split form's per-chunk sums: ceil(n2 / FVGP_MATVEC_CHUNK) n1 min(group width of s, 16) doubles; -1 for n1, n2 or s < 1 */
+int64_t fvgp_hip_kmatvec_workspace_bytes(int64_t n1, int64_t n2, int s);
+/* Greedy pivoted Cholesky of K(x, x; theta) (no noise), rank <= q, K never formed.  d = sigma^2 at every point; step t = 0 .. q-1:
+ *     j = argmax d over the points not picked yet, ties to the lowest index (step 0 picks point 0);
+ *     if d_j <= tol sigma^2 (or nothing is left): piv_out[t .. q-1] = -1 and the call ends there (decided on the device; the remaining
+ *         rows of G stay ZERO rows, so G^T G and every shape downstream are unaffected);
+ *     c_i = (k(x_i, x_j) - sum_{s<t} G[s][i] G[s][j]) / sqrt(d_j);   G[t][i] = c_i;   d_i <- max(d_i - c_i^2, 0).
+ * A point's column of G has the same bits whatever else is in the call as long as the pivots are the same.
+ *   x (n, d) device; G (q, ldg >= n) device, written inside its (q, n) view only; piv_out (q) int64 device; resid_diag_out (n) device or
+ *   NULL: d after the last step; work: device, 16-byte aligned, fvgp_hip_pchol_workspace_bytes(n, q) bytes; rank_host: the achieved rank.
+ * All q steps are enqueued by this one call; the stream is drained once, at the end, for the rank.
+ * Errors: -1 h, -2 unknown kernel_id, -3 x, -4 n < 1, -5 d, -6 theta_host, -7 too few hyperparameters, -8 q < 1, -9 tol negative or no
+ * number, -10 G, -11 ldg < n, -12 piv_out, -14 work NULL or misaligned, -15 work_bytes too small, -16 rank_host. */
+int fvgp_hip_pchol(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta_host, int ntheta,
+                   int q, double tol, double *G, int64_t ldg, int64_t *piv_out, double *resid_diag_out,
+                   double *work, int64_t work_bytes, int *rank_host);
+/* the slot, the state words, two doubles per 64 points, one byte per point and the residual diagonal: O(n); -1 for n or q < 1 */
+int64_t fvgp_hip_pchol_workspace_bytes(int64_t n, int q);
+/* The preconditioner M = G^T G + D, D = diag(vdiag), through Woodbury: M^-1 = D^-1 - D^-1 G^T C^-1 G D^-1 with C = I + G D^-1 G^T.
+ * Forms C (q x q; G is NOT modified) by plain streaming kernels -- partial sums over chunks of 8192 points, every entry's points in
+ * ascending order, chunks in ascending order -- into C (padded_dim(q) rows, ldc even and >= padded_dim(q), 16-byte aligned) and factors
+ * it in place like fvgp_hip_potrf; *info_host as there (0, or the failing pivot).  work: fvgp_hip_precond_workspace_bytes(n, q) bytes.
+ * Errors: -1 h, -2 G, -3 ldg < n, -4 q outside 1 .. FVGP_PCG_MAX_RANK, -5 n < 1, -6 vdiag, -7 C NULL or misaligned, -8 ldc, -9 work,
+ * -10 work_bytes too small, -11 info_host. */
+int fvgp_hip_precond_factor(fvgp_handle *h, const double *G, int64_t ldg, int q, int64_t n, const double *vdiag,
+                            double *C, int64_t ldc, double *work, int64_t work_bytes, int *info_host);
+int64_t fvgp_hip_precond_workspace_bytes(int64_t n, int q);      /* ceil(n / 8192) q^2 doubles; -1 for n or q < 1 */
+/* Preconditioned conjugate gradients for (K(x, x; theta) + D) X = B, s <= FVGP_PCG_MAX_RHS columns: s independent recurrences that share
+ * every product (fvgp_hip_kmatvec).  rho, alpha, beta, |r| and |b| live per column on the device; every dot product is reduced in an
+ * order n alone fixes.  A column FREEZES (no vector kernel writes it again) once its recurrence residual is <= tol |b|, after max_iter
+ * iterations of its own, or on breakdown (p^T A p or r^T z not positive or not finite).  The host reads the status words every
+ * check_every iterations.  When every column is frozen one more product gives the TRUE residual b - A x: a column above tol that met
+ * its recurrence test restarts from the true residual, at most max_restarts times.
+ *   G (q, ldg) and C (factor of fvgp_hip_precond_factor): the preconditioner; q == 0 or G == NULL: Jacobi, D^-1.  M^-1 is applied as
+ *   two streaming products with G and one potrs per column on C.
+ *   warm != 0: X holds the initial guess (one more product); else the start is x = 0.  A zero column of B returns x = 0, 0 iterations.
+ *   iters_host, relres_host (true relative residual), status_host (0 converged, 1 not converged: iteration or restart limit,
+ *   2 breakdown): s entries each.  Returns 0 whenever the call ran: non-convergence is data.  Synchronous.
+ * BIT CONTRACT: column c of X, its iters and its relres have the same bits whatever other columns share the call, and the same call
+ * returns the same bits every run.
+ *   work: device, 16-byte aligned, fvgp_hip_pcg_workspace_bytes(n, q) bytes.
+ * Errors: -1 h, -2 unknown kernel_id, -3 x, -4 n < 1, -5 d, -6 theta_host, -7 too few hyperparameters, -8 vdiag, -10 ldg < n,
+ * -11 q outside 0 .. FVGP_PCG_MAX_RANK, -12 C NULL or misaligned with q > 0, -13 ldc, -14 B, -15 ldb < s, -16 s outside
+ * 1 .. FVGP_PCG_MAX_RHS, -17 X, -18 ldx < s, -20 tol not positive, -21 max_iter < 1, -22 check_every < 1, -23 max_restarts < 0,
+ * -24 work NULL or misaligned, -25 work_bytes too small, -26 iters_host, -27 relres_host, -28 status_host. */
+int fvgp_hip_pcg(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta_host, int ntheta,
+                 const double *vdiag, const double *G_or_null, int64_t ldg, int q, const double *C, int64_t ldc,
+                 const double *B, int64_t ldb, int s, double *X, int64_t ldx, int warm,
+                 double tol, int max_iter, int check_every, int max_restarts,
+                 double *work, int64_t work_bytes, int *iters_host, double *relres_host, int *status_host);
+/* four (n, 16) vectors, the rank's partial sums (ceil(n / 4096) q 16 doubles), the dot products' partials and, while the product would
+ * split by itself, its per-chunk sums; -1 for n < 1 or q < 0 */
+int64_t fvgp_hip_pcg_workspace_bytes(int64_t n, int q);
 
 /* ---- building blocks exported for the parity tests --------------------------------------
  * C (M,N) = alpha * opA * opB + beta * C on fp64 MFMA.  M, N multiples of 128, K of 16.
