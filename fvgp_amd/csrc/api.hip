@@ -2,6 +2,7 @@
 // (ensure_*) and the blocked Cholesky drivers with their entries.  The other entries: tri_solve.hip (solves, POTRI), evaluate.hip (fused
 // single evaluations), batch_api.hip (batched evaluations), blas_api.hip (thin products, reductions, diagnostics).  No torch types.
 #include "common.h"
+#include "kernel_family.h"
 #include <string.h>
 
 // ---------------------------------------------------------------------------------------
@@ -349,6 +350,14 @@ int check_square(const void *A, int64_t n, int64_t ld, int argA, int argn, int a
     if (n <= 0) return -argn;
     if (ld < pad128(n) || (ld & 1)) { fvgp_set_error("leading dimension must be even and >= padded_dim(n)"); return -argld; }
     if ((uintptr_t)A & 15) { fvgp_set_error("matrix base must be 16-byte aligned"); return -argA; }
+    return 0;
+}
+
+// the run of checks behind a known kernel id: the inputs' dimension, theta (on the host) and its length
+int check_kernel_args(int kernel_id, int d, const double *theta, int ntheta, int arg_d, int arg_theta, int arg_ntheta) {
+    if (d < 1 || d > FVGP_MAX_DIM) { fvgp_set_error("input dimension out of range"); return -arg_d; }
+    if (!theta) return -arg_theta;
+    if (ntheta < kernel_param_count(kernel_id, d)) { fvgp_set_error("too few hyperparameters for this kernel"); return -arg_ntheta; }
     return 0;
 }
 

@@ -1,5 +1,5 @@
-// The running best {score, index} of an argmax with ties to the lowest index (select.hip, matrix_free.hip): one definition of the
-// order and of the wave's reduction.
+// The running best {score, index} of an argmax with ties to the lowest index: one definition of the order and of the wave's reduction,
+// for the pick and the 64-candidate partials of the greedy pivot core (pivot.h).
 #pragma once
 #include "common.h"
 

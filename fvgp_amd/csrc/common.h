@@ -163,6 +163,7 @@ int fvgp_hip_fail(hipError_t e, const char *what, int line);
     } while (0)
 
 static inline int64_t pad128(int64_t n) { return (n + TILE - 1) / TILE * TILE; }
+static inline int64_t even_up(int64_t v) { return (v + 1) & ~(int64_t)1; }      // workspace pieces in doubles: every offset stays 16-byte aligned
 
 // ---- launches implemented in the .hip units ------------------------------------------------
 struct GemmDesc {
@@ -324,6 +325,7 @@ int launch_s_finish_batch(fvgp_handle *h, double *S, int64_t s_stride, int64_t l
 
 // host helpers shared by the units of the C ABI (api.hip unless noted)
 int check_square(const void *A, int64_t n, int64_t ld, int argA, int argn, int argld);
+int check_kernel_args(int kernel_id, int d, const double *theta, int ntheta, int arg_d, int arg_theta, int arg_ntheta);   // kernel_id: a known one
 int ensure_linv(fvgp_handle *h, const double *L, int64_t n, int64_t ldl);
 int ensure_winv(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, int64_t WB = 1024, int64_t upto = 0);
 int ensure_scratch(fvgp_handle *h, int64_t np);

@@ -308,14 +308,12 @@ int fvgp_hip_loglik_hess(fvgp_handle *h, int kernel_id, const double *x, int64_t
     if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
     if (!x) return -3;
     if (n <= 0) return -4;
-    if (d < 1 || d > FVGP_MAX_DIM) { fvgp_set_error("input dimension out of range"); return -5; }
-    if (!theta) return -6;
+    int rc = check_kernel_args(kernel_id, d, theta, ntheta, 5, 6, 7); if (rc) return rc;
     const int nk = kernel_param_count(kernel_id, d);
-    if (ntheta < nk) { fvgp_set_error("too few hyperparameters for this kernel"); return -7; }
     if (!alpha) return -8;
     if (ncol < 1) return -9;
     if (component < 0 || component >= ncol) { fvgp_set_error("loglik_hess: 0 <= component < ncol"); return -10; }
-    int rc = check_square(KV, n, ld, 11, 4, 12);
+    rc = check_square(KV, n, ld, 11, 4, 12);
     if (rc) return rc;
     rc = check_square(work, n, ldw, 13, 4, 14);
     if (rc) return rc;

@@ -2,21 +2,22 @@
 // the preconditioned conjugate gradients whose scalars stay on the device.
 //
 // fvgp_hip_kmatvec   Y = K(x1, x2) B + diag(v) B.  select_cross_kernel widened: lanes along 64 output rows, the x2 rows and S entries of
-//     B per row staged in LDS (slice_sum.h, broadcast reads), S accumulator pairs per lane, so one exp (plus the rsq of the Matern
-//     kinds) serves S columns.  The order of every sum is a function of n2 alone: x2 is cut into chunks of MATVEC_CHUNK rows, a chunk
-//     into slices of SLICE_ROWS; wave w sums rows [64 w, 64 w + 64) of every slice of the chunk into an even-row and an odd-row
-//     accumulator; the chunk's sum is (((e0 + o0) + (e1 + o1)) + (e2 + o2)) + (e3 + o3); chunk sums are added to 0 in ascending order;
-//     v_i B_ic enters as the last fused multiply-add.  A workgroup that walks all chunks (gridDim.y == 1) and a launch that deals
-//     chunk ranges over gridDim.y, parks the per-chunk sums and adds them in a second pass give the same bits.
-// fvgp_hip_pchol     greedy pivoted Cholesky of K(x, x), q steps enqueued at once: pick (one workgroup, argmax.h) and a fused
-//     column + downdate kernel (one thread per point).
+//     B per row staged in LDS (slice_sum.h, broadcast reads), S accumulator pairs per lane filled by the same row loop (slice_rows),
+//     so one exp (plus the rsq of the Matern kinds) serves S columns.  The order of every sum is a function of n2 alone: x2 is cut
+//     into chunks of MATVEC_CHUNK rows, a chunk into slices of SLICE_ROWS; wave w sums rows [64 w, 64 w + 64) of every slice of the
+//     chunk into an even-row and an odd-row accumulator; the chunk's sum is (((e0 + o0) + (e1 + o1)) + (e2 + o2)) + (e3 + o3); chunk
+//     sums are added to 0 in ascending order; v_i B_ic enters as the last fused multiply-add.  A workgroup that walks all chunks
+//     (gridDim.y == 1) and a launch that deals chunk ranges over gridDim.y, parks the per-chunk sums and adds them in a second pass
+//     give the same bits.
+// fvgp_hip_pchol     greedy pivoted Cholesky of K(x, x), q steps enqueued at once: selection's greedy pivot core (pivot.h) with the
+//     data as their own candidates, no conditioning (pivot_downdate_kernel<KIND, CROSS = false>) and no noise.
 // fvgp_hip_precond_factor   C = I + G D^-1 G^T in fixed-order chunks of PF_CHUNK points, factored by potrf_driver.
 // fvgp_hip_pcg       s <= 16 independent recurrences that share the matvec; every vector kernel reads the per-column state
 //     (active, alpha, beta) from device memory, the host reads the status words every `check_every` iterations.
 #include "radial.h"
 #include "kernel_family.h"
 #include "slice_sum.h"
-#include "argmax.h"
+#include "pivot.h"
 #include <math.h>
 #include <string.h>
 
@@ -49,9 +50,9 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(MvArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long loc = (long)blockIdx.x * 64 + lane;
     const long i = loc < a.n1 ? loc : a.n1 - 1;
-    double u[DD];
+    double u[DD], il[DD];                                     // (il: a copy, so that the address of the kernel's arguments is never taken)
 #pragma unroll
-    for (int k = 0; k < DD; ++k) u[k] = k < d ? a.x1[i * d + k] : 0.0;
+    for (int k = 0; k < DD; ++k) { u[k] = k < d ? a.x1[i * d + k] : 0.0; il[k] = a.il[k]; }
     const long ch0 = (long)blockIdx.y * a.cpy, ch1 = ch0 + a.cpy < a.nchunks ? ch0 + a.cpy : a.nchunks;
     double tot[S];
 #pragma unroll
@@ -67,32 +68,7 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(MvArgs a) {
             slice_stage_cols<DD, S>(sx, sb, a.x2, a.B, a.ldb, a.c0, a.sc, a.n2, d, row0, tid);
             __syncthreads();
             const int r0 = wave * SLICE_WAVE_ROWS, rows = slice_wave_rows(a.n2, row0, wave);
-            int r = 0;
-            for (; r + 1 < rows; r += 2) {
-                const double *xa = sx + (r0 + r) * DD, *xb = xa + DD;
-                double ra = 0.0, rb = 0.0;
-#pragma unroll
-                for (int k = 0; k < DD; ++k)
-                    if (k < d) {
-                        const double ea = (u[k] - xa[k]) * a.il[k], eb = (u[k] - xb[k]) * a.il[k];
-                        ra = fma(ea, ea, ra); rb = fma(eb, eb, rb);
-                    }
-                const double ka = radial<KIND>(ra, a.sig), kb = radial<KIND>(rb, a.sig);
-                const double *ba = sb + (r0 + r) * S, *bb = ba + S;
-#pragma unroll
-                for (int c = 0; c < S; ++c) { s0[c] = fma(ka, ba[c], s0[c]); s1[c] = fma(kb, bb[c], s1[c]); }
-            }
-            if (r < rows) {
-                const double *xa = sx + (r0 + r) * DD;
-                double ra = 0.0;
-#pragma unroll
-                for (int k = 0; k < DD; ++k)
-                    if (k < d) { const double ea = (u[k] - xa[k]) * a.il[k]; ra = fma(ea, ea, ra); }
-                const double ka = radial<KIND>(ra, a.sig);
-                const double *ba = sb + (r0 + r) * S;
-#pragma unroll
-                for (int c = 0; c < S; ++c) s0[c] = fma(ka, ba[c], s0[c]);
-            }
+            slice_rows<KIND, DD, S>(sx, sb, r0, rows, d, u, il, a.sig, s0, s1);
         }
         __syncthreads();                                      // every wave is done with the staged rows
         if (wave > 0) {
@@ -189,117 +165,11 @@ int launch_kmatvec(fvgp_handle *h, const KmatDesc &k, const double *B, int64_t l
 }
 
 // ------------------------------------------------------------------------------------------------------ the pivoted Cholesky
-struct PcState { double dj; long long j, done, rank; };
-
-struct PcArgs {
-    const double *x;
-    double *dres;                            // (n) the residual diagonal
-    double *G; long ldg;                     // (q, n)
-    double *slot;                            // (FVGP_MAX_DIM) x_j
-    double *best;                            // (nparts, 2): score, index (as a double: n < 2^53)
-    PcState *st;
-    unsigned char *taken;                    // (n) 1 once the point has been a pivot
-    long long *piv;                          // (q)
-    long n;
-    int d, q, t;
-    double sig, tol;
-    double il[FVGP_MAX_DIM];
-};
-
-__device__ __forceinline__ Best pc_candidate(long i, double dv, bool taken) {
-    Best b;
-    b.score = dv;
-    b.idx = taken || !(dv >= 0.0) ? -1 : i;
-    return b;
-}
-
-__global__ __launch_bounds__(256) void pchol_init_kernel(PcArgs a) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    if (i == 0) { a.st->done = 0; a.st->j = -1; a.st->dj = 1.0; a.st->rank = 0; }
-    Best b{0.0, -1};
-    if (i < a.n) { a.dres[i] = a.sig; a.taken[i] = 0; b = pc_candidate(i, a.sig, false); }
-    b = wave_best(b);
-    if (lane == 0 && i < a.n) { double *o = a.best + 2 * (i / 64); o[0] = b.score; o[1] = (double)b.idx; }
-}
-
-// step t: the partials -> j_t (one workgroup); exhausted once the best d_j <= tol sigma^2
-__global__ __launch_bounds__(256) void pchol_pick_kernel(PcArgs a) {
-    __shared__ double ss[256];
-    __shared__ long si[256];
-    const int tid = threadIdx.x;
-    if (a.st->done) return;                                   // (uniform: written by an earlier launch)
-    const long nparts = (a.n + 63) / 64;
-    Best b{0.0, -1};
-    for (long k = tid; k < nparts; k += 256) {
-        const Best o{a.best[2 * k], (long)a.best[2 * k + 1]};
-        if (better(o, b)) b = o;
-    }
-    ss[tid] = b.score; si[tid] = b.idx;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (tid < off) {
-            const Best m{ss[tid], si[tid]}, o{ss[tid + off], si[tid + off]};
-            if (better(o, m)) { ss[tid] = o.score; si[tid] = o.idx; }
-        }
-        __syncthreads();
-    }
-    if (tid != 0) return;
-    const long j = si[0];
-    const double dj = j >= 0 ? a.dres[j] : 0.0;
-    if (j < 0 || dj <= a.tol * a.sig) {                       // exhausted: this row of G and every later one stay zero
-        a.st->done = 1;
-        for (int s = a.t; s < a.q; ++s) a.piv[s] = -1;
-        return;
-    }
-    a.piv[a.t] = j; a.taken[j] = 1;
-    a.st->j = j; a.st->dj = dj; a.st->rank = a.t + 1;
-    for (int k = 0; k < a.d; ++k) a.slot[k] = a.x[j * a.d + k];
-}
-
-// one thread per point: c_i = (k(x_i, x_j) - sum_{s<t} G[s,i] G[s,j]) / sqrt(d_j), G[t,i], d_i and the partial of its 64 points
-template <int KIND>
-__global__ __launch_bounds__(256) void pchol_column_kernel(PcArgs a) {
-    if (a.st->done) return;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    const long j = a.st->j;
-    Best b{0.0, -1};
-    if (i < a.n) {
-        double r2 = 0.0;
-        for (int k = 0; k < a.d; ++k) { const double e = (a.x[i * a.d + k] - a.slot[k]) * a.il[k]; r2 = fma(e, e, r2); }
-        double acc = 0.0;
-        for (int s = 0; s < a.t; ++s) acc = fma(a.G[s * a.ldg + i], a.G[s * a.ldg + j], acc);
-        const double c = (radial<KIND>(r2, a.sig) - acc) / sqrt(a.st->dj);
-        a.G[(long)a.t * a.ldg + i] = c;
-        double dv = fma(-c, c, a.dres[i]);
-        if (dv < 0.0) dv = 0.0;
-        a.dres[i] = dv;
-        b = pc_candidate(i, dv, a.taken[i] != 0);
-    }
-    b = wave_best(b);
-    if (lane == 0 && i < a.n) { double *o = a.best + 2 * (i / 64); o[0] = b.score; o[1] = (double)b.idx; }
-}
-
 __global__ __launch_bounds__(256) void mf_zero_rows_kernel(double *A, long ld, long rows, long cols) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= rows * cols) return;
     const long r = e / cols;
     A[r * ld + (e - r * cols)] = 0.0;
-}
-
-struct PcLayout { int64_t slot, state, best, taken, dres, total; };      // offsets in doubles
-PcLayout pc_layout(int64_t n) {
-    PcLayout l;
-    auto even = [](int64_t v) { return (v + 1) & ~(int64_t)1; };
-    int64_t o = 0;
-    l.slot = o; o += even(FVGP_MAX_DIM);
-    l.state = o; o += even((int64_t)(sizeof(PcState) / sizeof(double)));
-    l.best = o; o += even(2 * ((n + 63) / 64));
-    l.taken = o; o += even((n + 7) / 8);
-    l.dres = o; o += even(n);
-    l.total = o;
-    return l;
 }
 
 // ------------------------------------------------------------------------------------------------------ the preconditioner
@@ -584,7 +454,6 @@ __global__ __launch_bounds__(256) void pcg_apply_kernel(const double *G, long ld
 struct PcgLayout { int64_t R, Z, P, AP, T, tpart, part0, part1, state, mv, total; int64_t nblk, tchunks, mv_doubles; };
 PcgLayout pcg_layout(int64_t n, int q) {
     PcgLayout l;
-    auto even = [](int64_t v) { return (v + 1) & ~(int64_t)1; };
     const int64_t qp = q > 0 ? pad128(q) : 0;
     l.nblk = (n + 255) / 256;                 // the apply kernel's blocks (>= the DOT_ROWS blocks of the other partials)
     l.tchunks = (n + PT_CHUNK - 1) / PT_CHUNK;
@@ -594,7 +463,7 @@ PcgLayout pcg_layout(int64_t n, int q) {
     l.T = o; o += qp * PCG_LD;
     l.tpart = o; o += l.tchunks * q * PCG_LD;
     l.part0 = o; o += l.nblk * PCG_LD; l.part1 = o; o += l.nblk * PCG_LD;
-    l.state = o; o += even((int64_t)((sizeof(PcgState) + 7) / 8));
+    l.state = o; o += even_up((int64_t)((sizeof(PcgState) + 7) / 8));
     l.mv = o; o += l.mv_doubles;
     l.total = o;
     return l;
@@ -618,9 +487,7 @@ int fvgp_hip_kmatvec(fvgp_handle *h, int kernel_id, const double *x1, int64_t n1
     if (n1 <= 0) return -4;
     if (!x2) return -5;
     if (n2 <= 0) return -6;
-    if (d < 1 || d > FVGP_MAX_DIM) { fvgp_set_error("input dimension out of range"); return -7; }
-    if (!theta) return -8;
-    if (ntheta < kernel_param_count(kernel_id, d)) { fvgp_set_error("too few hyperparameters for this kernel"); return -9; }
+    int rc = check_kernel_args(kernel_id, d, theta, ntheta, 7, 8, 9); if (rc) return rc;
     if (vdiag && n1 != n2) { fvgp_set_error("kmatvec: vdiag needs n1 == n2"); return -10; }
     if (!B) return -11;
     if (s < 1) return -13;
@@ -632,7 +499,7 @@ int fvgp_hip_kmatvec(fvgp_handle *h, int kernel_id, const double *x1, int64_t n1
     if ((n1 + 63) / 64 > 0x7fffffffLL) return -4;
     HIPCHK(hipSetDevice(h->device));
     KmatDesc k{};
-    int rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
+    rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
     k.x1 = x1; k.n1 = n1; k.x2 = x2; k.n2 = n2; k.vdiag = vdiag;
     rc = launch_kmatvec(h, k, B, ldb, s, Y, ldy, work, work ? work_bytes / 8 : 0, false);
     return rc == -1 ? -17 : rc;
@@ -640,7 +507,7 @@ int fvgp_hip_kmatvec(fvgp_handle *h, int kernel_id, const double *x1, int64_t n1
 
 int64_t fvgp_hip_pchol_workspace_bytes(int64_t n, int q) {
     if (n < 1 || q < 1) return -1;
-    return pc_layout(n).total * (int64_t)sizeof(double);
+    return (pivot_layout(0, n, 2).end + even_up(n)) * (int64_t)sizeof(double);      // the core's pieces, then the residual diagonal
 }
 
 int fvgp_hip_pchol(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta, int ntheta,
@@ -650,9 +517,7 @@ int fvgp_hip_pchol(fvgp_handle *h, int kernel_id, const double *x, int64_t n, in
     if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
     if (!x) return -3;
     if (n <= 0) return -4;
-    if (d < 1 || d > FVGP_MAX_DIM) { fvgp_set_error("input dimension out of range"); return -5; }
-    if (!theta) return -6;
-    if (ntheta < kernel_param_count(kernel_id, d)) { fvgp_set_error("too few hyperparameters for this kernel"); return -7; }
+    int rc = check_kernel_args(kernel_id, d, theta, ntheta, 5, 6, 7); if (rc) return rc;
     if (q < 1) return -8;
     if (!(tol >= 0.0)) return -9;
     if (!G) return -10;
@@ -663,14 +528,16 @@ int fvgp_hip_pchol(fvgp_handle *h, int kernel_id, const double *x, int64_t n, in
     if (!rank_host) return -16;
     HIPCHK(hipSetDevice(h->device));
     KmatDesc k{};
-    int rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
-    const PcLayout lay = pc_layout(n);
-    PcArgs a;
-    a.x = x; a.dres = work + lay.dres; a.G = G; a.ldg = ldg; a.slot = work + lay.slot; a.best = work + lay.best;
-    a.st = reinterpret_cast<PcState *>(work + lay.state);
+    rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
+    const PivotLayout lay = pivot_layout(0, n, 2);
+    // selection's run with the data as their own candidates: no conditioning, no noise, d = sigma^2 at the start, G the caller's
+    PivotArgs a{};
+    a.x = x; a.xc = x; a.var = work + lay.end; a.G = G; a.ldg_in = ldg;
+    a.slot = work + lay.slot; a.best = work + lay.best;
+    a.st = reinterpret_cast<PivotState *>(work + lay.state);
     a.taken = reinterpret_cast<unsigned char *>(work + lay.taken);
-    a.piv = reinterpret_cast<long long *>(piv_out);
-    a.n = n; a.d = d; a.q = q; a.t = 0; a.sig = k.sig; a.tol = tol;
+    a.idx = reinterpret_cast<long long *>(piv_out);
+    a.n = n; a.P = n; a.cn = n; a.d = d; a.q = q; a.sig = k.sig; a.tol = tol;
     for (int i = 0; i < FVGP_MAX_DIM; ++i) a.il[i] = k.invl[i];
     const unsigned nb = (unsigned)((n + 255) / 256);
     // the rows an exhausted run never reaches are zero rows: G is cleared first, inside its (q, n) view only
@@ -680,23 +547,23 @@ int fvgp_hip_pchol(fvgp_handle *h, int kernel_id, const double *x, int64_t n, in
                            (long)rows, (long)n);
         HIPCHK(hipGetLastError());
     }
-    hipLaunchKernelGGL(pchol_init_kernel, dim3(nb), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL(pivot_init_kernel, dim3(nb), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
     for (int t = 0; t < q; ++t) {
         a.t = t;
-        hipLaunchKernelGGL(pchol_pick_kernel, dim3(1), dim3(256), 0, h->stream, a);
+        hipLaunchKernelGGL(pivot_pick_kernel, dim3(1), dim3(256), 0, h->stream, a);
         HIPCHK(hipGetLastError());
         dispatch_kind(k.kind, [&](auto KIND) {
-            hipLaunchKernelGGL((pchol_column_kernel<decltype(KIND)::value>), dim3(nb), dim3(256), 0, h->stream, a);
+            hipLaunchKernelGGL((pivot_downdate_kernel<decltype(KIND)::value, false>), dim3(nb), dim3(256), 0, h->stream, a, 0L);
         });
         HIPCHK(hipGetLastError());
     }
     if (resid_diag_out)
-        HIPCHK(hipMemcpyAsync(resid_diag_out, a.dres, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    long long rank = 0;
-    HIPCHK(hipMemcpyAsync(&rank, &a.st->rank, sizeof(rank), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(resid_diag_out, a.var, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    long long done = 0;                                           // 0, or 1 + the step that found nothing left to pick
+    HIPCHK(hipMemcpyAsync(&done, &a.st->done, sizeof(done), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    *rank_host = (int)rank;
+    *rank_host = done ? (int)done - 1 : q;
     return 0;
 }
 
@@ -744,15 +611,13 @@ int fvgp_hip_pcg(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int 
     if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
     if (!x) return -3;
     if (n <= 0) return -4;
-    if (d < 1 || d > FVGP_MAX_DIM) { fvgp_set_error("input dimension out of range"); return -5; }
-    if (!theta) return -6;
-    if (ntheta < kernel_param_count(kernel_id, d)) { fvgp_set_error("too few hyperparameters for this kernel"); return -7; }
+    int rc = check_kernel_args(kernel_id, d, theta, ntheta, 5, 6, 7); if (rc) return rc;
     if (!vdiag) { fvgp_set_error("pcg: the noise variances are the Jacobi part of the preconditioner and must be given"); return -8; }
     if (!G) q = 0;
     if (q < 0 || q > FVGP_PCG_MAX_RANK) { fvgp_set_error("pcg: rank outside 0 .. FVGP_PCG_MAX_RANK"); return -11; }
     if (q > 0) {
         if (ldg < n) return -10;
-        int rc = check_square(C, q, ldc, 12, 11, 13);
+        rc = check_square(C, q, ldc, 12, 11, 13);
         if (rc) return rc;
     }
     if (!B) return -14;
@@ -771,7 +636,7 @@ int fvgp_hip_pcg(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int 
     if (!status_host) return -28;
     HIPCHK(hipSetDevice(h->device));
     KmatDesc k{};
-    int rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
+    rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
     k.x1 = x; k.n1 = n; k.x2 = x; k.n2 = n; k.vdiag = vdiag;
     const PcgLayout lay = pcg_layout(n, q);
     PcgVec a;

@@ -2,8 +2,11 @@
 // workgroup of four waves per (64 points, slice).  The slice's x rows and one vector entry per row are staged in LDS once (every lane
 // reads the same row: broadcast reads), each wave takes SLICE_WAVE_ROWS of them, and the sums of waves 1 .. 3 are parked in LDS for
 // wave 0 to add in wave order.  The split is a function of n alone: a point's sums have the same bits whatever else rides in the launch.
+// slice_rows is the row loop of the two kernels whose summand is k(u, x_r) times S staged entries (select_cross_kernel, S = 1, and
+// kmatvec_kernel); posterior_grad.hip has its own.
 #pragma once
 #include "common.h"
+#include "radial.h"
 
 namespace {
 
@@ -48,6 +51,39 @@ __device__ __forceinline__ void slice_stage_cols(double *sx, double *sb, const d
 __device__ __forceinline__ int slice_wave_rows(long n, long row0, int wave) {
     const long left = n - row0 - (long)wave * SLICE_WAVE_ROWS;
     return left >= SLICE_WAVE_ROWS ? SLICE_WAVE_ROWS : (left > 0 ? (int)left : 0);
+}
+
+// this wave's rows [r0, r0 + rows) of the staged slice against the lane's point u: s0[c] += k(u, x_r) sb[r][c] over the even rows,
+// s1[c] over the odd ones (two exp chains in flight; the caller adds the pair once, at the end), then an odd last row into s0
+template <int KIND, int DD, int S>
+__device__ __forceinline__ void slice_rows(const double *sx, const double *sb, int r0, int rows, int d, const double (&u)[DD],
+                                           const double (&il)[DD], double sig, double (&s0)[S], double (&s1)[S]) {
+    int r = 0;
+    for (; r + 1 < rows; r += 2) {
+        const double *xa = sx + (r0 + r) * DD, *xb = xa + DD;
+        double ra = 0.0, rb = 0.0;
+#pragma unroll
+        for (int k = 0; k < DD; ++k)
+            if (k < d) {
+                const double ea = (u[k] - xa[k]) * il[k], eb = (u[k] - xb[k]) * il[k];
+                ra = fma(ea, ea, ra); rb = fma(eb, eb, rb);
+            }
+        const double ka = radial<KIND>(ra, sig), kb = radial<KIND>(rb, sig);
+        const double *ba = sb + (r0 + r) * S, *bb = ba + S;
+#pragma unroll
+        for (int c = 0; c < S; ++c) { s0[c] = fma(ka, ba[c], s0[c]); s1[c] = fma(kb, bb[c], s1[c]); }
+    }
+    if (r < rows) {
+        const double *xa = sx + (r0 + r) * DD;
+        double ra = 0.0;
+#pragma unroll
+        for (int k = 0; k < DD; ++k)
+            if (k < d) { const double ea = (u[k] - xa[k]) * il[k]; ra = fma(ea, ea, ra); }
+        const double ka = radial<KIND>(ra, sig);
+        const double *ba = sb + (r0 + r) * S;
+#pragma unroll
+        for (int c = 0; c < S; ++c) s0[c] = fma(ka, ba[c], s0[c]);
+    }
 }
 
 // where wave w (1 .. 3) parks its nacc sums for this lane: sum s at [s * 64]

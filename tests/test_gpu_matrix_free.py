@@ -216,6 +216,56 @@ def test_pchol_bits_exhaustion_and_the_solve_behind_it(H):
     assert np.linalg.norm(X.cpu().numpy() - want) <= np.linalg.cond(A) * TOL * np.linalg.norm(want)
 
 
+def test_pchol_and_selection_share_kernels_not_state(H):
+    """fvgp_hip_pchol, fvgp_hip_select_batch and fvgp_hip_pchol again, back to back on one handle and in ONE workspace: the selection (the
+    information criterion, noise, repeats allowed, one that exhausts with repeats off) leaves nothing behind that the second
+    factorisation reads.  n = 65 is two 64-point partials with a ragged second one, and the point at index 64 is the second pivot.
+    Both factorisations: piv equal to the twin's (its picks lead by >= 1e-9 sigma^2 after the first, a tie that goes to index 0),
+    G within 1e-10 sigma^2 of it, rank 8; the second equal to the first bit for bit; the frames around every output untouched."""
+    from fvgp_amd import _lib
+    fx = mf.FIXTURES[2]
+    f = mf.fixture(fx)
+    kernel, theta, n, q, P = f["kernel"], f["theta"], 65, 8, 5
+    x, V = f["x"][:n].copy(), f["V"][:n].copy()
+    x[[13, 64]] = x[[64, 13]]
+    Gt, pivt, _, rankt, margins = mf.pchol_ref(mf.k_double(kernel, x, theta), q, sigma2=mf.SIGMA2)
+    assert rankt == q and pivt[1] == 64 and margins[1:].min() >= 1e-9 * mf.SIGMA2
+    xd, Vd = H.to_device(x), H.to_device(V)
+    dim = _lib.loglik_dim(n, 1)
+    KV, alpha = H.empty(dim, dim), H.empty(_lib.pad128(n), 1)
+    assert H.loglik(_kid(kernel), xd, theta, Vd, H.zeros(n, 1), KV, alpha)[3] == 0      # the factor of K + V for the selection
+    xcd, noise = H.to_device(np.random.default_rng(65).random((P, 2))), H.to_device(np.full(P, 0.05))
+    work = H.empty(max(_lib.pchol_workspace_bytes(n, q), _lib.select_workspace_bytes(n, P, q)) // 8)
+
+    def pchol():
+        gbig, G = _framed(H, (q, n))
+        pbig, piv = _framed(H, (q,), dtype=H.torch.int64)
+        rank = H.pchol(_kid(kernel), xd, theta, q, G, piv, work=work)
+        return (gbig, (q, n)), (pbig, (q,)), G, piv, rank
+
+    def select(**kw):
+        vbig, var = _framed(H, (P,))
+        var.fill_(mf.SIGMA2)
+        ibig, idx = _framed(H, (q,), dtype=H.torch.int64)
+        kbig, pick = _framed(H, (q,))
+        sbig, Gs = _framed(H, (q, P))
+        H.select_batch(_kid(kernel), xd, theta, KV, xcd, var, q, idx, pick, G_out=Gs, work=work, **kw)
+        return [(vbig, (P,)), (ibig, (q,)), (kbig, (q,)), (sbig, (q, P))], idx
+
+    fg1, fp1, G1, piv1, rank1 = pchol()
+    frames, idx_info = select(noise=noise, criterion=1, allow_repeats=True)
+    more, idx_plain = select()                                           # 5 candidates, 8 steps, no repeats: `done` is set
+    fg2, fp2, G2, piv2, rank2 = pchol()
+    H.sync()
+    assert idx_info.cpu().numpy().min() >= 0 and np.array_equal(idx_plain.cpu().numpy()[P:], np.full(q - P, -1))
+    for big, shape in [fg1, fp1, fg2, fp2] + frames + more:
+        assert _frame_untouched(big, shape)
+    for G, piv, rank in ((G1, piv1, rank1), (G2, piv2, rank2)):
+        assert rank == q and np.array_equal(piv.cpu().numpy(), pivt)
+        assert np.max(np.abs(G.cpu().numpy() - Gt)) <= 1e-10 * mf.SIGMA2
+    assert np.array_equal(piv2.cpu().numpy(), piv1.cpu().numpy()) and np.array_equal(G2.cpu().numpy(), G1.cpu().numpy())
+
+
 # ---- 5. conjugate gradients ------------------------------------------------------------------------------------------------------------------
 _DEV = {}
 
