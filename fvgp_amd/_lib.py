@@ -42,10 +42,13 @@ SYMBOLS = [
     "fvgp_hip_loglik_hess", "fvgp_hip_loglik_hess_workspace_bytes",
     "fvgp_hip_kmatvec", "fvgp_hip_kmatvec_workspace_bytes", "fvgp_hip_pchol", "fvgp_hip_pchol_workspace_bytes",
     "fvgp_hip_precond_factor", "fvgp_hip_precond_workspace_bytes", "fvgp_hip_pcg", "fvgp_hip_pcg_workspace_bytes",
+    "fvgp_hip_kgrad_form", "fvgp_hip_kgrad_form_workspace_bytes", "fvgp_hip_precond_probes", "fvgp_hip_precond_apply",
+    "fvgp_hip_precond_apply_workspace_bytes", "fvgp_hip_pcg_lanczos", "fvgp_hip_pcg_lanczos_workspace_bytes",
 ]
 MATVEC_CHUNK = 4096       # FVGP_MATVEC_CHUNK: rows of x2 per chunk sum of fvgp_hip_kmatvec
 PCG_MAX_RHS = 16          # FVGP_PCG_MAX_RHS
 PCG_MAX_RANK = 1024       # FVGP_PCG_MAX_RANK
+LANCZOS_MAX_STEPS = 256   # FVGP_LANCZOS_MAX_STEPS: most CG coefficients per column fvgp_hip_pcg_lanczos records
 BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
 
 
@@ -213,6 +216,21 @@ def pcg_workspace_bytes(n, q):
     return int(lib().fvgp_hip_pcg_workspace_bytes(int(n), int(q)))
 
 
+def pcg_lanczos_workspace_bytes(n, q, lanczos_steps):
+    """bytes of the caller-owned workspace of Handle.pcg_lanczos (fvgp_hip_pcg_lanczos_workspace_bytes); -1 for bad arguments"""
+    return int(lib().fvgp_hip_pcg_lanczos_workspace_bytes(int(n), int(q), int(lanczos_steps)))
+
+
+def kgrad_form_workspace_bytes(n1, n2):
+    """bytes of the caller-owned workspace of Handle.kgrad_form (fvgp_hip_kgrad_form_workspace_bytes); -1 for n1 or n2 < 1"""
+    return int(lib().fvgp_hip_kgrad_form_workspace_bytes(int(n1), int(n2)))
+
+
+def precond_apply_workspace_bytes(n, q):
+    """bytes of the caller-owned workspace of Handle.precond_apply (fvgp_hip_precond_apply_workspace_bytes); -1 for n < 1 or q < 0"""
+    return int(lib().fvgp_hip_precond_apply_workspace_bytes(int(n), int(q)))
+
+
 def loglik_hess_workspace_bytes(n, d):
     """bytes of the caller-owned scratch of Handle.loglik_hess (fvgp_hip_loglik_hess_workspace_bytes); -1 for n < 1 or d outside 1..16"""
     return int(lib().fvgp_hip_loglik_hess_workspace_bytes(int(n), int(d)))
@@ -307,8 +325,16 @@ def lib():
     L.fvgp_hip_pcg.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_i,
                                c_d, c_i, c_i, c_i, c_p, c_l, P_i, P_d, P_i]
     L.fvgp_hip_pcg_workspace_bytes.argtypes = [c_l, c_i]
+    L.fvgp_hip_pcg_lanczos.argtypes = L.fvgp_hip_pcg.argtypes + [c_i, P_d, P_d, P_i, P_d]
+    L.fvgp_hip_pcg_lanczos_workspace_bytes.argtypes = [c_l, c_i, c_i]
+    L.fvgp_hip_kgrad_form.argtypes = [c_p, c_i, c_p, c_l, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_i, c_p, c_l, P_d]
+    L.fvgp_hip_kgrad_form_workspace_bytes.argtypes = [c_l, c_l]
+    L.fvgp_hip_precond_probes.argtypes = [c_p, c_u, c_u, c_l, c_p, c_l, c_i, c_l, c_p, c_p, c_l, c_i]
+    L.fvgp_hip_precond_apply.argtypes = [c_p, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_l]
+    L.fvgp_hip_precond_apply_workspace_bytes.argtypes = [c_l, c_i]
     for name in ("fvgp_hip_kmatvec_workspace_bytes", "fvgp_hip_pchol_workspace_bytes", "fvgp_hip_precond_workspace_bytes",
-                 "fvgp_hip_pcg_workspace_bytes"):
+                 "fvgp_hip_pcg_workspace_bytes", "fvgp_hip_pcg_lanczos_workspace_bytes", "fvgp_hip_kgrad_form_workspace_bytes",
+                 "fvgp_hip_precond_apply_workspace_bytes"):
         getattr(L, name).restype = c_l
     L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
     L.fvgp_hip_loglik_hess.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, P_d, P_d]
@@ -346,7 +372,8 @@ def lib():
                      "fvgp_hip_posterior_batch_workspace_bytes", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_loo_workspace_bytes",
                      "fvgp_hip_mvn_sample_workspace_bytes", "fvgp_hip_select_workspace_bytes", "fvgp_hip_loglik_hess_workspace_bytes",
                      "fvgp_hip_kmatvec_workspace_bytes", "fvgp_hip_pchol_workspace_bytes", "fvgp_hip_precond_workspace_bytes",
-                     "fvgp_hip_pcg_workspace_bytes"):
+                     "fvgp_hip_pcg_workspace_bytes", "fvgp_hip_pcg_lanczos_workspace_bytes", "fvgp_hip_kgrad_form_workspace_bytes",
+                     "fvgp_hip_precond_apply_workspace_bytes"):
             getattr(L, s).restype = c_i
     _lib = L
     return L
@@ -876,6 +903,67 @@ class Handle(DistCalls):
                                   relres.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                   status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))), "fvgp_hip_pcg")
         return iters[:s], relres[:s], status[:s]
+
+    def pcg_lanczos(self, kernel_id, x, theta, vdiag, B, X, lanczos_steps, G=None, q=0, C=None, s=None, warm=False, tol=1e-10,
+                    max_iter=1000, check_every=8, max_restarts=3, work=None):
+        """fvgp_hip_pcg_lanczos: Handle.pcg that also records the coefficients of every column's first recurrence.  Returns (iters,
+        relres, status, alpha (s, L), beta (s, L), steps (s), rho0 (s)); with lanczos_steps == 0 the last four are empty."""
+        t, tp, nt = _theta(theta)
+        n, d = x.shape
+        s = int(B.shape[1] if s is None else s)
+        q = 0 if G is None else int(q)
+        L = int(lanczos_steps)
+        if work is None:
+            work = self.empty(max(1, pcg_lanczos_workspace_bytes(n, q, L)) // 8)
+        iters = np.zeros(max(s, 1), dtype=np.int32)
+        status = np.zeros(max(s, 1), dtype=np.int32)
+        relres = np.zeros(max(s, 1), dtype=np.float64)
+        alpha, beta = np.zeros((max(s, 1), max(L, 1))), np.zeros((max(s, 1), max(L, 1)))
+        steps, rho0 = np.zeros(max(s, 1), dtype=np.int32), np.zeros(max(s, 1))
+        P_d, P_i = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+        _check(lib().fvgp_hip_pcg_lanczos(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(vdiag), _ptr(G),
+                                          0 if G is None else G.stride(0), q, _ptr(C), 0 if C is None else C.stride(0),
+                                          _ptr(B), B.stride(0), s, _ptr(X), X.stride(0), int(bool(warm)), float(tol), int(max_iter),
+                                          int(check_every), int(max_restarts), _ptr(work), work.numel() * 8,
+                                          iters.ctypes.data_as(P_i), relres.ctypes.data_as(P_d), status.ctypes.data_as(P_i), L,
+                                          alpha.ctypes.data_as(P_d), beta.ctypes.data_as(P_d), steps.ctypes.data_as(P_i),
+                                          rho0.ctypes.data_as(P_d)), "fvgp_hip_pcg_lanczos")
+        if L == 0:
+            return iters[:s], relres[:s], status[:s], alpha[:s, :0], beta[:s, :0], steps[:0], rho0[:0]
+        return iters[:s], relres[:s], status[:s], alpha[:s], beta[:s], steps[:s], rho0[:s]
+
+    def kgrad_form(self, kernel_id, x1, U, x2, W, theta, s=None, work=None):
+        """fvgp_hip_kgrad_form: the vector of sum_{c < s} U[:, c]^T (dK(x1, x2) / dtheta_j) W[:, c] over the kernel's own hyperparameters
+        (sigma^2, then the length scales), K never formed.  U (n1, >= s), W (n2, >= s) device tensors; synchronous."""
+        t, tp, nt = _theta(theta)
+        s = int(U.shape[1] if s is None else s)
+        n1, n2 = x1.shape[0], x2.shape[0]
+        if work is None:
+            work = self.empty(max(1, kgrad_form_workspace_bytes(n1, n2)) // 8)
+        out = np.zeros(max(nt, 1), dtype=np.float64)
+        _check(lib().fvgp_hip_kgrad_form(self._h, int(kernel_id), _ptr(x1), n1, _ptr(x2), n2, x1.shape[1], tp, nt, _ptr(U), U.stride(0),
+                                         _ptr(W), W.stride(0), s, _ptr(work), work.numel() * 8,
+                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "fvgp_hip_kgrad_form")
+        return out
+
+    def precond_probes(self, Z, vdiag, G=None, q=0, seed=0, stream=0, col0=0):
+        """fvgp_hip_precond_probes: Z[:, c] = D^1/2 z(seed, 2 stream, :, col0 + c) + G^T z(seed, 2 stream + 1, :, col0 + c) over the
+        columns of the device tensor Z (n, s <= PCG_MAX_RHS): probes with covariance G^T G + D.  Asynchronous."""
+        q = 0 if G is None else int(q)
+        _check(lib().fvgp_hip_precond_probes(self._h, int(seed), int(stream), int(col0), _ptr(G), 0 if G is None else G.stride(0), q,
+                                             Z.shape[0], _ptr(vdiag), _ptr(Z), Z.stride(0), Z.shape[1]), "fvgp_hip_precond_probes")
+
+    def precond_apply(self, R, W, vdiag, G=None, q=0, C=None, s=None, work=None):
+        """fvgp_hip_precond_apply: W[:, :s] = (G^T G + D)^-1 R[:, :s] with the factor C of precond_factor (G None: D^-1 R), by the
+        solver's own launches.  Asynchronous."""
+        n = R.shape[0]
+        s = int(R.shape[1] if s is None else s)
+        q = 0 if G is None else int(q)
+        if work is None:
+            work = self.empty(max(1, precond_apply_workspace_bytes(n, q)) // 8)
+        _check(lib().fvgp_hip_precond_apply(self._h, _ptr(G), 0 if G is None else G.stride(0), q, _ptr(C),
+                                            0 if C is None else C.stride(0), n, _ptr(vdiag), _ptr(R), R.stride(0), s, _ptr(W),
+                                            W.stride(0), _ptr(work), work.numel() * 8), "fvgp_hip_precond_apply")
 
     def potrs_cols(self, L, n, B, nrhs):
         """Handle.potrs for nrhs % 128 == 0 columns whose bits do not depend on nrhs (fvgp_hip_potrs_cols)"""

@@ -4,21 +4,29 @@ K is never stored.  Every product with K evaluates the kernel on the fly (fvgp_h
 pivoted Cholesky G^T G + V of K + V applied through Woodbury (fvgp_hip_pchol, fvgp_hip_precond_factor), the recurrences' scalars live
 on the device (fvgp_hip_pcg).  Memory is O(N (q + 16)): N = 10^6 at rank 256 holds about 2 GB of preconditioner.
 
-The intended use: train on a subset with the dense fvgp_amd.GP, then predict with everything --
+Two uses: train on a subset with the dense fvgp_amd.GP, then predict with everything --
 
     gp = GP(x_sub, y_sub, ...); gp.train(...)
     big = gp.matrix_free(x_all, y_all, noise_all)
     big.posterior_mean(x_pred); big.posterior_covariance(x_pred, variance_only=True)
 
+-- or learn from everything with the stochastic likelihood: big.train_stochastic(bounds).
+
 With alpha = (K + V)^-1 (y - m) and Z = (K + V)^-1 k(X, x*):   m(x*) = m + k(x*, X) alpha,   v = k** - sum k o Z,
-S = k** - k(x*, X) Z.  The likelihood, its gradient and train() need a stochastic log-determinant and trace on this path; they
-are not here (use the dense GP).
+S = k** - k(x*, X) Z.
+
+The likelihood on this path is an ESTIMATE with a reported standard error.  With A = K + V, M = G^T G + V the preconditioner and probes
+z_c ~ N(0, M) (fvgp_hip_precond_probes):   log det A = log det M + mean_c rho_0 e_1^T log(T_c) e_1, T_c the Lanczos tridiagonal the
+preconditioned CG on A u_c = z_c records (fvgp_hip_pcg_lanczos), log det M in closed form;   tr(A^-1 dK_j) = mean_c u_c^T dK_j (M^-1 z_c)
+(fvgp_hip_precond_apply, fvgp_hip_kgrad_form).  Only the kernel's own hyperparameters get a gradient: the noise is numbers here.  The
+exact Hessian stays with the dense GP.
 """
 import warnings
 
 import numpy as np
 
 from . import _lib
+from . import gp_training as _training
 from . import kernels as _kernels
 from .device import default_handle
 from .gp_lin_alg import NonPositiveDefiniteError
@@ -34,7 +42,10 @@ class MatrixFreeGP:
 
     x_data (N, D), y_data (N,), hyperparameters in the named kernel's layout, noise_variances (N,) or None (the rule and the warning
     of GP: (0.01 mean|y|)^2).  The prior mean is mean(y).  args: "precond_rank" (128; 0 = Jacobi), "tol" (1e-10, relative
-    residual), "max_iter" (1000), "check_every" (8), "max_restarts" (3), "pchol_tol" (1e-12), "z_max_bytes"."""
+    residual), "max_iter" (1000), "check_every" (8), "max_restarts" (3), "pchol_tol" (1e-12), "z_max_bytes"; for the stochastic
+    likelihood "probe_tol" (1e-6: the relative residual of the probe solves, a default and not a measured optimum; alpha keeps "tol"),
+    "lanczos_steps" (64: CG coefficients recorded per probe) and "stochastic_likelihood" (False; True lets the fvgp.GP method names
+    log_likelihood, neg_log_likelihood, neg_log_likelihood_gradient and train return the estimates)."""
 
     def __init__(self, x_data, y_data, hyperparameters, noise_variances=None, kernel_function="matern32_ard", args=None):
         native = _kernels.resolve(kernel_function) if not callable(kernel_function) or isinstance(kernel_function, _kernels.NativeKernel) \
@@ -53,6 +64,11 @@ class MatrixFreeGP:
         self.max_iter = int(self.args.get("max_iter", 1000))
         self.check_every = int(self.args.get("check_every", 8))
         self.max_restarts = int(self.args.get("max_restarts", 3))
+        self.probe_tol = float(self.args.get("probe_tol", 1e-6))
+        self.lanczos_steps = int(self.args.get("lanczos_steps", 64))
+        assert 1 <= self.lanczos_steps <= _lib.LANCZOS_MAX_STEPS, f"lanczos_steps must lie in 1 .. {_lib.LANCZOS_MAX_STEPS}"
+        self.stochastic_likelihood = bool(self.args.get("stochastic_likelihood", False))
+        self._scratch = {}
         self._H = default_handle()
         if noise_variances is None:
             warnings.warn("No noise function or measurement noise provided. "
@@ -81,7 +97,8 @@ class MatrixFreeGP:
         self._m = float(np.mean(self.y_data))
         self._x_dev, self._V_dev = H.to_device(self.x_data), H.to_device(self._V)
         self._ym_dev = H.to_device((self.y_data - self._m)[:, None])
-        self._G = self._C = self._work = None
+        self._G = self._C = None
+        self._scratch = {}
         self._rank = 0
 
     @property
@@ -98,46 +115,68 @@ class MatrixFreeGP:
         self._alpha = self._alpha_info = None
         self._G = self._C = None
 
+    def _build_preconditioner(self, hps):
+        """(G, q, C) at hps: the pivoted Cholesky of K and the factor of I + G V^-1 G^T; nothing is kept"""
+        if self.precond_rank == 0:
+            return None, 0, None
+        H, n = self._H, self.point_number
+        q = min(self.precond_rank, n)
+        G = H.empty(q, n)
+        piv = H.torch.empty(q, dtype=H.torch.int64, device=G.device)
+        rank = H.pchol(self._native.kernel_id, self._x_dev, hps, q, G, piv, tol=float(self.args.get("pchol_tol", 1e-12)))
+        qp = _lib.pad128(q)
+        C = H.empty(qp, qp)
+        info = H.precond_factor(G, q, n, self._V_dev, C)
+        if info != 0:
+            raise NonPositiveDefiniteError(f"the preconditioner's {q} x {q} system I + G V^-1 G^T is not positive definite "
+                                           f"(pivot {info}): the noise variances or the hyperparameters are no numbers")
+        self._rank = rank
+        return G, q, C
+
     def _preconditioner(self):
-        """(G, q, C) at the current hyperparameters, built once: the pivoted Cholesky of K and the factor of I + G V^-1 G^T"""
+        """(G, q, C) at the current hyperparameters, built once"""
         if self.precond_rank == 0:
             return None, 0, None
         if self._G is None:
-            H, n = self._H, self.point_number
-            q = min(self.precond_rank, n)
-            G = H.empty(q, n)
-            piv = H.torch.empty(q, dtype=H.torch.int64, device=G.device)
-            self._rank = H.pchol(self._native.kernel_id, self._x_dev, self._hps, q, G, piv, tol=float(self.args.get("pchol_tol", 1e-12)))
-            qp = _lib.pad128(q)
-            C = H.empty(qp, qp)
-            info = H.precond_factor(G, q, n, self._V_dev, C)
-            if info != 0:
-                raise NonPositiveDefiniteError(f"the preconditioner's {q} x {q} system I + G V^-1 G^T is not positive definite "
-                                               f"(pivot {info}): the noise variances or the hyperparameters are no numbers")
-            self._G, self._C, self._q = G, C, q
+            self._G, self._q, self._C = self._build_preconditioner(self._hps)
         return self._G, self._q, self._C
 
-    def _pcg(self, B, X, s, warm=False):
-        H, n = self._H, self.point_number
-        G, q, C = self._preconditioner()
-        need = _lib.pcg_workspace_bytes(n, q) // 8
-        if self._work is None or self._work.numel() < need:
-            self._work = H.empty(max(1, need))
-        return H.pcg(self._native.kernel_id, self._x_dev, self._hps, self._V_dev, B, X, G=G, q=q, C=C, s=s, warm=warm, tol=self.tol,
-                     max_iter=self.max_iter, check_every=self.check_every, max_restarts=self.max_restarts, work=self._work)
+    def _buffer(self, name, doubles):
+        """a flat device buffer of at least `doubles` doubles, kept under `name` and regrown when too small"""
+        buf = self._scratch.get(name)
+        if buf is None or buf.numel() < doubles:
+            buf = self._scratch[name] = self._H.empty(max(1, int(doubles)))
+        return buf
 
-    def _solve_device(self, B, X, warm=False):
+    def _pcg(self, B, X, s, warm=False, at=None, tol=None, lanczos_steps=0):
+        """one solver call of s <= 16 columns; at = (hps, G, q, C) solves at other hyperparameters than the object's; lanczos_steps > 0
+        also returns the records (alpha, beta, steps, rho0)"""
+        H, n = self._H, self.point_number
+        hps, G, q, C = at if at is not None else (self._hps,) + self._preconditioner()
+        tol = self.tol if tol is None else tol
+        kw = dict(G=G, q=q, C=C, s=s, warm=warm, tol=tol, max_iter=self.max_iter, check_every=self.check_every,
+                  max_restarts=self.max_restarts)
+        if lanczos_steps:
+            work = self._buffer("pcg", _lib.pcg_lanczos_workspace_bytes(n, q, lanczos_steps) // 8)
+            return H.pcg_lanczos(self._native.kernel_id, self._x_dev, hps, self._V_dev, B, X, lanczos_steps, work=work, **kw)
+        work = self._buffer("pcg", _lib.pcg_workspace_bytes(n, q) // 8)
+        return H.pcg(self._native.kernel_id, self._x_dev, hps, self._V_dev, B, X, work=work, **kw)
+
+    def _breakdown(self):
+        return NonPositiveDefiniteError(
+            f"conjugate gradients broke down on K + V ({self.point_number} points, smallest noise variance "
+            f"{float(np.min(self._V)):.3e}): p^T (K + V) p or r^T M^-1 r was not positive -- the matrix is not positive "
+            "definite in double precision; add noise or rethink the hyperparameters")
+
+    def _solve_device(self, B, X, warm=False, at=None):
         """X (n, c) <- (K + V)^-1 B (n, c) on the device in blocks of 16 columns; (iterations, residuals, converged) per column"""
         c = B.shape[1]
         its, res, ok = np.zeros(c, dtype=np.int64), np.zeros(c), np.zeros(c, dtype=bool)
         for a in range(0, c, _lib.PCG_MAX_RHS):
             b = min(a + _lib.PCG_MAX_RHS, c)
-            it, rr, st = self._pcg(B[:, a:b], X[:, a:b], b - a, warm=warm)
+            it, rr, st = self._pcg(B[:, a:b], X[:, a:b], b - a, warm=warm, at=at)
             if np.any(st == 2):
-                raise NonPositiveDefiniteError(
-                    f"conjugate gradients broke down on K + V ({self.point_number} points, smallest noise variance "
-                    f"{float(np.min(self._V)):.3e}): p^T (K + V) p or r^T M^-1 r was not positive -- the matrix is not positive "
-                    "definite in double precision; add noise or rethink the hyperparameters")
+                raise self._breakdown()
             its[a:b], res[a:b], ok[a:b] = it, rr, st == 0
         if not np.all(ok):
             warnings.warn(f"conjugate gradients did not converge: relative residual {float(np.max(res)):.3e} reached, "
@@ -254,25 +293,160 @@ class MatrixFreeGP:
             # (the prior mean moved with the data: the old alpha still nearly solves the old rows, which is all a start needs)
             self._ensure_alpha(warm_from=old)
 
-    # ---- what this path does not have ------------------------------------------------------------------------------------
+    # ---- the stochastic likelihood -----------------------------------------------------------------------------------
+    @staticmethod
+    def _quadrature(alpha, beta, rho0):
+        """rho_0 e_1^T log(T) e_1 with T the Lanczos tridiagonal of the recorded CG coefficients: T[k, k] = 1 / alpha_k +
+        beta_{k-1} / alpha_{k-1}, T[k, k+1] = sqrt(beta_k) / alpha_k; numpy.linalg.eigh on the dense T (a few hundred rows at most)"""
+        m = len(alpha)
+        if m == 0:
+            return 0.0
+        T = np.zeros((m, m))
+        for k in range(m):
+            T[k, k] = 1.0 / alpha[k] + (beta[k - 1] / alpha[k - 1] if k else 0.0)
+            if k + 1 < m:
+                T[k, k + 1] = T[k + 1, k] = np.sqrt(beta[k]) / alpha[k]
+        lam, Q = np.linalg.eigh(T)
+        return float(rho0 * np.sum(Q[0] ** 2 * np.log(lam)))
+
+    def log_likelihood_estimate(self, hyperparameters=None, n_probes=16, seed=0, gradient=False):
+        """The log marginal likelihood at the object's hyperparameters, or at `hyperparameters` with a preconditioner of its own and
+        the object's state untouched.  A dict: "log_likelihood" and its "std_error" (over the probes), "logdet" = log det(K + V) with
+        "logdet_std_error", "logdet_preconditioner", "data_fit" = 1/2 (y - m)^T alpha, "per_probe" (n_probes,): every probe's
+        rho_0 e_1^T log(T) e_1, "iterations" and "lanczos_steps" per probe, "alpha_iterations", "converged"; with gradient=True also
+        "neg_gradient" over the kernel's own hyperparameters, d(-log L)/dtheta_j = -1/2 alpha^T dK_j alpha + 1/2 tr((K + V)^-1 dK_j), and
+        "neg_gradient_std_error": half the spread of the trace over groups of 4 probes (one fvgp_hip_kgrad_form call each).  The same
+        (hyperparameters, n_probes, seed) returns the same bits: the probes are a pure function of the seed."""
+        H, n, kid = self._H, self.point_number, self._native.kernel_id
+        n_probes = int(n_probes)
+        assert n_probes >= 1, "n_probes must be at least 1"
+        if hyperparameters is None:
+            hps = self._hps
+            G, q, C = self._preconditioner()
+            at = None
+            alpha = self._ensure_alpha()
+            alpha_info = self._alpha_info
+        else:
+            hps = np.array(hyperparameters, dtype=np.float64)
+            assert hps.shape == self._hps.shape, "wrong number of hyperparameters for this kernel"
+            G, q, C = self._build_preconditioner(hps)
+            at = (hps, G, q, C)
+            alpha = H.zeros(n, 1)
+            its, res, ok = self._solve_device(self._ym_dev, alpha, at=at)
+            alpha_info = {"iterations": int(its[0]), "relative_residual": float(res[0]), "converged": bool(ok[0])}
+        fit = 0.5 * H.dot(self._ym_dev, alpha, n)
+        ldm = float(np.sum(np.log(self._V))) + (H.logdet(C, q) if q else 0.0)
+
+        S = _lib.PCG_MAX_RHS
+        Z, U, W = H.empty(n, S), H.empty(n, S), H.empty(n, S)
+        awork = self._buffer("apply", _lib.precond_apply_workspace_bytes(n, q) // 8)
+        gwork = self._buffer("form", _lib.kgrad_form_workspace_bytes(n, n) // 8)
+        quad, its, steps, res = np.zeros(n_probes), np.zeros(n_probes, dtype=np.int64), np.zeros(n_probes, dtype=np.int64), np.zeros(n_probes)
+        ok = np.zeros(n_probes, dtype=bool)
+        n_own = self._native.n_hyperparameters(self.index_set_dim)
+        sums, means = np.zeros(n_own), []
+        for c0 in range(0, n_probes, S):
+            s = min(S, n_probes - c0)
+            H.precond_probes(Z[:, :s], self._V_dev, G=G, q=q, seed=seed, stream=0, col0=c0)
+            it, rr, st, al, be, stp, rho0 = self._pcg(Z, U, s, at=at, tol=self.probe_tol, lanczos_steps=self.lanczos_steps)
+            if np.any(st == 2):
+                raise self._breakdown()
+            for c in range(s):
+                m = int(stp[c])
+                quad[c0 + c] = self._quadrature(al[c, :m], be[c, :max(m - 1, 0)], rho0[c])
+            its[c0:c0 + s], steps[c0:c0 + s], res[c0:c0 + s], ok[c0:c0 + s] = it, stp, rr, st == 0
+            if gradient:
+                H.precond_apply(Z, W, self._V_dev, G=G, q=q, C=C, s=s, work=awork)
+                for g0 in range(0, s, 4):
+                    g1 = min(g0 + 4, s)
+                    f = H.kgrad_form(kid, self._x_dev, U[:, g0:g1], self._x_dev, W[:, g0:g1], hps, work=gwork)[:n_own]
+                    sums += f
+                    means.append(f / (g1 - g0))
+        if not np.all(ok):
+            warnings.warn(f"conjugate gradients did not converge on the probes: relative residual {float(np.max(res)):.3e} reached, "
+                          f"probe_tol = {self.probe_tol:.1e} asked, after at most {int(np.max(its))} iterations (args: max_iter, "
+                          "precond_rank, probe_tol)", stacklevel=2)
+        logdet = ldm + float(np.mean(quad))
+        ld_se = float(np.std(quad, ddof=1) / np.sqrt(n_probes)) if n_probes > 1 else float("nan")
+        out = {"log_likelihood": -(fit + 0.5 * logdet + 0.5 * n * np.log(2.0 * np.pi)), "std_error": 0.5 * ld_se, "logdet": logdet,
+               "logdet_std_error": ld_se, "logdet_preconditioner": ldm, "data_fit": fit, "per_probe": quad, "iterations": its,
+               "lanczos_steps": steps, "alpha_iterations": alpha_info["iterations"],
+               "converged": bool(np.all(ok) and alpha_info["converged"])}
+        if gradient:
+            a_term = H.kgrad_form(kid, self._x_dev, alpha, self._x_dev, alpha, hps, s=1, work=gwork)[:n_own]
+            trace = sums / n_probes
+            tr_se = np.std(np.array(means), axis=0, ddof=1) / np.sqrt(len(means)) if len(means) > 1 else np.full(n_own, np.nan)
+            out.update({"neg_gradient": -0.5 * a_term + 0.5 * trace, "neg_gradient_std_error": 0.5 * tr_se, "trace": trace,
+                        "trace_std_error": tr_se})
+        return out
+
+    def stochastic_log_likelihood(self, hyperparameters=None, n_probes=16, seed=0):
+        return self.log_likelihood_estimate(hyperparameters, n_probes, seed)["log_likelihood"]
+
+    def stochastic_neg_log_likelihood(self, hyperparameters=None, n_probes=16, seed=0):
+        return -self.log_likelihood_estimate(hyperparameters, n_probes, seed)["log_likelihood"]
+
+    def stochastic_neg_log_likelihood_gradient(self, hyperparameters=None, n_probes=16, seed=0):
+        return self.log_likelihood_estimate(hyperparameters, n_probes, seed, gradient=True)["neg_gradient"]
+
+    def stochastic_neg_log_likelihood_and_gradient(self, hyperparameters=None, n_probes=16, seed=0):
+        e = self.log_likelihood_estimate(hyperparameters, n_probes, seed, gradient=True)
+        return -e["log_likelihood"], e["neg_gradient"]
+
+    def train_stochastic(self, hyperparameter_bounds, init_hyperparameters=None, max_iter=200, lr=1e-2, tolerance=1e-4, n_probes=16, seed=0,
+                         callback=None):
+        """Adam (gp_training.adam_optimize) on the estimated negative log-likelihood with the SAME seed at every step -- common random
+        numbers: the objective is then a deterministic function of theta -- every iterate clipped into hyperparameter_bounds (H, 2).
+        Ends with set_hyperparameters(theta) and returns (theta, history)."""
+        bounds = np.asarray(hyperparameter_bounds, dtype=np.float64)
+        assert bounds.ndim == 2 and bounds.shape == (len(self._hps), 2), "wrong bounds format"
+        theta0 = np.array(self._hps if init_hyperparameters is None else init_hyperparameters, dtype=np.float64)
+        if np.any(theta0 < bounds[:, 0]) or np.any(theta0 > bounds[:, 1]):
+            raise Exception("Starting positions outside of optimization bounds.", theta0, bounds)
+        last = {}
+
+        def evaluate(theta):
+            key = theta.tobytes()
+            if last.get("key") != key:
+                last["key"], last["value"] = key, self.stochastic_neg_log_likelihood_and_gradient(theta, n_probes, seed)
+            return last["value"]
+
+        theta, history = _training.adam_optimize(lambda t: evaluate(t)[0], lambda t: evaluate(t)[1], theta0, lr=lr, max_iter=max_iter,
+                                                 tol=tolerance, callback=callback,
+                                                 project=lambda t: np.clip(t, bounds[:, 0], bounds[:, 1]))
+        self.set_hyperparameters(theta)
+        return theta, history
+
+    # ---- the fvgp.GP method names ----------------------------------------------------------------------------------------------
     def _dense_only(self, what):
-        raise NotImplementedError(f"{what} needs log det(K + V) or traces with (K + V)^-1, which the matrix-free path does not have yet "
-                                  "(a stochastic log-determinant and trace are the follow-up): " + _DENSE)
+        raise NotImplementedError(f"{what} needs log det(K + V) or traces with (K + V)^-1; on the matrix-free path these are stochastic "
+                                  "estimates (log_likelihood_estimate, stochastic_neg_log_likelihood_gradient, train_stochastic), and "
+                                  "this method name returns them only with args={'stochastic_likelihood': True}.  Exact values: "
+                                  + _DENSE)
 
     def log_likelihood(self, hyperparameters=None):
-        self._dense_only("log_likelihood")
+        if not self.stochastic_likelihood:
+            self._dense_only("log_likelihood")
+        return self.stochastic_log_likelihood(hyperparameters)
 
     def neg_log_likelihood(self, hyperparameters=None):
-        self._dense_only("neg_log_likelihood")
+        if not self.stochastic_likelihood:
+            self._dense_only("neg_log_likelihood")
+        return self.stochastic_neg_log_likelihood(hyperparameters)
 
     def neg_log_likelihood_gradient(self, hyperparameters=None, component=0):
-        self._dense_only("neg_log_likelihood_gradient")
+        if not self.stochastic_likelihood:
+            self._dense_only("neg_log_likelihood_gradient")
+        return self.stochastic_neg_log_likelihood_gradient(hyperparameters)
 
     def neg_log_likelihood_hessian(self, hyperparameters=None):
-        self._dense_only("neg_log_likelihood_hessian")
+        raise NotImplementedError("neg_log_likelihood_hessian: there is no stochastic Hessian on the matrix-free path: " + _DENSE)
 
-    def train(self, *a, **kw):
-        self._dense_only("train")
+    def train(self, hyperparameter_bounds=None, init_hyperparameters=None, **kw):
+        if not self.stochastic_likelihood:
+            self._dense_only("train")
+        assert hyperparameter_bounds is not None, "train needs hyperparameter_bounds"
+        return self.train_stochastic(hyperparameter_bounds, init_hyperparameters, **kw)[0]
 
 
 class MatrixFreeMixin:

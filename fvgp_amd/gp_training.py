@@ -190,9 +190,10 @@ def run_mcmc(log_likelihood, bounds, x0, n_updates=10000, info=False, rng=None, 
 
 
 def adam_optimize(nlml, grad_nlml, theta0, lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8, max_iter=1000, tol=1e-6,
-                  callback=None, early_stop=None):
+                  callback=None, early_stop=None, project=None):
     """Adam on the negative log marginal likelihood (GPtraining.adam_optimize, gp_training.py:576-667): one value and
     one gradient evaluation per step, bias-corrected moments, stop when the parameter update is shorter than `tol`.
+    project: None, or a map applied to every new iterate (MatrixFreeGP.train_stochastic clips into the bounds with it).
     Returns (theta, history) with history = {"theta", "nlml", "grad_norm"} as the reference keeps it."""
     theta = np.array(theta0, dtype=np.float64)
     m = np.zeros(theta.size)
@@ -206,6 +207,8 @@ def adam_optimize(nlml, grad_nlml, theta0, lr=1e-2, beta1=0.9, beta2=0.999, eps=
         m_hat = m / (1.0 - beta1 ** t)
         v_hat = v / (1.0 - beta2 ** t)
         theta_new = theta - lr * m_hat / (np.sqrt(v_hat) + eps)
+        if project is not None:
+            theta_new = project(theta_new)
         history["theta"].append(theta.copy())
         history["nlml"].append(fval)
         history["grad_norm"].append(np.linalg.norm(g))

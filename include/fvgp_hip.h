@@ -54,6 +54,7 @@ enum fvgp_uplo { FVGP_FULL = 0, FVGP_LOWER = 1 };
 #define FVGP_MATVEC_CHUNK 4096   /* rows of x2 per chunk sum of fvgp_hip_kmatvec (part of its bit contract) */
 #define FVGP_PCG_MAX_RHS 16      /* right-hand sides per call of fvgp_hip_pcg */
 #define FVGP_PCG_MAX_RANK 1024   /* largest rank of the pivoted-Cholesky preconditioner */
+#define FVGP_LANCZOS_MAX_STEPS 256   /* most CG coefficients per column fvgp_hip_pcg_lanczos records */
 #define FVGP_MAX_RHS_VEC 8  /* potrs switches from the GEMV path to the GEMM path above this */
 #define FVGP_CHAIN_MAX_BLOCKS 32   /* widest panel (in 128-column blocks) the resident panel kernel takes; wider ones use the launch-per-step chain */
 #define FVGP_BATCH_MAX_DIM 4096    /* largest per-problem square the batched evaluation takes (32 block columns) */
@@ -689,6 +690,77 @@ int fvgp_hip_pcg(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int 
 /* four (n, 16) vectors, the rank's partial sums (ceil(n / 4096) q 16 doubles), the dot products' partials and, while the product would
  * split by itself, its per-chunk sums; -1 for n < 1 or q < 0 */
 int64_t fvgp_hip_pcg_workspace_bytes(int64_t n, int q);
+
+/* ---- the stochastic log-likelihood on the matrix-free path (csrc/matrix_free.hip) --------------------------
+ * log det(K + D) by preconditioned stochastic Lanczos quadrature and tr((K + D)^-1 dK/dtheta_j) by Hutchinson probes drawn from the
+ * preconditioner M = G^T G + D: probes (precond_probes), M^-1 outside the solver (precond_apply), the solver with its coefficients
+ * recorded (pcg_lanczos), and the bilinear form u^T (dK/dtheta_j) w without dK (kgrad_form).
+ *
+ * fvgp_hip_kgrad_form: out_host[j] = sum_{c < s} U[:, c]^T (dK(x1, x2; theta) / dtheta_j) W[:, c], j < the kernel's own hyperparameter count
+ * (sigma^2 first, then one length scale or d of them).  x1 (n1, d), U (n1, ldu >= s), x2 (n2, d), W (n2, ldw >= s), 1 <= s <=
+ * FVGP_PCG_MAX_RHS: device, row-major, fp64.  Noise never enters.  One pass over the n1 x n2 kernel entries per column group: per entry
+ * one exp (and one rsq for the Matern kinds), t = sum_c U[i][c] W[k][c], and one fused multiply-add per hyperparameter.  Synchronous.
+ * BIT CONTRACT: the result is a function of the arguments' VALUES alone -- the same bits on every run, for every "matvec_split" and
+ * whatever `work` held before.  The order: the columns go in groups of 16, 8, 4 or 1 as in fvgp_hip_kmatvec, t is a chain of fused
+ * multiply-adds over the group's columns in ascending order starting from 0 (so a zero column changes nothing); per row i of x1 the rows of
+ * x2 are summed exactly as fvgp_hip_kmatvec sums them (chunks of FVGP_MATVEC_CHUNK, slices of 256, four waves, even and odd rows apart,
+ * chunk sums added to 0 in ascending order); the length-scale sums are multiplied by 1 / l once per row; the 64 rows of a block are added
+ * by a halving tree (lane i += lane i + 32, 16, .. 1), the blocks to 0 in ascending order, and the groups in ascending order.  The split
+ * into column groups is part of the value: s columns in one call and the same columns in several calls added on the host differ in the
+ * last bits.
+ * work: device, 8-byte aligned, fvgp_hip_kgrad_form_workspace_bytes(n1, n2) bytes at least.
+ * Errors (argument numbers, nothing is launched): -1 h, -2 unknown kernel_id, -3 x1, -4 n1 < 1, -5 x2, -6 n2 < 1, -7 d outside
+ * 1 .. FVGP_MAX_DIM, -8 theta_host, -9 too few hyperparameters, -10 U, -11 ldu < s, -12 W, -13 ldw < s, -14 s outside
+ * 1 .. FVGP_PCG_MAX_RHS, -15 work NULL or misaligned, -16 work_bytes too small, -17 out_host. */
+int fvgp_hip_kgrad_form(fvgp_handle *h, int kernel_id, const double *x1, int64_t n1, const double *x2, int64_t n2, int d,
+                        const double *theta_host, int ntheta, const double *U, int64_t ldu, const double *W, int64_t ldw, int s,
+                        double *work, int64_t work_bytes, double *out_host);
+/* (1 + ceil(n1 / 64)) (1 + FVGP_MAX_DIM) doubles for the result and the blocks' sums, and, while the product would deal chunk ranges
+ * over workgroups by itself (fewer than 512 blocks of 64 rows and at least two chunks), ceil(n2 / FVGP_MATVEC_CHUNK) n1 (1 + FVGP_MAX_DIM)
+ * more for the parked chunk sums; with less than that second part the chunks are walked by one workgroup per 64 rows (the same bits);
+ * -1 for n1 or n2 < 1 */
+int64_t fvgp_hip_kgrad_form_workspace_bytes(int64_t n1, int64_t n2);
+/* Probes with covariance M = G^T G + D: Z[i][c] = sqrt(v_i) z(seed, 2 stream, i, col0 + c) + sum_t G[t][i] z(seed, 2 stream + 1, t, col0 + c),
+ * z the function of fvgp_hip_normal_fill; the first product first, then fused multiply-adds over t in ascending order.  G (q, ldg >= n)
+ * or NULL / q == 0 (then Z = D^1/2 z), vdiag (n), Z (n, ldz >= s), 1 <= s <= FVGP_PCG_MAX_RHS: device.  Z is written inside its n x s
+ * view only.  Column c is a function of (seed, stream, col0 + c, G, v) alone: a longer call extends a shorter one bit for bit, and col0
+ * shifts columns.  Asynchronous.
+ * Errors: -1 h, -3 stream (2 stream + 1 must fit 64 bits), -4 col0 negative or col0 + s past 2^32, -6 ldg < n with q > 0, -7 q outside
+ * 0 .. FVGP_PCG_MAX_RANK, -8 n < 1 or past 2^32, -9 vdiag, -10 Z, -11 ldz < s, -12 s outside 1 .. FVGP_PCG_MAX_RHS. */
+int fvgp_hip_precond_probes(fvgp_handle *h, uint64_t seed, uint64_t stream, int64_t col0, const double *G_or_null, int64_t ldg, int q,
+                            int64_t n, const double *vdiag, double *Z, int64_t ldz, int s);
+/* W = M^-1 R for an (n, s <= FVGP_PCG_MAX_RHS) block, M = G^T G + D with the factor C of fvgp_hip_precond_factor (q == 0 or G NULL:
+ * W = D^-1 R): the launches fvgp_hip_pcg applies its preconditioner with, so a column of W has the bits the solver's first z has for the
+ * same right-hand side, whatever else is in the call.  R (n, ldr >= s), W (n, ldw >= s): device; W is written inside its n x s view only
+ * and may be R.  work: device, 16-byte aligned, fvgp_hip_precond_apply_workspace_bytes(n, q) bytes.  Asynchronous (the host waits only
+ * where fvgp_hip_potrs would).
+ * Errors: -1 h, -3 ldg < n with q > 0, -4 q outside 0 .. FVGP_PCG_MAX_RANK, -5 C NULL or misaligned with q > 0, -6 ldc, -7 n < 1,
+ * -8 vdiag, -9 R, -10 ldr < s, -11 s outside 1 .. FVGP_PCG_MAX_RHS, -12 W, -13 ldw < s, -14 work NULL or misaligned, -15 work_bytes too
+ * small. */
+int fvgp_hip_precond_apply(fvgp_handle *h, const double *G_or_null, int64_t ldg, int q, const double *C, int64_t ldc, int64_t n,
+                           const double *vdiag, const double *R, int64_t ldr, int s, double *W, int64_t ldw,
+                           double *work, int64_t work_bytes);
+/* two (n, 16) vectors, the rank's partial sums and the padded (q, 16) block; -1 for n < 1 or q < 0 */
+int64_t fvgp_hip_precond_apply_workspace_bytes(int64_t n, int q);
+/* fvgp_hip_pcg that also records the coefficients of every column's FIRST recurrence (before any restart), the Lanczos tridiagonal of
+ * M^-1/2 (K + D) M^-1/2 started from M^-1/2 b:  T[k][k] = 1 / alpha_k + beta_{k-1} / alpha_{k-1} (the second term absent at k = 0),
+ * T[k][k+1] = sqrt(beta_k) / alpha_k.  One driver serves both entries: X, iters_host, relres_host and status_host have the bits of
+ * fvgp_hip_pcg for every lanczos_steps, and the solve goes on to its tolerance whatever is recorded.
+ *   lanczos_steps = L in 0 .. FVGP_LANCZOS_MAX_STEPS;  alpha_host, beta_host (s, L) row-major, steps_host (s), rho0_host (s): host.
+ *   rho0_host[c] = r_0^T M^-1 r_0 (b^T M^-1 b for a cold start; 0 for a column that never started);  alpha_host[c][k], k < steps_host[c] =
+ *   min(L, iterations of the first recurrence);  beta_host[c][k] for every k < L the recurrence went on after (at least steps_host[c] - 1 of
+ *   them); entries not recorded are 0.  With L == 0 nothing is recorded and the four pointers may be NULL.
+ * A column's records do not depend on what else is in the call.  work: fvgp_hip_pcg_lanczos_workspace_bytes(n, q, L) bytes.
+ * Errors: those of fvgp_hip_pcg (-25 against this entry's workspace size), -29 lanczos_steps outside 0 .. FVGP_LANCZOS_MAX_STEPS, and
+ * with L > 0: -30 alpha_host, -31 beta_host, -32 steps_host, -33 rho0_host. */
+int fvgp_hip_pcg_lanczos(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta_host, int ntheta,
+                         const double *vdiag, const double *G_or_null, int64_t ldg, int q, const double *C, int64_t ldc,
+                         const double *B, int64_t ldb, int s, double *X, int64_t ldx, int warm,
+                         double tol, int max_iter, int check_every, int max_restarts,
+                         double *work, int64_t work_bytes, int *iters_host, double *relres_host, int *status_host,
+                         int lanczos_steps, double *alpha_host, double *beta_host, int *steps_host, double *rho0_host);
+/* the solver's workspace and, behind it, 16 (2 L + 3) doubles of records; -1 for n < 1, q < 0 or L outside 0 .. FVGP_LANCZOS_MAX_STEPS */
+int64_t fvgp_hip_pcg_lanczos_workspace_bytes(int64_t n, int q, int lanczos_steps);
 
 /* ---- building blocks exported for the parity tests --------------------------------------
  * C (M,N) = alpha * opA * opB + beta * C on fp64 MFMA.  M, N multiples of 128, K of 16.
