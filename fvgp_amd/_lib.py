@@ -44,11 +44,14 @@ SYMBOLS = [
     "fvgp_hip_precond_factor", "fvgp_hip_precond_workspace_bytes", "fvgp_hip_pcg", "fvgp_hip_pcg_workspace_bytes",
     "fvgp_hip_kgrad_form", "fvgp_hip_kgrad_form_workspace_bytes", "fvgp_hip_precond_probes", "fvgp_hip_precond_apply",
     "fvgp_hip_precond_apply_workspace_bytes", "fvgp_hip_pcg_lanczos", "fvgp_hip_pcg_lanczos_workspace_bytes",
+    "fvgp_hip_chol_update", "fvgp_hip_chol_delete", "fvgp_hip_chol_update_workspace_bytes",
 ]
 MATVEC_CHUNK = 4096       # FVGP_MATVEC_CHUNK: rows of x2 per chunk sum of fvgp_hip_kmatvec
 PCG_MAX_RHS = 16          # FVGP_PCG_MAX_RHS
 PCG_MAX_RANK = 1024       # FVGP_PCG_MAX_RANK
 LANCZOS_MAX_STEPS = 256   # FVGP_LANCZOS_MAX_STEPS: most CG coefficients per column fvgp_hip_pcg_lanczos records
+CHOL_UPDATE_MAX_RANK = 16 # FVGP_CHOL_UPDATE_MAX_RANK: columns of W per pass of fvgp_hip_chol_update
+CHOL_UPDATE_TABLE_BYTES = 128 * CHOL_UPDATE_MAX_RANK * 2 * 8   # FVGP_CHOL_UPDATE_TABLE_BYTES: all of the workspace the update itself uses
 BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
 
 
@@ -231,6 +234,11 @@ def precond_apply_workspace_bytes(n, q):
     return int(lib().fvgp_hip_precond_apply_workspace_bytes(int(n), int(q)))
 
 
+def chol_update_workspace_bytes(n, k):
+    """bytes of the caller-owned workspace of Handle.chol_update / chol_delete (fvgp_hip_chol_update_workspace_bytes); -1 for n or k < 1"""
+    return int(lib().fvgp_hip_chol_update_workspace_bytes(int(n), int(k)))
+
+
 def loglik_hess_workspace_bytes(n, d):
     """bytes of the caller-owned scratch of Handle.loglik_hess (fvgp_hip_loglik_hess_workspace_bytes); -1 for n < 1 or d outside 1..16"""
     return int(lib().fvgp_hip_loglik_hess_workspace_bytes(int(n), int(d)))
@@ -336,6 +344,10 @@ def lib():
                  "fvgp_hip_pcg_workspace_bytes", "fvgp_hip_pcg_lanczos_workspace_bytes", "fvgp_hip_kgrad_form_workspace_bytes",
                  "fvgp_hip_precond_apply_workspace_bytes"):
         getattr(L, name).restype = c_l
+    L.fvgp_hip_chol_update.argtypes = [c_p, c_p, c_l, c_l, c_p, c_l, c_l, c_l, c_p, c_l]
+    L.fvgp_hip_chol_delete.argtypes = [c_p, c_p, c_l, c_l, ctypes.POINTER(c_l), c_l, c_p, c_l]
+    L.fvgp_hip_chol_update_workspace_bytes.argtypes = [c_l, c_l]
+    L.fvgp_hip_chol_update_workspace_bytes.restype = c_l
     L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
     L.fvgp_hip_loglik_hess.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, P_d, P_d]
     L.fvgp_hip_loglik_hess_workspace_bytes.argtypes = [c_l, c_i]
@@ -373,7 +385,7 @@ def lib():
                      "fvgp_hip_mvn_sample_workspace_bytes", "fvgp_hip_select_workspace_bytes", "fvgp_hip_loglik_hess_workspace_bytes",
                      "fvgp_hip_kmatvec_workspace_bytes", "fvgp_hip_pchol_workspace_bytes", "fvgp_hip_precond_workspace_bytes",
                      "fvgp_hip_pcg_workspace_bytes", "fvgp_hip_pcg_lanczos_workspace_bytes", "fvgp_hip_kgrad_form_workspace_bytes",
-                     "fvgp_hip_precond_apply_workspace_bytes"):
+                     "fvgp_hip_precond_apply_workspace_bytes", "fvgp_hip_chol_update_workspace_bytes"):
             getattr(L, s).restype = c_i
     _lib = L
     return L
@@ -968,6 +980,24 @@ class Handle(DistCalls):
     def potrs_cols(self, L, n, B, nrhs):
         """Handle.potrs for nrhs % 128 == 0 columns whose bits do not depend on nrhs (fvgp_hip_potrs_cols)"""
         _check(lib().fvgp_hip_potrs_cols(self._h, _ptr(L), n, L.stride(0), _ptr(B), nrhs, B.stride(0)), "fvgp_hip_potrs_cols")
+
+    def chol_update(self, L, n, W, k=None, row0=0, work=None):
+        """fvgp_hip_chol_update: L <- chol(L L^T + W[:, :k] W[:, :k]^T) in place on the n leading rows; W (n, >= k) device, destroyed, its
+        rows < row0 zero.  Asynchronous; call invalidate_factor() before the next solve with L."""
+        k = int(W.shape[1] if k is None else k)
+        if work is None:
+            work = self.empty(CHOL_UPDATE_TABLE_BYTES // 8)
+        _check(lib().fvgp_hip_chol_update(self._h, _ptr(L), int(n), L.stride(0), _ptr(W), k, W.stride(0), int(row0), _ptr(work),
+                                          work.numel() * 8), "fvgp_hip_chol_update")
+
+    def chol_delete(self, L, n, idx, work=None):
+        """fvgp_hip_chol_delete: the factor of the points that remain when the strictly increasing indices `idx` (host) leave, in the same
+        buffer and as potrf leaves a factor of n - len(idx) points.  Asynchronous; call invalidate_factor() before the next solve."""
+        idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).ravel())
+        if work is None:
+            work = self.empty(max(1, chol_update_workspace_bytes(n, len(idx))) // 8)
+        _check(lib().fvgp_hip_chol_delete(self._h, _ptr(L), int(n), L.stride(0), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(idx),
+                                          _ptr(work), work.numel() * 8), "fvgp_hip_chol_delete")
 
     def posterior_prepare(self, L, n):
         """enqueue the inverted diagonal blocks the posterior's sweep substitutes with (fvgp_hip_posterior_prepare)"""

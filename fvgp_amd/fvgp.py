@@ -68,3 +68,29 @@ class fvGP(GP):
                                          else np.vstack([self.fvgp_noise_variances, noise_variances_new]))
         else:
             self.fvgp_x_data, self.fvgp_y_data, self.fvgp_noise_variances = x_new, y_new, noise_variances_new
+
+    def remove_data(self, indices):
+        """Take the positions `indices` (rows of fvgp_x_data: an integer array or a boolean mask) out of the multi-task GP: every
+        non-NaN task row of those positions leaves the task-major index set (GP.remove_data), and fvgp_x_data, fvgp_y_data and
+        fvgp_noise_variances lose the rows.  Returns GP.remove_data's dictionary with "removed" / "kept" as positions and the index-set
+        rows that left as "removed_rows"."""
+        from .gp_update import removal_indices
+        V = len(self.fvgp_x_data)
+        pos = removal_indices(indices, V)
+        gone = np.zeros(V, dtype=bool)
+        gone[pos] = True
+        if gone.all():
+            raise ValueError("remove_data: at least one position must remain")
+        observed = ~np.isnan(np.asarray(self.fvgp_y_data, dtype=np.float64).T.reshape(-1))      # task-major, as transform_index_set
+        rows = np.flatnonzero(np.tile(gone, self.output_num)[observed])
+        x_out, isd = self.x_out, self.input_set_dim
+        try:
+            res = super().remove_data(rows)
+        finally:
+            self.x_out, self.input_set_dim = x_out, isd
+        if len(pos):
+            self.fvgp_x_data = self.fvgp_x_data[~gone]
+            self.fvgp_y_data = self.fvgp_y_data[~gone]
+            if self.fvgp_noise_variances is not None:
+                self.fvgp_noise_variances = self.fvgp_noise_variances[~gone]
+        return {"removed": pos, "kept": np.flatnonzero(~gone), "route": res["route"], "removed_rows": res["removed"]}

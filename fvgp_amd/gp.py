@@ -31,6 +31,7 @@ from .gp_lin_alg import NonPositiveDefiniteError, _non_pd_message
 from .gp_loo import LOOMixin
 from .gp_matrix_free import MatrixFreeMixin
 from .gp_sampling import SamplingMixin
+from .gp_update import UpdateMixin
 from .gp_validation import ValidationMixin
 
 # device-memory budget of the B squares one batched evaluation factors at once (GP.log_likelihood_batch; args["batch_max_bytes"]
@@ -83,7 +84,7 @@ def _mixture_moments(m, v, w):
     return mean, within + between, within, between
 
 
-class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin, HessianMixin, MatrixFreeMixin):
+class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin, HessianMixin, MatrixFreeMixin, UpdateMixin):
     def __init__(
         self,
         x_data,

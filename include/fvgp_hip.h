@@ -762,6 +762,40 @@ int fvgp_hip_pcg_lanczos(fvgp_handle *h, int kernel_id, const double *x, int64_t
 /* the solver's workspace and, behind it, 16 (2 L + 3) doubles of records; -1 for n < 1, q < 0 or L outside 0 .. FVGP_LANCZOS_MAX_STEPS */
 int64_t fvgp_hip_pcg_lanczos_workspace_bytes(int64_t n, int q, int lanczos_steps);
 
+/* ---- rank-k update of a resident factor, removal of data points (csrc/chol_update.hip) ---------------
+ * The other half of the bordering append (gp_lin_alg.py:1310-1477 only ever grows a factor): with S the kept and R the removed indices
+ * of a factor L of K+V,  KV[S,S] = L[S,S] L[S,S]^T + L[S,R] L[S,R]^T,  so the factor of the kept points is a POSITIVE rank-|R| update
+ * of the compacted triangle -- orthogonal transforms only, no kernel evaluation, nothing that can lose positive definiteness.
+ *
+ * fvgp_hip_chol_update: L <- chol(L L^T + W W^T) in place.  L: the factor (padded_dim(n) rows, ldl) as fvgp_hip_potrf leaves it;
+ *   W: device (n, ldw >= k) row-major, DESTROYED.  Rows < row0 of W are promised to be zero (0 <= row0 <= n): block columns left of
+ *   row0 are not touched.  The strict upper triangle of L is never read or written, the padding rows are left as they were.  k above
+ *   FVGP_CHOL_UPDATE_MAX_RANK runs as successive passes of at most that many columns of W, each an exact update.  Per pass and
+ *   128-column block: one workgroup rotates the diagonal block and writes the block's Givens coefficients, then one launch applies them
+ *   to every row below, each element of L read once and written once.  Plain stream-ordered launches, no atomics.
+ *   BIT INVARIANT: the same call returns the same bits, and row i of the result depends only on rows <= i of L and W -- the leading m
+ *   rows of an update of n rows equal, bit for bit, the update of the leading m x m problem alone (whatever ldl is).
+ *   ws: device, 16-byte aligned; the update itself uses its first FVGP_CHOL_UPDATE_TABLE_BYTES only.  Asynchronous on the handle's stream.
+ *   Returns, before anything is launched, minus the position of a bad argument: -1 h, -2 L NULL or misaligned, -3 n < 1, -4 ldl odd or
+ *   below padded_dim(n), -5 W, -6 k < 1, -7 ldw < k, -8 row0 outside 0 .. n, -9 ws NULL or misaligned, -10 ws_bytes too small.
+ * fvgp_hip_chol_delete: the factor of the n - k points that remain when the points idx_host[0 .. k) (HOST, strictly increasing, every
+ *   index in [0, n), 1 <= k < n) leave: W = L[S,R] is gathered, L[S,S] moved up-left inside the same buffer (through a strip of at most
+ *   1024 rows in ws, strip after strip in stream order: there is no second n x n buffer), rows n - k .. padded_dim(n) - 1 become
+ *   identity padding again, and the update runs -- one enqueue.  On return the buffer holds the factor of the kept points, in their
+ *   original order, exactly as fvgp_hip_potrf leaves a factor of n - k points.  Removing only trailing points costs no update at all.
+ *   THE CALLER MUST INVALIDATE THE HANDLE'S CACHED DIAGONAL-BLOCK INVERSES (fvgp_hip_invalidate_factor) after either call and before
+ *   the next potrs / trsm / potri / posterior on that buffer: the factor changed under the same (pointer, n, ld) key or a stale one.
+ *   Returns -1 h, -2 .. -4 as above, -5 idx_host NULL, not strictly increasing or out of range, -6 k outside 1 .. n - 1, -7 ws NULL or
+ *   misaligned, -8 ws_bytes below fvgp_hip_chol_update_workspace_bytes(n, k); nothing is written then.
+ * fvgp_hip_chol_update_workspace_bytes(n, k): what both calls accept -- the coefficient table, the index lists (n + k words), W
+ *   (n k doubles) and the strip (min(1024, n, 2^25 / n) rows of n doubles): O(n (k + 1024)), never n x n;  -1 for n < 1 or k < 1. */
+#define FVGP_CHOL_UPDATE_MAX_RANK 16
+#define FVGP_CHOL_UPDATE_TABLE_BYTES (128 * FVGP_CHOL_UPDATE_MAX_RANK * 2 * 8)
+int fvgp_hip_chol_update(fvgp_handle *h, double *L, int64_t n, int64_t ldl, double *W, int64_t k, int64_t ldw, int64_t row0,
+                         double *ws, int64_t ws_bytes);
+int fvgp_hip_chol_delete(fvgp_handle *h, double *L, int64_t n, int64_t ldl, const int64_t *idx_host, int64_t k, double *ws, int64_t ws_bytes);
+int64_t fvgp_hip_chol_update_workspace_bytes(int64_t n, int64_t k);
+
 /* ---- building blocks exported for the parity tests --------------------------------------
  * C (M,N) = alpha * opA * opB + beta * C on fp64 MFMA.  M, N multiples of 128, K of 16.
  *   a_kmajor == 0: A stored (M,K) row-major;  != 0: A stored (K,M) row-major (A^T product)
