@@ -117,7 +117,7 @@ struct fvgp_handle {
     // 8000 5.7 -> 5.1, 20000 46.9 -> 45.6, 50000 620 -> 595 on the same box); `lookahead_min` = 4608 restores the old schedule
     int64_t lookahead_min = (int64_t)1 << 40;
     int64_t select_block = 65536;     // measurement only: candidates per launch pair of the batch selection (select.hip; a multiple of 64, at most 65536)
-    int64_t matvec_split = 0;         // fvgp_hip_kmatvec's gridDim.y: 0 by the shape, 1 never split, k chunk ranges dealt over k workgroups (same bits; matrix_free.hip)
+    int64_t matvec_split = 0;         // fvgp_hip_kmatvec's gridDim.y: 0 by the shape, 1 never split, k chunk ranges dealt over k workgroups (same bits; matvec.hip)
     int posterior_halves = 1;         // posterior covariance at >= 512 points: two halves of the points side by side on two streams (tri_solve.hip)
     int64_t outer_block_small = 512, small_threshold = 12288;   // panel width for the last `small_threshold` rows (potrf_driver)
     int lookahead = 1;
@@ -161,6 +161,10 @@ int fvgp_hip_fail(hipError_t e, const char *what, int line);
         hipError_t e__ = (call);                                      \
         if (e__ != hipSuccess) return fvgp_hip_fail(e__, #call, __LINE__); \
     } while (0)
+
+// a kernel launch on `stream` (no dynamic LDS) and the check that it was accepted
+#define HIPLAUNCH(kernel, grid, block, stream, ...) \
+    do { hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__); HIPCHK(hipGetLastError()); } while (0)
 
 static inline int64_t pad128(int64_t n) { return (n + TILE - 1) / TILE * TILE; }
 static inline int64_t even_up(int64_t v) { return (v + 1) & ~(int64_t)1; }      // workspace pieces in doubles: every offset stays 16-byte aligned
@@ -233,6 +237,21 @@ struct KmatDesc {
 };
 int launch_kmat(fvgp_handle *h, const KmatDesc &k);
 int kmat_desc_from_theta(int kernel_id, int d, const double *theta, int ntheta, KmatDesc *out);
+int launch_kmatvec(fvgp_handle *h, const KmatDesc &k, const double *B, int64_t ldb, int s, double *Y, int64_t ldy, double *work,
+                   int64_t work_doubles, bool fallback);      // matvec.hip: Y[:, 0 .. s) = K(x1, x2) B + diag(vdiag) B
+// the split plan's arithmetic: matvec.hip deals the chunks by it (mv_plan), matrix_free.hip sizes the solver's parking room by it
+constexpr int MATVEC_CHUNK = FVGP_MATVEC_CHUNK;      // x2 rows per chunk sum (a multiple of the slice: matvec.hip)
+constexpr int MV_MAXS = 16;                          // widest column group
+static inline int64_t mv_chunks(int64_t n2) { return (n2 + MATVEC_CHUNK - 1) / MATVEC_CHUNK; }
+static inline int mv_group(int left) { return left >= MV_MAXS ? MV_MAXS : left > 4 ? 8 : left > 1 ? 4 : 1; }      // the narrowest group that holds what is left
+static inline int64_t mv_split_doubles(int64_t n1, int64_t n2, int s) { return mv_chunks(n2) * n1 * mv_group(s); }
+// the launches' gridDim.y when nothing is forced: chunk ranges are dealt out only while the 64-row blocks alone cannot fill the chip
+static inline int64_t mv_auto_split(int64_t n1, int64_t n2) {
+    const int64_t bx = (n1 + 63) / 64, nch = mv_chunks(n2);
+    if (nch < 2 || bx >= 512) return 1;
+    const int64_t gy = (1024 + bx - 1) / bx;
+    return gy < nch ? gy : nch;
+}
 
 struct GradDesc {
     KmatDesc k;               // x1 == x2 == x, n1 == n2 == n

@@ -1,24 +1,12 @@
-// Solves with K(theta) + V without the matrix: the product with a block of vectors, the pivoted-Cholesky preconditioner and
-// the preconditioned conjugate gradients whose scalars stay on the device.
+// Solves with K(theta) + V without the matrix: the pivoted-Cholesky preconditioner and the preconditioned conjugate gradients
+// whose scalars stay on the device.  The product with a block of vectors, launch_kmatvec, and the gradient's bilinear form are matvec.hip.
 //
-// fvgp_hip_kmatvec   Y = K(x1, x2) B + diag(v) B.  select_cross_kernel widened: lanes along 64 output rows, the x2 rows and S entries of
-//     B per row staged in LDS (slice_sum.h, broadcast reads), S accumulator pairs per lane filled by the same row loop (slice_rows),
-//     so one exp (plus the rsq of the Matern kinds) serves S columns.  The order of every sum is a function of n2 alone: x2 is cut
-//     into chunks of MATVEC_CHUNK rows, a chunk into slices of SLICE_ROWS; wave w sums rows [64 w, 64 w + 64) of every slice of the
-//     chunk into an even-row and an odd-row accumulator; the chunk's sum is (((e0 + o0) + (e1 + o1)) + (e2 + o2)) + (e3 + o3); chunk
-//     sums are added to 0 in ascending order; v_i B_ic enters as the last fused multiply-add.  A workgroup that walks all chunks
-//     (gridDim.y == 1) and a launch that deals chunk ranges over gridDim.y, parks the per-chunk sums and adds them in a second pass
-//     give the same bits.
 // fvgp_hip_pchol     greedy pivoted Cholesky of K(x, x), q steps enqueued at once: selection's greedy pivot core (pivot.h) with the
 //     data as their own candidates, no conditioning (pivot_downdate_kernel<KIND, CROSS = false>) and no noise.
 // fvgp_hip_precond_factor   C = I + G D^-1 G^T in fixed-order chunks of PF_CHUNK points, factored by potrf_driver.
 // fvgp_hip_pcg       s <= 16 independent recurrences that share the matvec; every vector kernel reads the per-column state
 //     (active, alpha, beta) from device memory, the host reads the status words every `check_every` iterations.
 // The stochastic log-likelihood:
-// fvgp_hip_kgrad_form       sum_c U[:, c]^T (dK / dtheta_j) W[:, c] for every j in ONE pass over the kernel entries: kmatvec_kernel's shape
-//     (lanes along 64 rows of x1, x2 rows and S entries of W per row staged in LDS, U[i, 0 .. S) in registers), per entry one
-//     radial_grad, S fused multiply-adds for t = sum_c U[i][c] W[k][c] and one per hyperparameter.  Sums as in the product; the rows of
-//     a block by a halving tree, the blocks in ascending order by one small kernel: no atomics.
 // fvgp_hip_precond_probes   Z = D^1/2 eps + G^T eta from the normals of normal.h;  fvgp_hip_precond_apply   the solver's M^-1 on its own;
 // fvgp_hip_pcg_lanczos      the solver with the coefficients of every column's first recurrence recorded (one driver serves both entries).
 #include "radial.h"
@@ -31,286 +19,10 @@
 
 namespace {
 
-constexpr int MATVEC_CHUNK = FVGP_MATVEC_CHUNK;      // x2 rows per chunk sum (a multiple of SLICE_ROWS)
-constexpr int MV_MAXS = 16;                          // widest column group
 constexpr int PCG_LD = FVGP_PCG_MAX_RHS;             // row stride of the solver's own vectors
 constexpr int PF_CHUNK = 8192;                       // points per partial Gram sum of precond_factor
 constexpr int PT_CHUNK = 4096;                       // points per partial of G (D^-1 R)
 constexpr int DOT_ROWS = 1024;                       // rows per partial of the dot products
-static_assert(MATVEC_CHUNK % SLICE_ROWS == 0, "a chunk is whole slices");
-
-// ---------------------------------------------------------------------------------------------------------------- the product
-struct MvArgs {
-    const double *x1, *x2, *B, *v;
-    double *Y, *part;                        // part: nullptr (the workgroup adds its chunks itself) or (nchunks, n1, S) chunk sums
-    long n1, n2, ldb, ldy, nchunks, cpy;     // cpy: chunks per blockIdx.y
-    int d, c0, sc;                           // columns [c0, c0 + sc) of B and Y, sc <= S
-    double sig;
-    double il[FVGP_MAX_DIM];
-};
-
-template <int KIND, int D, int S>   // D == 0: runtime dimension (<= FVGP_MAX_DIM)
-__global__ __launch_bounds__(256) void kmatvec_kernel(MvArgs a) {
-    constexpr int DD = D ? D : FVGP_MAX_DIM;
-    __shared__ __attribute__((aligned(16))) double sm[SLICE_ROWS * (DD + S)];     // (>= 3 * 64 * S: the parked sums of waves 1 .. 3)
-    double *sx = sm, *sb = sm + SLICE_ROWS * DD;
-    const int d = D ? D : a.d;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long loc = (long)blockIdx.x * 64 + lane;
-    const long i = loc < a.n1 ? loc : a.n1 - 1;
-    double u[DD], il[DD];                                     // (il: a copy, so that the address of the kernel's arguments is never taken)
-#pragma unroll
-    for (int k = 0; k < DD; ++k) { u[k] = k < d ? a.x1[i * d + k] : 0.0; il[k] = a.il[k]; }
-    const long ch0 = (long)blockIdx.y * a.cpy, ch1 = ch0 + a.cpy < a.nchunks ? ch0 + a.cpy : a.nchunks;
-    double tot[S];
-#pragma unroll
-    for (int c = 0; c < S; ++c) tot[c] = 0.0;
-
-    for (long ch = ch0; ch < ch1; ++ch) {
-        double s0[S], s1[S];                                  // even and odd rows of this wave's share of the chunk
-#pragma unroll
-        for (int c = 0; c < S; ++c) { s0[c] = 0.0; s1[c] = 0.0; }
-        const long rbeg = ch * MATVEC_CHUNK, rend = rbeg + MATVEC_CHUNK < a.n2 ? rbeg + MATVEC_CHUNK : a.n2;
-        for (long row0 = rbeg; row0 < rend; row0 += SLICE_ROWS) {
-            __syncthreads();                                  // the last slice's rows (or the parked sums) have been read
-            slice_stage_cols<DD, S>(sx, sb, a.x2, a.B, a.ldb, a.c0, a.sc, a.n2, d, row0, tid);
-            __syncthreads();
-            const int r0 = wave * SLICE_WAVE_ROWS, rows = slice_wave_rows(a.n2, row0, wave);
-            slice_rows<KIND, DD, S>(sx, sb, r0, rows, d, u, il, a.sig, s0, s1);
-        }
-        __syncthreads();                                      // every wave is done with the staged rows
-        if (wave > 0) {
-#pragma unroll
-            for (int c = 0; c < S; ++c) slice_parked(sm, S, wave, lane)[c * 64] = s0[c] + s1[c];
-        }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int c = 0; c < S; ++c) {
-                double t = s0[c] + s1[c];
-#pragma unroll
-                for (int ww = 1; ww < 4; ++ww) t += slice_parked(sm, S, ww, lane)[c * 64];      // ((wave 0 + wave 1) + wave 2) + wave 3
-                if (a.part) { if (loc < a.n1) a.part[(ch * a.n1 + loc) * S + c] = t; }
-                else tot[c] += t;
-            }
-        }
-    }
-    if (a.part || wave != 0 || loc >= a.n1) return;
-#pragma unroll
-    for (int c = 0; c < S; ++c)
-        if (c < a.sc) a.Y[loc * a.ldy + a.c0 + c] = a.v ? fma(a.v[loc], a.B[loc * a.ldb + a.c0 + c], tot[c]) : tot[c];
-}
-
-// the second pass of a split launch: one thread per (row, column), the chunk sums added to 0 in ascending order
-__global__ __launch_bounds__(256) void kmatvec_reduce_kernel(MvArgs a, int S) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= a.n1 * a.sc) return;
-    const long loc = e / a.sc;
-    const int c = (int)(e - loc * a.sc);
-    double tot = 0.0;
-    for (long ch = 0; ch < a.nchunks; ++ch) tot += a.part[(ch * a.n1 + loc) * S + c];
-    a.Y[loc * a.ldy + a.c0 + c] = a.v ? fma(a.v[loc], a.B[loc * a.ldb + a.c0 + c], tot) : tot;
-}
-
-inline int64_t mv_chunks(int64_t n2) { return (n2 + MATVEC_CHUNK - 1) / MATVEC_CHUNK; }
-inline int mv_group(int left) { return left >= MV_MAXS ? MV_MAXS : left > 4 ? 8 : left > 1 ? 4 : 1; }      // the narrowest group that holds what is left
-inline int64_t mv_split_doubles(int64_t n1, int64_t n2, int s) { return mv_chunks(n2) * n1 * mv_group(s); }
-// the launches' gridDim.y when nothing is forced: chunk ranges are dealt out only while the 64-row blocks alone cannot fill the chip
-inline int64_t mv_auto_split(int64_t n1, int64_t n2) {
-    const int64_t bx = (n1 + 63) / 64, nch = mv_chunks(n2);
-    if (nch < 2 || bx >= 512) return 1;
-    const int64_t gy = (1024 + bx - 1) / bx;
-    return gy < nch ? gy : nch;
-}
-
-template <int KIND, int D, int S>
-void mv_launch(fvgp_handle *h, const MvArgs &a, dim3 grid) {
-    hipLaunchKernelGGL((kmatvec_kernel<KIND, D, S>), grid, dim3(256), 0, h->stream, a);
-}
-
-// Y[:, 0 .. s) = K B + diag(v) B.  k: x1, n1, x2, n2, d, kind, sig, invl, vdiag.  work_doubles < what a forced split needs: -1 unless
-// `fallback` (then the unsplit form, which has the same bits)
-int launch_kmatvec(fvgp_handle *h, const KmatDesc &k, const double *B, int64_t ldb, int s, double *Y, int64_t ldy, double *work,
-                   int64_t work_doubles, bool fallback) {
-    MvArgs a;
-    a.x1 = k.x1; a.x2 = k.x2; a.B = B; a.v = k.vdiag; a.Y = Y;
-    a.n1 = k.n1; a.n2 = k.n2; a.ldb = ldb; a.ldy = ldy; a.nchunks = mv_chunks(k.n2);
-    a.d = k.d; a.sig = k.sig;
-    for (int i = 0; i < FVGP_MAX_DIM; ++i) a.il[i] = k.invl[i];
-    int64_t gy = h->matvec_split == 0 ? mv_auto_split(k.n1, k.n2) : h->matvec_split;
-    if (gy > a.nchunks) gy = a.nchunks;
-    if (gy > 65535) gy = 65535;
-    const int64_t bx = (k.n1 + 63) / 64;
-    for (int c0 = 0; c0 < s;) {
-        const int left = s - c0;
-        const int S = mv_group(left);
-        a.c0 = c0; a.sc = left < S ? left : S;
-        bool split = gy > 1;
-        if (split && (!work || work_doubles < a.nchunks * k.n1 * S)) {
-            if (h->matvec_split > 1 && !fallback) { fvgp_set_error("kmatvec: work smaller than fvgp_hip_kmatvec_workspace_bytes(n1, n2, s)"); return -1; }
-            split = false;
-        }
-        a.part = split ? work : nullptr;
-        a.cpy = split ? (a.nchunks + gy - 1) / gy : a.nchunks;
-        const dim3 grid((unsigned)bx, split ? (unsigned)((a.nchunks + a.cpy - 1) / a.cpy) : 1u);
-        dispatch_kind_dim(k.kind, k.d, [&](auto KIND, auto D) {
-            constexpr int KK = decltype(KIND)::value, DV = decltype(D)::value;
-            switch (S) {
-                case 16: mv_launch<KK, DV, 16>(h, a, grid); break;
-                case 8: mv_launch<KK, DV, 8>(h, a, grid); break;
-                case 4: mv_launch<KK, DV, 4>(h, a, grid); break;
-                default: mv_launch<KK, DV, 1>(h, a, grid); break;
-            }
-        });
-        HIPCHK(hipGetLastError());
-        if (split) {
-            hipLaunchKernelGGL(kmatvec_reduce_kernel, dim3((unsigned)((k.n1 * a.sc + 255) / 256)), dim3(256), 0, h->stream, a, S);
-            HIPCHK(hipGetLastError());
-        }
-        c0 += a.sc;
-    }
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------ the gradient's bilinear form
-constexpr int KG_H = 1 + FVGP_MAX_DIM;               // stride of every per-hyperparameter sum (sigma^2, then the length scales)
-
-struct KgArgs {
-    const double *x1, *x2, *U, *W;
-    double *park, *bpart;                    // park: nullptr (the workgroup adds its chunks itself) or (nchunks, n1, KG_H) chunk sums; bpart (blocks, KG_H)
-    long n1, n2, ldu, ldw, nchunks, cpy;     // cpy: chunks per blockIdx.y
-    int d, c0, sc, iso;                      // columns [c0, c0 + sc) of U and W, sc <= S
-    double sig;
-    double il[FVGP_MAX_DIM];
-};
-
-// the lane's sums of one row of x1 (length scales already times 1 / l) added over the block's 64 lanes by the halving tree; lane 0 writes
-template <int DD>
-__device__ __forceinline__ void kg_block_sum(double (&tot)[DD + 1], int nh, int lane, double *out) {
-#pragma unroll
-    for (int hh = 0; hh < DD + 1; ++hh)
-        if (hh < nh) {
-            double w = tot[hh];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
-            if (lane == 0) out[hh] = w;
-        }
-}
-
-template <int KIND, int D, int S>   // D == 0: runtime dimension (<= FVGP_MAX_DIM)
-__global__ __launch_bounds__(256) void kgrad_form_kernel(KgArgs a) {
-    constexpr int DD = D ? D : FVGP_MAX_DIM;
-    constexpr int NH = DD + 1;                                                    // accumulators per chain: sigma^2 and DD length scales (iso: one)
-    __shared__ __attribute__((aligned(16))) double sm[SLICE_ROWS * (DD + S)];     // (>= 3 * 64 * NH: the parked sums of waves 1 .. 3)
-    double *sx = sm, *sw = sm + SLICE_ROWS * DD;
-    const int d = D ? D : a.d;
-    const int nh = a.iso ? 2 : d + 1;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long loc = (long)blockIdx.x * 64 + lane;
-    const long i = loc < a.n1 ? loc : a.n1 - 1;
-    double u[DD], il[DD], uc[S];
-#pragma unroll
-    for (int k = 0; k < DD; ++k) { u[k] = k < d ? a.x1[i * d + k] : 0.0; il[k] = a.il[k]; }
-#pragma unroll
-    for (int c = 0; c < S; ++c) uc[c] = (loc < a.n1 && c < a.sc) ? a.U[i * a.ldu + a.c0 + c] : 0.0;
-    const long ch0 = (long)blockIdx.y * a.cpy, ch1 = ch0 + a.cpy < a.nchunks ? ch0 + a.cpy : a.nchunks;
-    double tot[NH];
-#pragma unroll
-    for (int hh = 0; hh < NH; ++hh) tot[hh] = 0.0;
-
-    for (long ch = ch0; ch < ch1; ++ch) {
-        double g0[NH], g1[NH];                                // even and odd rows of this wave's share of the chunk
-#pragma unroll
-        for (int hh = 0; hh < NH; ++hh) { g0[hh] = 0.0; g1[hh] = 0.0; }
-        // one entry: row r of the staged slice into the chain g
-        auto entry = [&](const int r, double (&g)[NH]) {
-            const double *xr = sx + r * DD, *wr = sw + r * S;
-            double e2[DD], r2 = 0.0;
-#pragma unroll
-            for (int k = 0; k < DD; ++k) {
-                if (k < d) { const double e = (u[k] - xr[k]) * il[k]; e2[k] = e * e; r2 += e2[k]; }
-                else e2[k] = 0.0;
-            }
-            double phi, cf, t = 0.0;
-            radial_grad<KIND>(r2, a.sig, phi, cf);
-#pragma unroll
-            for (int c = 0; c < S; ++c) t = fma(uc[c], wr[c], t);
-            g[0] = fma(phi, t, g[0]);
-            const double wc = cf * t;
-            if (a.iso) g[1] = fma(wc, r2, g[1]);
-            else {
-#pragma unroll
-                for (int k = 0; k < DD; ++k) if (k < d) g[1 + k] = fma(wc, e2[k], g[1 + k]);
-            }
-        };
-        const long rbeg = ch * MATVEC_CHUNK, rend = rbeg + MATVEC_CHUNK < a.n2 ? rbeg + MATVEC_CHUNK : a.n2;
-        for (long row0 = rbeg; row0 < rend; row0 += SLICE_ROWS) {
-            __syncthreads();                                  // the last slice's rows (or the parked sums) have been read
-            slice_stage_cols<DD, S>(sx, sw, a.x2, a.W, a.ldw, a.c0, a.sc, a.n2, d, row0, tid);
-            __syncthreads();
-            const int r0 = wave * SLICE_WAVE_ROWS, rows = slice_wave_rows(a.n2, row0, wave);
-            int r = 0;
-            for (; r + 1 < rows; r += 2) { entry(r0 + r, g0); entry(r0 + r + 1, g1); }
-            if (r < rows) entry(r0 + r, g0);
-        }
-        __syncthreads();                                      // every wave is done with the staged rows
-        if (wave > 0) {
-#pragma unroll
-            for (int hh = 0; hh < NH; ++hh) if (hh < nh) slice_parked(sm, NH, wave, lane)[hh * 64] = g0[hh] + g1[hh];
-        }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int hh = 0; hh < NH; ++hh)
-                if (hh < nh) {
-                    double t = g0[hh] + g1[hh];
-#pragma unroll
-                    for (int ww = 1; ww < 4; ++ww) t += slice_parked(sm, NH, ww, lane)[hh * 64];      // ((wave 0 + wave 1) + wave 2) + wave 3
-                    if (a.park) { if (loc < a.n1) a.park[(ch * a.n1 + loc) * KG_H + hh] = t; }
-                    else tot[hh] += t;
-                }
-        }
-    }
-    if (a.park || wave != 0) return;
-    if (loc >= a.n1) {                                        // (a lane past n1 repeats the last row with U = 0: its sums count as 0 whatever they are)
-#pragma unroll
-        for (int hh = 0; hh < NH; ++hh) tot[hh] = 0.0;
-    }
-#pragma unroll
-    for (int hh = 1; hh < NH; ++hh) if (hh < nh) tot[hh] *= il[hh - 1];
-    kg_block_sum<DD>(tot, nh, lane, a.bpart + (long)blockIdx.x * KG_H);
-}
-
-// the second pass of a split launch: one wave per 64 rows, a lane adds its row's chunk sums to 0 in ascending order, then as above
-__global__ __launch_bounds__(64) void kgrad_rows_kernel(KgArgs a) {
-    const int lane = threadIdx.x, nh = a.iso ? 2 : a.d + 1;
-    const long loc = (long)blockIdx.x * 64 + lane;
-    double tot[KG_H];
-#pragma unroll
-    for (int hh = 0; hh < KG_H; ++hh) {
-        double t = 0.0;
-        if (hh < nh && loc < a.n1)
-            for (long ch = 0; ch < a.nchunks; ++ch) t += a.park[(ch * a.n1 + loc) * KG_H + hh];
-        tot[hh] = hh >= 1 && hh < nh ? t * a.il[hh - 1] : t;
-    }
-    kg_block_sum<FVGP_MAX_DIM>(tot, nh, lane, a.bpart + (long)blockIdx.x * KG_H);
-}
-
-// out[j] = (first ? 0 : out[j]) + the blocks' sums added to 0 in ascending order; one thread per hyperparameter
-__global__ __launch_bounds__(64) void kgrad_sum_kernel(const double *bpart, long nblocks, int nh, int first, double *out) {
-    const int hh = threadIdx.x;
-    if (hh >= nh) return;
-    double acc = 0.0;
-    for (long b = 0; b < nblocks; ++b) acc += bpart[b * KG_H + hh];
-    out[hh] = first ? acc : out[hh] + acc;
-}
-
-template <int KIND, int D, int S>
-void kg_launch(fvgp_handle *h, const KgArgs &a, dim3 grid) {
-    hipLaunchKernelGGL((kgrad_form_kernel<KIND, D, S>), grid, dim3(256), 0, h->stream, a);
-}
-
-inline int64_t kg_base_doubles(int64_t n1) { return (1 + (n1 + 63) / 64) * KG_H; }
 
 // ------------------------------------------------------------------------------------------------------ the probes
 struct ProbeArgs {
@@ -434,16 +146,23 @@ struct PcgVec {
     int s;
 };
 
-// the block's share of sum_i a_i b_i for every column: thread (g, c) adds rows g, g + 16, .. of the DOT_ROWS, then a tree over g
-__device__ __forceinline__ void dot_block(double acc, double *out, int tid, bool live) {
-    __shared__ double sh[256];
-    sh[tid] = acc;
+// sh[a][c] <- the sum over g of sh[a][16 g + c] for the NA arrays at once: a halving tree over g, 256 threads
+template <int NA>
+__device__ __forceinline__ void tree_over_g(double (&sh)[NA][256], int tid) {
     __syncthreads();
     for (int off = 128; off >= 16; off >>= 1) {
-        if (tid < off) sh[tid] += sh[tid + off];
+        if (tid < off)
+            for (int a = 0; a < NA; ++a) sh[a][tid] += sh[a][tid + off];
         __syncthreads();
     }
-    if (tid < 16 && live) out[(long)blockIdx.x * PCG_LD + tid] = sh[tid];
+}
+
+// the block's share of sum_i a_i b_i for every column: thread (g, c) adds rows g, g + 16, .. of the DOT_ROWS, then the tree over g
+__device__ __forceinline__ void dot_block(double acc, double *out, int tid, bool live) {
+    __shared__ double sh[1][256];
+    sh[0][tid] = acc;
+    tree_over_g(sh, tid);
+    if (tid < 16 && live) out[(long)blockIdx.x * PCG_LD + tid] = sh[0][tid];
 }
 
 // what = 0: R = B, part0 = b.b;  1: R = B - AP, part0 = b.b, part1 = r.r (warm start);  2: R = B - AP for frozen columns, part1 = r.r
@@ -521,11 +240,7 @@ __global__ __launch_bounds__(256) void pcg_scalar_kernel(PcgVec a, long nblk, in
     if (c < a.s)
         for (long b = g; b < nblk; b += 16) { s0 += a.part0[b * PCG_LD + c]; s1 += a.part1[b * PCG_LD + c]; }
     sh[0][tid] = s0; sh[1][tid] = s1;
-    __syncthreads();
-    for (int off = 128; off >= 16; off >>= 1) {
-        if (tid < off) { sh[0][tid] += sh[0][tid + off]; sh[1][tid] += sh[1][tid + off]; }
-        __syncthreads();
-    }
+    tree_over_g(sh, tid);
     if (tid >= a.s) return;
     PcgState &st = *a.st;
     const double v0 = sh[0][tid], v1 = sh[1][tid];
@@ -666,156 +381,159 @@ __global__ __launch_bounds__(256) void pcg_apply_kernel(const double *G, long ld
     }
 }
 
-struct PcgLayout { int64_t R, Z, P, AP, T, tpart, part0, part1, state, mv, total; int64_t nblk, tchunks, mv_doubles; };
+// the preconditioner's pieces of a workspace from offset o on: T (pad128(q) rows of PCG_LD whose padding stays zero), the chunks' partials
+// of G (D^-1 R), part0 (r.z by blocks of 256 points: >= the DOT_ROWS blocks of the solver's other partials)
+struct PrecondLayout { int64_t T, tpart, part0, end, qp, tchunks; };
+PrecondLayout precond_layout(int64_t n, int q, int64_t o) {
+    PrecondLayout l;
+    l.qp = q > 0 ? pad128(q) : 0;
+    l.tchunks = (n + PT_CHUNK - 1) / PT_CHUNK;
+    l.T = o; o += l.qp * PCG_LD;
+    l.tpart = o; o += l.tchunks * q * PCG_LD;
+    l.part0 = o; o += (n + 255) / 256 * PCG_LD;
+    l.end = o;
+    return l;
+}
+
+// before the first pcg_precond on a workspace: the padding of T is zeroed, a.part0 points at the layout's
+int precond_begin(fvgp_handle *h, double *work, const PrecondLayout &l, PcgVec &a) {
+    a.part0 = work + l.part0;
+    if (l.qp) HIPCHK(hipMemsetAsync(work + l.T, 0, (size_t)l.qp * PCG_LD * sizeof(double), h->stream));
+    return 0;
+}
+
+// Z = M^-1 R for the solver's own vectors, part0 = r.z: G (D^-1 R) in chunks, one potrs per column, the apply kernel
+int pcg_precond(fvgp_handle *h, const double *G, int64_t ldg, int q, const double *C, int64_t ldc, const PcgVec &a, double *work,
+                const PrecondLayout &l) {
+    double *T = work + l.T, *tpart = work + l.tpart;
+    if (q > 0) {
+        HIPLAUNCH(pcg_gr_kernel, dim3((unsigned)l.tchunks), dim3(256), h->stream, G, (long)ldg, q, a, tpart);
+        HIPLAUNCH(pcg_gr_finish_kernel, dim3((unsigned)((q * PCG_LD + 255) / 256)), dim3(256), h->stream, tpart, (long)l.tchunks, q, a.s, T);
+        // one right-hand side at a time: a column's sweeps are then the same launches whatever s is
+        for (int c = 0; c < a.s; ++c) { const int r = potrs_vec(h, C, q, ldc, T + c, 1, PCG_LD, true); if (r) return r; }
+    }
+    HIPLAUNCH(pcg_apply_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), h->stream, G, (long)ldg, q, T, a);
+    return 0;
+}
+
+struct PcgLayout { int64_t R, Z, P, AP, part1, state, mv, total, mv_doubles; PrecondLayout pre; };
 PcgLayout pcg_layout(int64_t n, int q) {
     PcgLayout l;
-    const int64_t qp = q > 0 ? pad128(q) : 0;
-    l.nblk = (n + 255) / 256;                 // the apply kernel's blocks (>= the DOT_ROWS blocks of the other partials)
-    l.tchunks = (n + PT_CHUNK - 1) / PT_CHUNK;
     l.mv_doubles = mv_auto_split(n, n) > 1 ? mv_split_doubles(n, n, MV_MAXS) : 0;
     int64_t o = 0;
     l.R = o; o += n * PCG_LD; l.Z = o; o += n * PCG_LD; l.P = o; o += n * PCG_LD; l.AP = o; o += n * PCG_LD;
-    l.T = o; o += qp * PCG_LD;
-    l.tpart = o; o += l.tchunks * q * PCG_LD;
-    l.part0 = o; o += l.nblk * PCG_LD; l.part1 = o; o += l.nblk * PCG_LD;
+    l.pre = precond_layout(n, q, o); o = l.pre.end;
+    l.part1 = o; o += (n + 255) / 256 * PCG_LD;
     l.state = o; o += even_up((int64_t)((sizeof(PcgState) + 7) / 8));
     l.mv = o; o += l.mv_doubles;
     l.total = o;
     return l;
 }
 
-// Z = M^-1 R for the solver's own vectors, part0 = r.z (blocks of 256 points): G (D^-1 R) in chunks, one potrs per column, the apply kernel.
-// T: pad128(q) rows of PCG_LD whose padding is zero
-int pcg_precond(fvgp_handle *h, const double *G, int64_t ldg, int q, const double *C, int64_t ldc, const PcgVec &a, double *T, double *tpart,
-                int64_t tchunks) {
-    hipStream_t st = h->stream;
-    if (q > 0) {
-        hipLaunchKernelGGL(pcg_gr_kernel, dim3((unsigned)tchunks), dim3(256), 0, st, G, (long)ldg, q, a, tpart);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(pcg_gr_finish_kernel, dim3((unsigned)((q * PCG_LD + 255) / 256)), dim3(256), 0, st, tpart, (long)tchunks, q, a.s, T);
-        HIPCHK(hipGetLastError());
-        // one right-hand side at a time: a column's sweeps are then the same launches whatever s is
-        for (int c = 0; c < a.s; ++c) { const int r = potrs_vec(h, C, q, ldc, T + c, 1, PCG_LD, true); if (r) return r; }
-    }
-    hipLaunchKernelGGL(pcg_apply_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, st, G, (long)ldg, q, T, a);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
 inline int64_t pcg_rec_doubles(int L) { return L > 0 ? (int64_t)PCG_LD * (2 * L + 3) : 0; }      // alpha, beta, rho0, and steps and first (ints) in two rows
 
-struct ApplyLayout { int64_t R, Z, T, tpart, part0, total, tchunks; };
+struct ApplyLayout { int64_t R, Z, total; PrecondLayout pre; };
 ApplyLayout apply_layout(int64_t n, int q) {
-    ApplyLayout l;
-    const int64_t qp = q > 0 ? pad128(q) : 0;
-    l.tchunks = (n + PT_CHUNK - 1) / PT_CHUNK;
-    int64_t o = 0;
-    l.R = o; o += n * PCG_LD; l.Z = o; o += n * PCG_LD;
-    l.T = o; o += qp * PCG_LD;
-    l.tpart = o; o += l.tchunks * q * PCG_LD;
-    l.part0 = o; o += (n + 255) / 256 * PCG_LD;
-    l.total = o;
+    ApplyLayout l{0, n * PCG_LD, 0, precond_layout(n, q, 2 * n * PCG_LD)};
+    l.total = l.pre.end;
     return l;
 }
 
+// what the two solver entries ask of the driver: the arguments of fvgp_hip_pcg_lanczos (include/fvgp_hip.h); fvgp_hip_pcg leaves L = 0
+struct PcgCall {
+    int kernel_id; const double *x; int64_t n; int d; const double *theta; int ntheta; const double *vdiag, *G; int64_t ldg; int q;
+    const double *C; int64_t ldc; const double *B; int64_t ldb; int s; double *X; int64_t ldx; int warm; double tol;
+    int max_iter, check_every, max_restarts; double *work; int64_t work_bytes; int *iters_host; double *relres_host; int *status_host;
+    int L; double *alpha_host, *beta_host; int *steps_host; double *rho0_host;
+};
+
 // the one driver of fvgp_hip_pcg (L == 0) and fvgp_hip_pcg_lanczos
-int pcg_driver(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta, int ntheta,
-               const double *vdiag, const double *G, int64_t ldg, int q, const double *C, int64_t ldc,
-               const double *B, int64_t ldb, int s, double *X, int64_t ldx, int warm,
-               double tol, int max_iter, int check_every, int max_restarts,
-               double *work, int64_t work_bytes, int *iters_host, double *relres_host, int *status_host,
-               int L, double *alpha_host, double *beta_host, int *steps_host, double *rho0_host) {
+int pcg_driver(fvgp_handle *h, PcgCall p) {
     if (!h) return -1;
-    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
-    if (!x) return -3;
-    if (n <= 0) return -4;
-    int rc = check_kernel_args(kernel_id, d, theta, ntheta, 5, 6, 7); if (rc) return rc;
-    if (!vdiag) { fvgp_set_error("pcg: the noise variances are the Jacobi part of the preconditioner and must be given"); return -8; }
-    if (!G) q = 0;
-    if (q < 0 || q > FVGP_PCG_MAX_RANK) { fvgp_set_error("pcg: rank outside 0 .. FVGP_PCG_MAX_RANK"); return -11; }
-    if (q > 0) {
-        if (ldg < n) return -10;
-        rc = check_square(C, q, ldc, 12, 11, 13);
+    if (!kernel_id_known(p.kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
+    if (!p.x) return -3;
+    if (p.n <= 0) return -4;
+    int rc = check_kernel_args(p.kernel_id, p.d, p.theta, p.ntheta, 5, 6, 7); if (rc) return rc;
+    if (!p.vdiag) { fvgp_set_error("pcg: the noise variances are the Jacobi part of the preconditioner and must be given"); return -8; }
+    if (!p.G) p.q = 0;
+    if (p.q < 0 || p.q > FVGP_PCG_MAX_RANK) { fvgp_set_error("pcg: rank outside 0 .. FVGP_PCG_MAX_RANK"); return -11; }
+    if (p.q > 0) {
+        if (p.ldg < p.n) return -10;
+        rc = check_square(p.C, p.q, p.ldc, 12, 11, 13);
         if (rc) return rc;
     }
-    if (!B) return -14;
-    if (s < 1 || s > FVGP_PCG_MAX_RHS) { fvgp_set_error("pcg: 1 .. FVGP_PCG_MAX_RHS right-hand sides per call"); return -16; }
-    if (ldb < s) return -15;
-    if (!X) return -17;
-    if (ldx < s) return -18;
-    if (!(tol > 0.0)) return -20;
-    if (max_iter < 1) return -21;
-    if (check_every < 1) return -22;
-    if (max_restarts < 0) return -23;
-    if (!work || ((uintptr_t)work & 15)) { fvgp_set_error("pcg: work must be 16-byte aligned"); return -24; }
-    if (L < 0 || L > FVGP_LANCZOS_MAX_STEPS) { fvgp_set_error("pcg_lanczos: lanczos_steps outside 0 .. FVGP_LANCZOS_MAX_STEPS"); return -29; }
-    if (work_bytes < (pcg_layout(n, q).total + pcg_rec_doubles(L)) * (int64_t)sizeof(double)) {
-        fvgp_set_error(L ? "pcg_lanczos: work smaller than fvgp_hip_pcg_lanczos_workspace_bytes(n, rank, lanczos_steps)"
+    if (!p.B) return -14;
+    if (p.s < 1 || p.s > FVGP_PCG_MAX_RHS) { fvgp_set_error("pcg: 1 .. FVGP_PCG_MAX_RHS right-hand sides per call"); return -16; }
+    if (p.ldb < p.s) return -15;
+    if (!p.X) return -17;
+    if (p.ldx < p.s) return -18;
+    if (!(p.tol > 0.0)) return -20;
+    if (p.max_iter < 1) return -21;
+    if (p.check_every < 1) return -22;
+    if (p.max_restarts < 0) return -23;
+    if (!p.work || ((uintptr_t)p.work & 15)) { fvgp_set_error("pcg: work must be 16-byte aligned"); return -24; }
+    if (p.L < 0 || p.L > FVGP_LANCZOS_MAX_STEPS) { fvgp_set_error("pcg_lanczos: lanczos_steps outside 0 .. FVGP_LANCZOS_MAX_STEPS"); return -29; }
+    if (p.work_bytes < (pcg_layout(p.n, p.q).total + pcg_rec_doubles(p.L)) * (int64_t)sizeof(double)) {
+        fvgp_set_error(p.L ? "pcg_lanczos: work smaller than fvgp_hip_pcg_lanczos_workspace_bytes(n, rank, lanczos_steps)"
                          : "pcg: work smaller than fvgp_hip_pcg_workspace_bytes(n, rank)");
         return -25;
     }
-    if (!iters_host) return -26;
-    if (!relres_host) return -27;
-    if (!status_host) return -28;
-    if (L > 0) {
-        if (!alpha_host) return -30;
-        if (!beta_host) return -31;
-        if (!steps_host) return -32;
-        if (!rho0_host) return -33;
+    if (!p.iters_host) return -26;
+    if (!p.relres_host) return -27;
+    if (!p.status_host) return -28;
+    if (p.L > 0) {
+        if (!p.alpha_host) return -30;
+        if (!p.beta_host) return -31;
+        if (!p.steps_host) return -32;
+        if (!p.rho0_host) return -33;
     }
     HIPCHK(hipSetDevice(h->device));
     KmatDesc k{};
-    rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
-    k.x1 = x; k.n1 = n; k.x2 = x; k.n2 = n; k.vdiag = vdiag;
-    const PcgLayout lay = pcg_layout(n, q);
+    rc = kmat_desc_from_theta(p.kernel_id, p.d, p.theta, p.ntheta, &k); if (rc) return rc;
+    k.x1 = p.x; k.n1 = p.n; k.x2 = p.x; k.n2 = p.n; k.vdiag = p.vdiag;
+    const PcgLayout lay = pcg_layout(p.n, p.q);
     PcgRec rec{};                                                 // L == 0: every pointer NULL, the scalar kernel records nothing
-    if (L > 0) {
-        double *rw = work + lay.total;
-        rec.alpha = rw; rec.beta = rw + (int64_t)PCG_LD * L; rec.rho0 = rw + 2 * (int64_t)PCG_LD * L;
-        rec.steps = reinterpret_cast<int *>(rw + 2 * (int64_t)PCG_LD * L + PCG_LD); rec.first = rec.steps + PCG_LD;
-        rec.L = L;
-        HIPCHK(hipMemsetAsync(rw, 0, (size_t)pcg_rec_doubles(L) * sizeof(double), h->stream));
+    if (p.L > 0) {
+        double *rw = p.work + lay.total;
+        rec.alpha = rw; rec.beta = rw + (int64_t)PCG_LD * p.L; rec.rho0 = rw + 2 * (int64_t)PCG_LD * p.L;
+        rec.steps = reinterpret_cast<int *>(rw + 2 * (int64_t)PCG_LD * p.L + PCG_LD); rec.first = rec.steps + PCG_LD;
+        rec.L = p.L;
+        HIPCHK(hipMemsetAsync(rw, 0, (size_t)pcg_rec_doubles(p.L) * sizeof(double), h->stream));
     }
     PcgVec a;
-    a.R = work + lay.R; a.Z = work + lay.Z; a.P = work + lay.P; a.AP = work + lay.AP;
-    a.X = X; a.ldx = ldx; a.B = B; a.ldb = ldb; a.v = vdiag;
-    a.st = reinterpret_cast<PcgState *>(work + lay.state);
-    a.part0 = work + lay.part0; a.part1 = work + lay.part1;
-    a.n = n; a.s = s;
-    double *T = work + lay.T, *tpart = work + lay.tpart, *mvws = lay.mv_doubles ? work + lay.mv : nullptr;
-    const int64_t qp = q > 0 ? pad128(q) : 0;
-    const long nblk = (long)((n + DOT_ROWS - 1) / DOT_ROWS), nblk_apply = (long)((n + 255) / 256);
-    const dim3 gdot((unsigned)nblk), gdir((unsigned)((n * PCG_LD + 255) / 256));
+    a.R = p.work + lay.R; a.Z = p.work + lay.Z; a.P = p.work + lay.P; a.AP = p.work + lay.AP;
+    a.X = p.X; a.ldx = p.ldx; a.B = p.B; a.ldb = p.ldb; a.v = p.vdiag;
+    a.st = reinterpret_cast<PcgState *>(p.work + lay.state);
+    a.part1 = p.work + lay.part1;
+    a.n = p.n; a.s = p.s;
+    rc = precond_begin(h, p.work, lay.pre, a); if (rc) return rc;
+    double *mvws = lay.mv_doubles ? p.work + lay.mv : nullptr;
+    const long nblk = (long)((p.n + DOT_ROWS - 1) / DOT_ROWS), nblk_apply = (long)((p.n + 255) / 256);
+    const dim3 gdot((unsigned)nblk), gdir((unsigned)((p.n * PCG_LD + 255) / 256));
     hipStream_t st = h->stream;
 
     auto matvec = [&](const double *V, int64_t ldv) -> int {     // AP = (K + D) V
-        return launch_kmatvec(h, k, V, ldv, s, a.AP, PCG_LD, mvws, lay.mv_doubles, true);
+        return launch_kmatvec(h, k, V, ldv, p.s, a.AP, PCG_LD, mvws, lay.mv_doubles, true);
     };
     auto scalar = [&](const PcgVec &v, long nb, int mode) -> int {
-        hipLaunchKernelGGL(pcg_scalar_kernel, dim3(1), dim3(256), 0, st, v, nb, mode, tol, max_iter, rec);
-        HIPCHK(hipGetLastError());
+        HIPLAUNCH(pcg_scalar_kernel, dim3(1), dim3(256), st, v, nb, mode, p.tol, p.max_iter, rec);
         return 0;
     };
-    auto precond = [&]() -> int { return pcg_precond(h, G, ldg, q, C, ldc, a, T, tpart, lay.tchunks); };
+    auto precond = [&]() -> int { return pcg_precond(h, p.G, p.ldg, p.q, p.C, p.ldc, a, p.work, lay.pre); };
     PcgVec a1 = a; a1.part1 = a.part0;                            // (a scalar step that reads one partial array)
 
-    if (qp) HIPCHK(hipMemsetAsync(T, 0, (size_t)qp * PCG_LD * sizeof(double), st));
-    if (warm) {
-        rc = matvec(X, ldx); if (rc) return rc;
-        hipLaunchKernelGGL(pcg_resid_kernel, gdot, dim3(256), 0, st, a, 1);
-        HIPCHK(hipGetLastError());
+    if (p.warm) {
+        rc = matvec(p.X, p.ldx); if (rc) return rc;
+        HIPLAUNCH(pcg_resid_kernel, gdot, dim3(256), st, a, 1);
         rc = scalar(a, nblk, SC_INIT); if (rc) return rc;
-        hipLaunchKernelGGL(pcg_zero_cols_kernel, gdir, dim3(256), 0, st, a);
-        HIPCHK(hipGetLastError());
+        HIPLAUNCH(pcg_zero_cols_kernel, gdir, dim3(256), st, a);
     } else {
-        hipLaunchKernelGGL(pcg_resid_kernel, gdot, dim3(256), 0, st, a, 0);
-        HIPCHK(hipGetLastError());
+        HIPLAUNCH(pcg_resid_kernel, gdot, dim3(256), st, a, 0);
         rc = scalar(a1, nblk, SC_INIT); if (rc) return rc;
     }
     rc = precond(); if (rc) return rc;
     rc = scalar(a1, nblk_apply, SC_RHO0); if (rc) return rc;
-    hipLaunchKernelGGL(pcg_dir_kernel, gdir, dim3(256), 0, st, a);
-    HIPCHK(hipGetLastError());
+    HIPLAUNCH(pcg_dir_kernel, gdir, dim3(256), st, a);
 
     PcgState hs;
     int restarts[PCG_LD] = {0};
@@ -823,39 +541,35 @@ int pcg_driver(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
     // no column iterates more than max_iter times in all; each restart round ends when every column is frozen
     for (;;) {
         for (int it = 0;; ++it) {
-            if (it % check_every == 0) {
+            if (it % p.check_every == 0) {
                 HIPCHK(hipMemcpyAsync(&hs, a.st, sizeof(hs), hipMemcpyDeviceToHost, st));
                 HIPCHK(hipStreamSynchronize(st));
                 bool any = false;
-                for (int c = 0; c < s; ++c) any = any || hs.active[c];
+                for (int c = 0; c < p.s; ++c) any = any || hs.active[c];
                 if (!any) break;
             }
             rc = matvec(a.P, PCG_LD); if (rc) return rc;
-            hipLaunchKernelGGL(pcg_dot_kernel, gdot, dim3(256), 0, st, a.P, a.AP, (long)n, s, a.part0);
-            HIPCHK(hipGetLastError());
+            HIPLAUNCH(pcg_dot_kernel, gdot, dim3(256), st, a.P, a.AP, (long)p.n, p.s, a.part0);
             rc = scalar(a1, nblk, SC_ALPHA); if (rc) return rc;
-            hipLaunchKernelGGL(pcg_axpy_kernel, gdot, dim3(256), 0, st, a);
-            HIPCHK(hipGetLastError());
+            HIPLAUNCH(pcg_axpy_kernel, gdot, dim3(256), st, a);
             rc = scalar(a1, nblk, SC_RNORM); if (rc) return rc;
             rc = precond(); if (rc) return rc;
             rc = scalar(a1, nblk_apply, SC_BETA); if (rc) return rc;
-            hipLaunchKernelGGL(pcg_dir_kernel, gdir, dim3(256), 0, st, a);
-            HIPCHK(hipGetLastError());
+            HIPLAUNCH(pcg_dir_kernel, gdir, dim3(256), st, a);
         }
         // every column is frozen: the true residual b - A x decides
-        rc = matvec(X, ldx); if (rc) return rc;
-        hipLaunchKernelGGL(pcg_resid_kernel, gdot, dim3(256), 0, st, a, 2);
-        HIPCHK(hipGetLastError());
+        rc = matvec(p.X, p.ldx); if (rc) return rc;
+        HIPLAUNCH(pcg_resid_kernel, gdot, dim3(256), st, a, 2);
         rc = scalar(a, nblk, SC_TRUE); if (rc) return rc;
         HIPCHK(hipMemcpyAsync(&hs, a.st, sizeof(hs), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         bool again = false;
-        for (int c = 0; c < s; ++c) {
+        for (int c = 0; c < p.s; ++c) {
             if (final_col[c]) continue;
-            iters_host[c] = hs.iters[c]; relres_host[c] = hs.relres[c];
-            if (hs.relres[c] <= tol) { status_host[c] = 0; final_col[c] = true; }
-            else if (hs.code[c] == 2) { status_host[c] = 2; final_col[c] = true; }
-            else if (hs.code[c] == 1 || restarts[c] >= max_restarts || !(hs.relres[c] == hs.relres[c])) { status_host[c] = 1; final_col[c] = true; }
+            p.iters_host[c] = hs.iters[c]; p.relres_host[c] = hs.relres[c];
+            if (hs.relres[c] <= p.tol) { p.status_host[c] = 0; final_col[c] = true; }
+            else if (hs.code[c] == 2) { p.status_host[c] = 2; final_col[c] = true; }
+            else if (hs.code[c] == 1 || restarts[c] >= p.max_restarts || !(hs.relres[c] == hs.relres[c])) { p.status_host[c] = 1; final_col[c] = true; }
             else { restarts[c] += 1; hs.restart[c] = 1; again = true; }
         }
         if (!again) break;
@@ -863,14 +577,13 @@ int pcg_driver(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
         HIPCHK(hipStreamSynchronize(st));                         // (hs is on the stack: the copy must have read it before it changes)
         rc = precond(); if (rc) return rc;
         rc = scalar(a1, nblk_apply, SC_RESTART); if (rc) return rc;
-        hipLaunchKernelGGL(pcg_dir_kernel, gdir, dim3(256), 0, st, a);
-        HIPCHK(hipGetLastError());
+        HIPLAUNCH(pcg_dir_kernel, gdir, dim3(256), st, a);
     }
-    if (L > 0) {
-        HIPCHK(hipMemcpyAsync(alpha_host, rec.alpha, (size_t)s * L * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(beta_host, rec.beta, (size_t)s * L * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(rho0_host, rec.rho0, (size_t)s * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(steps_host, rec.steps, (size_t)s * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (p.L > 0) {
+        HIPCHK(hipMemcpyAsync(p.alpha_host, rec.alpha, (size_t)p.s * p.L * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(p.beta_host, rec.beta, (size_t)p.s * p.L * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(p.rho0_host, rec.rho0, (size_t)p.s * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(p.steps_host, rec.steps, (size_t)p.s * sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
     return 0;
@@ -879,38 +592,6 @@ int pcg_driver(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
 }  // namespace
 
 extern "C" {
-
-int64_t fvgp_hip_kmatvec_workspace_bytes(int64_t n1, int64_t n2, int s) {
-    if (n1 < 1 || n2 < 1 || s < 1) return -1;
-    return mv_split_doubles(n1, n2, s) * (int64_t)sizeof(double);
-}
-
-int fvgp_hip_kmatvec(fvgp_handle *h, int kernel_id, const double *x1, int64_t n1, const double *x2, int64_t n2, int d,
-                     const double *theta, int ntheta, const double *vdiag, const double *B, int64_t ldb, int s,
-                     double *Y, int64_t ldy, double *work, int64_t work_bytes) {
-    if (!h) return -1;
-    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
-    if (!x1) return -3;
-    if (n1 <= 0) return -4;
-    if (!x2) return -5;
-    if (n2 <= 0) return -6;
-    int rc = check_kernel_args(kernel_id, d, theta, ntheta, 7, 8, 9); if (rc) return rc;
-    if (vdiag && n1 != n2) { fvgp_set_error("kmatvec: vdiag needs n1 == n2"); return -10; }
-    if (!B) return -11;
-    if (s < 1) return -13;
-    if (ldb < s) return -12;
-    if (!Y) return -14;
-    if (ldy < s) return -15;
-    if (work && ((uintptr_t)work & 7)) return -16;
-    if (work_bytes < 0) return -17;
-    if ((n1 + 63) / 64 > 0x7fffffffLL) return -4;
-    HIPCHK(hipSetDevice(h->device));
-    KmatDesc k{};
-    rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
-    k.x1 = x1; k.n1 = n1; k.x2 = x2; k.n2 = n2; k.vdiag = vdiag;
-    rc = launch_kmatvec(h, k, B, ldb, s, Y, ldy, work, work ? work_bytes / 8 : 0, false);
-    return rc == -1 ? -17 : rc;
-}
 
 int64_t fvgp_hip_pchol_workspace_bytes(int64_t n, int q) {
     if (n < 1 || q < 1) return -1;
@@ -950,16 +631,13 @@ int fvgp_hip_pchol(fvgp_handle *h, int kernel_id, const double *x, int64_t n, in
     // the rows an exhausted run never reaches are zero rows: G is cleared first, inside its (q, n) view only
     for (int64_t r0 = 0; r0 < q; r0 += 1024) {
         const int64_t rows = q - r0 < 1024 ? q - r0 : 1024;
-        hipLaunchKernelGGL(mf_zero_rows_kernel, dim3((unsigned)((rows * n + 255) / 256)), dim3(256), 0, h->stream, G + r0 * ldg, (long)ldg,
-                           (long)rows, (long)n);
-        HIPCHK(hipGetLastError());
+        HIPLAUNCH(mf_zero_rows_kernel, dim3((unsigned)((rows * n + 255) / 256)), dim3(256), h->stream, G + r0 * ldg, (long)ldg,
+                  (long)rows, (long)n);
     }
-    hipLaunchKernelGGL(pivot_init_kernel, dim3(nb), dim3(256), 0, h->stream, a);
-    HIPCHK(hipGetLastError());
+    HIPLAUNCH(pivot_init_kernel, dim3(nb), dim3(256), h->stream, a);
     for (int t = 0; t < q; ++t) {
         a.t = t;
-        hipLaunchKernelGGL(pivot_pick_kernel, dim3(1), dim3(256), 0, h->stream, a);
-        HIPCHK(hipGetLastError());
+        HIPLAUNCH(pivot_pick_kernel, dim3(1), dim3(256), h->stream, a);
         dispatch_kind(k.kind, [&](auto KIND) {
             hipLaunchKernelGGL((pivot_downdate_kernel<decltype(KIND)::value, false>), dim3(nb), dim3(256), 0, h->stream, a, 0L);
         });
@@ -996,10 +674,8 @@ int fvgp_hip_precond_factor(fvgp_handle *h, const double *G, int64_t ldg, int q,
     const int64_t nch = (n + PF_CHUNK - 1) / PF_CHUNK;
     if (nch > 65535) { fvgp_set_error("precond_factor: n too large"); return -5; }
     const int nt = (q + 15) / 16;
-    hipLaunchKernelGGL(pf_gram_kernel, dim3((unsigned)(nt * nt), (unsigned)nch), dim3(256), 0, h->stream, G, (long)ldg, q, (long)n, vdiag, work);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(pf_finish_kernel, dim3((unsigned)(((int64_t)q * q + 255) / 256)), dim3(256), 0, h->stream, work, (long)nch, q, C, (long)ldc);
-    HIPCHK(hipGetLastError());
+    HIPLAUNCH(pf_gram_kernel, dim3((unsigned)(nt * nt), (unsigned)nch), dim3(256), h->stream, G, (long)ldg, q, (long)n, vdiag, work);
+    HIPLAUNCH(pf_finish_kernel, dim3((unsigned)(((int64_t)q * q + 255) / 256)), dim3(256), h->stream, work, (long)nch, q, C, (long)ldc);
     rc = launch_pad_identity(h, C, q, pad128(q), ldc); if (rc) return rc;
     return potrf_driver(h, C, q, ldc, info_host);
 }
@@ -1014,8 +690,8 @@ int fvgp_hip_pcg(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int 
                  const double *B, int64_t ldb, int s, double *X, int64_t ldx, int warm,
                  double tol, int max_iter, int check_every, int max_restarts,
                  double *work, int64_t work_bytes, int *iters_host, double *relres_host, int *status_host) {
-    return pcg_driver(h, kernel_id, x, n, d, theta, ntheta, vdiag, G, ldg, q, C, ldc, B, ldb, s, X, ldx, warm, tol, max_iter, check_every,
-                      max_restarts, work, work_bytes, iters_host, relres_host, status_host, 0, nullptr, nullptr, nullptr, nullptr);
+    return pcg_driver(h, PcgCall{kernel_id, x, n, d, theta, ntheta, vdiag, G, ldg, q, C, ldc, B, ldb, s, X, ldx, warm, tol, max_iter, check_every,
+                                 max_restarts, work, work_bytes, iters_host, relres_host, status_host, 0, nullptr, nullptr, nullptr, nullptr});
 }
 
 int64_t fvgp_hip_pcg_lanczos_workspace_bytes(int64_t n, int q, int lanczos_steps) {
@@ -1029,80 +705,9 @@ int fvgp_hip_pcg_lanczos(fvgp_handle *h, int kernel_id, const double *x, int64_t
                          double tol, int max_iter, int check_every, int max_restarts,
                          double *work, int64_t work_bytes, int *iters_host, double *relres_host, int *status_host,
                          int lanczos_steps, double *alpha_host, double *beta_host, int *steps_host, double *rho0_host) {
-    return pcg_driver(h, kernel_id, x, n, d, theta, ntheta, vdiag, G, ldg, q, C, ldc, B, ldb, s, X, ldx, warm, tol, max_iter, check_every,
-                      max_restarts, work, work_bytes, iters_host, relres_host, status_host, lanczos_steps, alpha_host, beta_host, steps_host,
-                      rho0_host);
-}
-
-int64_t fvgp_hip_kgrad_form_workspace_bytes(int64_t n1, int64_t n2) {
-    if (n1 < 1 || n2 < 1) return -1;
-    const int64_t park = (n1 + 63) / 64 < 512 && mv_chunks(n2) > 1 ? mv_chunks(n2) * n1 * KG_H : 0;
-    return (kg_base_doubles(n1) + park) * (int64_t)sizeof(double);
-}
-
-int fvgp_hip_kgrad_form(fvgp_handle *h, int kernel_id, const double *x1, int64_t n1, const double *x2, int64_t n2, int d,
-                        const double *theta, int ntheta, const double *U, int64_t ldu, const double *W, int64_t ldw, int s,
-                        double *work, int64_t work_bytes, double *out_host) {
-    if (!h) return -1;
-    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
-    if (!x1) return -3;
-    if (n1 <= 0 || (n1 + 63) / 64 > 0x7fffffffLL) return -4;
-    if (!x2) return -5;
-    if (n2 <= 0) return -6;
-    int rc = check_kernel_args(kernel_id, d, theta, ntheta, 7, 8, 9); if (rc) return rc;
-    if (!U) return -10;
-    if (s < 1 || s > FVGP_PCG_MAX_RHS) { fvgp_set_error("kgrad_form: 1 .. FVGP_PCG_MAX_RHS columns per call"); return -14; }
-    if (ldu < s) return -11;
-    if (!W) return -12;
-    if (ldw < s) return -13;
-    if (!work || ((uintptr_t)work & 7)) return -15;
-    if (work_bytes < kg_base_doubles(n1) * (int64_t)sizeof(double)) { fvgp_set_error("kgrad_form: work smaller than fvgp_hip_kgrad_form_workspace_bytes(n1, n2)"); return -16; }
-    if (!out_host) return -17;
-    HIPCHK(hipSetDevice(h->device));
-    KmatDesc k{};
-    rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
-    KgArgs a;
-    a.x1 = x1; a.x2 = x2; a.U = U; a.W = W;
-    a.n1 = n1; a.n2 = n2; a.ldu = ldu; a.ldw = ldw; a.nchunks = mv_chunks(n2);
-    a.d = d; a.iso = k.iso ? 1 : 0; a.sig = k.sig;
-    for (int i = 0; i < FVGP_MAX_DIM; ++i) a.il[i] = k.invl[i];
-    const int nh = kernel_param_count(kernel_id, d);
-    const int64_t bx = (n1 + 63) / 64;
-    double *out = work, *bpart = work + KG_H, *park = work + kg_base_doubles(n1);
-    a.bpart = bpart;
-    // the chunk ranges are dealt over gridDim.y by the product's rule, where `work` has room for the chunk sums (the bits are the same)
-    int64_t gy = h->matvec_split == 0 ? mv_auto_split(n1, n2) : h->matvec_split;
-    if (gy > a.nchunks) gy = a.nchunks;
-    if (gy > 65535) gy = 65535;
-    const bool split = gy > 1 && work_bytes / 8 >= kg_base_doubles(n1) + a.nchunks * n1 * KG_H;
-    a.park = split ? park : nullptr;
-    a.cpy = split ? (a.nchunks + gy - 1) / gy : a.nchunks;
-    const dim3 grid((unsigned)bx, split ? (unsigned)((a.nchunks + a.cpy - 1) / a.cpy) : 1u);
-    for (int c0 = 0; c0 < s;) {
-        const int left = s - c0;
-        const int S = mv_group(left);
-        a.c0 = c0; a.sc = left < S ? left : S;
-        dispatch_kind_dim(k.kind, d, [&](auto KIND, auto D) {
-            constexpr int KK = decltype(KIND)::value, DV = decltype(D)::value;
-            switch (S) {
-                case 16: kg_launch<KK, DV, 16>(h, a, grid); break;
-                case 8: kg_launch<KK, DV, 8>(h, a, grid); break;
-                case 4: kg_launch<KK, DV, 4>(h, a, grid); break;
-                default: kg_launch<KK, DV, 1>(h, a, grid); break;
-            }
-        });
-        HIPCHK(hipGetLastError());
-        if (split) {
-            hipLaunchKernelGGL(kgrad_rows_kernel, dim3((unsigned)bx), dim3(64), 0, h->stream, a);
-            HIPCHK(hipGetLastError());
-        }
-        hipLaunchKernelGGL(kgrad_sum_kernel, dim3(1), dim3(64), 0, h->stream, (const double *)bpart, (long)bx, nh, c0 == 0 ? 1 : 0, out);
-        HIPCHK(hipGetLastError());
-        c0 += a.sc;
-    }
-    HIPCHK(hipMemcpyAsync(out_host, out, (size_t)nh * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return pcg_driver(h, PcgCall{kernel_id, x, n, d, theta, ntheta, vdiag, G, ldg, q, C, ldc, B, ldb, s, X, ldx, warm, tol, max_iter, check_every,
+                                 max_restarts, work, work_bytes, iters_host, relres_host, status_host, lanczos_steps, alpha_host, beta_host,
+                                 steps_host, rho0_host});
 }
 
 int fvgp_hip_precond_probes(fvgp_handle *h, uint64_t seed, uint64_t stream, int64_t col0, const double *G, int64_t ldg, int q,
@@ -1125,8 +730,7 @@ int fvgp_hip_precond_probes(fvgp_handle *h, uint64_t seed, uint64_t stream, int6
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
     a.e0 = (uint32_t)se; a.e1 = (uint32_t)(se >> 32); a.g0 = (uint32_t)sg; a.g1 = (uint32_t)(sg >> 32);
     a.G = G; a.v = vdiag; a.Z = Z; a.ldg = ldg; a.n = n; a.ldz = ldz; a.col0 = col0; a.q = q; a.s = s;
-    hipLaunchKernelGGL(precond_probes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, a);
-    HIPCHK(hipGetLastError());
+    HIPLAUNCH(precond_probes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), h->stream, a);
     return 0;
 }
 
@@ -1158,15 +762,12 @@ int fvgp_hip_precond_apply(fvgp_handle *h, const double *G, int64_t ldg, int q, 
     HIPCHK(hipSetDevice(h->device));
     const ApplyLayout lay = apply_layout(n, q);
     PcgVec a{};
-    a.R = work + lay.R; a.Z = work + lay.Z; a.v = vdiag; a.part0 = work + lay.part0; a.n = n; a.s = s;
-    const int64_t qp = q > 0 ? pad128(q) : 0;
+    a.R = work + lay.R; a.Z = work + lay.Z; a.v = vdiag; a.n = n; a.s = s;
+    int rc = precond_begin(h, work, lay.pre, a); if (rc) return rc;
     const dim3 gcopy((unsigned)((n * PCG_LD + 255) / 256));
-    if (qp) HIPCHK(hipMemsetAsync(work + lay.T, 0, (size_t)qp * PCG_LD * sizeof(double), h->stream));
-    hipLaunchKernelGGL(mf_copy_cols_kernel, gcopy, dim3(256), 0, h->stream, R, (long)ldr, a.R, (long)PCG_LD, (long)n, s);
-    HIPCHK(hipGetLastError());
-    const int rc = pcg_precond(h, G, ldg, q, C, ldc, a, work + lay.T, work + lay.tpart, lay.tchunks); if (rc) return rc;
-    hipLaunchKernelGGL(mf_copy_cols_kernel, gcopy, dim3(256), 0, h->stream, (const double *)a.Z, (long)PCG_LD, W, (long)ldw, (long)n, s);
-    HIPCHK(hipGetLastError());
+    HIPLAUNCH(mf_copy_cols_kernel, gcopy, dim3(256), h->stream, R, (long)ldr, a.R, (long)PCG_LD, (long)n, s);
+    rc = pcg_precond(h, G, ldg, q, C, ldc, a, work, lay.pre); if (rc) return rc;
+    HIPLAUNCH(mf_copy_cols_kernel, gcopy, dim3(256), h->stream, (const double *)a.Z, (long)PCG_LD, W, (long)ldw, (long)n, s);
     return 0;
 }
 

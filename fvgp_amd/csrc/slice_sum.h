@@ -1,4 +1,4 @@
-// Sums over the data rows with LANES ALONG POINTS (posterior_grad.hip, select.hip, matrix_free.hip): the rows are cut into slices of SLICE_ROWS, one
+// Sums over the data rows with LANES ALONG POINTS (posterior_grad.hip, select.hip, matvec.hip): the rows are cut into slices of SLICE_ROWS, one
 // workgroup of four waves per (64 points, slice).  The slice's x rows and one vector entry per row are staged in LDS once (every lane
 // reads the same row: broadcast reads), each wave takes SLICE_WAVE_ROWS of them, and the sums of waves 1 .. 3 are parked in LDS for
 // wave 0 to add in wave order.  The split is a function of n alone: a point's sums have the same bits whatever else rides in the launch.
@@ -31,7 +31,7 @@ __device__ __forceinline__ void slice_stage(double *sx, double *sa, const double
     }
 }
 
-// slice_stage with S entries per row (matrix_free.hip): sb[r][S] <- B[row0 + r][c0 .. c0 + sc) (0 past n and from column sc on)
+// slice_stage with S entries per row (matvec.hip): sb[r][S] <- B[row0 + r][c0 .. c0 + sc) (0 past n and from column sc on)
 template <int DD, int S>
 __device__ __forceinline__ void slice_stage_cols(double *sx, double *sb, const double *x, const double *B, long ldb, int c0, int sc,
                                                  long n, int d, long row0, int tid) {

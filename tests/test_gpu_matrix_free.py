@@ -88,7 +88,8 @@ def test_identity_columns_return_the_entries_of_k(H, kernel):
 
 # ---- 2. the product against longdouble ---------------------------------------------------------------------------------------------------
 # (kernel, d, n1, n2, s, vdiag, matvec_split): every n1 of {1, 63, 64, 65, 300}, every n2 of {1, 255, 256, 257, CHUNK - 1, CHUNK, CHUNK + 1,
-# 2 CHUNK + 37}, every s of {1, 3, 8, 16, 17}, vdiag on and off (on needs n1 == n2), split forced (k), forbidden (1) and by the shape (0)
+# 2 CHUNK + 37}, every s of {1, 3, 8, 16, 17}, vdiag on and off (on needs n1 == n2), split forced (k), forbidden (1) and by the shape (0);
+# the last two are the runtime-dimension kernels (d = 5) with wide column groups and parked chunk sums
 PRODUCT_CASES = [
     ("rbf_ard", 1, 1, 1, 1, True, 0),
     ("matern32_ard", 2, 63, 255, 3, False, 0),
@@ -103,6 +104,8 @@ PRODUCT_CASES = [
     ("matern32_ard", 1, 65, 2 * CHUNK + 37, 3, False, 1),
     ("rbf_ard", 3, 1, 2 * CHUNK + 37, 16, False, 0),
     ("matern32_ard", 2, 257, 257, 5, True, 2),
+    ("rbf_ard", 5, 65, 2 * CHUNK + 37, 8, False, 3),
+    ("matern52_iso", 5, 1, CHUNK + 1, 16, False, 2),
 ]
 
 
@@ -127,7 +130,8 @@ def test_product_against_longdouble(H, case):
 # ---- 3. the bit contract of the product --------------------------------------------------------------------------------------------------
 def test_product_bits_do_not_depend_on_the_rest_of_the_call(H):
     """column c alone against inside s = 17 (groups 16 + 1 against a group of 1); row i in calls of 1, 65 and 300 rows; split (forced 2, 3
-    and by the shape) against unsplit at n2 = 2 CHUNK + 37; the same call twice"""
+    and by the shape) against unsplit at n2 = 2 CHUNK + 37; the same call twice; split 3 against unsplit on the runtime-dimension kernel
+    (d = 5, n1 = 65, s = 16)"""
     kernel, d, n2, s = "matern52_ard", 3, 2 * CHUNK + 37, 17
     x1, x2, B, _ = mf.matvec_case(300, n2, d, s, 4242)
     theta = mf.theta_of(kernel, d, 0.3)
@@ -143,6 +147,9 @@ def test_product_bits_do_not_depend_on_the_rest_of_the_call(H):
         for i0 in (0, 131):
             got = _matvec(H, kernel, x1[i0:i0 + rows].copy(), x2, theta, B, split=0, x2d=x2d)
             assert np.array_equal(full[i0:i0 + rows], got), (rows, i0)
+    x5, y5, B5, _ = mf.matvec_case(65, n2, 5, 16, 4243)
+    th5 = mf.theta_of(kernel, 5, 0.3)
+    assert np.array_equal(_matvec(H, kernel, x5, y5, th5, B5, split=1), _matvec(H, kernel, x5, y5, th5, B5, split=3))
     # with vdiag (n1 == n2): rows cannot be cut, columns can
     xs, _, Bs, v = mf.matvec_case(300, 300, d, 17, 99, square=True)
     sq = _matvec(H, kernel, xs, xs, theta, Bs, v=v)

@@ -101,7 +101,8 @@ def _form(H, kernel, x1, x2, U, W, theta, split=0, work=None, fill=None):
 
 # (kernel, d, n1, n2, s, x1 = x2 and U = W): every kernel id, d = 1 .. 4 and 5 (the runtime-dimension instantiation), the shapes
 # (1, 1), (63, 65), (64, 257), (257, 255), (300, 4097), (130, 8193) -- one row, ragged blocks, more than one block, a ragged last slice, one
-# chunk and a bit, two chunks and a bit (the split launch) -- s of {1, 3, 4, 16}, and s = 9: two groups (8 + 1), the second ADDED to the first
+# chunk and a bit, two chunks and a bit (the split launch) -- s of {1, 3, 4, 16}, and s = 9: two groups (8 + 1), the second ADDED to the first;
+# the last two are the runtime-dimension kernels with wide column groups and parked chunk sums (the register-tight instantiations)
 FORM_CASES = [
     ("rbf_ard", 1, 1, 1, 1, False),
     ("matern32_ard", 2, 63, 65, 3, False),
@@ -115,6 +116,8 @@ FORM_CASES = [
     ("matern32_iso", 1, 64, 257, 1, False),
     ("rbf_iso", 3, 63, 65, 4, False),
     ("matern52_iso", 4, 1, 1, 3, False),
+    ("matern52_ard", 5, 65, 2 * CHUNK + 37, 16, False),
+    ("rbf_ard", 5, 130, CHUNK + 1, 9, False),
 ]
 
 
@@ -139,16 +142,17 @@ def test_form_against_longdouble(H, case):
 def test_form_bits(H):
     """the same call twice; whatever the workspace held before; unsplit (1), forced splits (2, 3) and the split by the shape (0), with and
     without room for the parked chunk sums; nothing behind the result's entries is written.  (The column groups are part of the value --
-    include/fvgp_hip.h -- so a sum of one-column calls on the host is NOT asserted equal.)"""
+    include/fvgp_hip.h -- so a sum of one-column calls on the host is NOT asserted equal.)  The same at d = 5, n1 = 65, s = 16: the
+    runtime-dimension kernel with the widest column group."""
     from fvgp_amd import _lib
-    kernel, d, n1, n2, s = "matern52_ard", 3, 130, 2 * CHUNK + 37, 9
-    x1, x2, U, W, theta = form_case(kernel, d, n1, n2, s, False, 77)
-    full = _form(H, kernel, x1, x2, U, W, theta, split=1, fill=0.0)
-    assert np.array_equal(full, _form(H, kernel, x1, x2, U, W, theta, split=1, fill=float("nan")))
-    for k in (0, 2, 3):
-        assert np.array_equal(full, _form(H, kernel, x1, x2, U, W, theta, split=k, fill=CANARY)), k
-    small = H.empty((1 + 3) * 17)                                 # no room for the chunk sums: one workgroup walks the chunks
-    assert np.array_equal(full, _form(H, kernel, x1, x2, U, W, theta, split=3, work=small, fill=CANARY))
+    for kernel, d, n1, n2, s in (("matern52_ard", 5, 65, 2 * CHUNK + 37, 16), ("matern52_ard", 3, 130, 2 * CHUNK + 37, 9)):
+        x1, x2, U, W, theta = form_case(kernel, d, n1, n2, s, False, 77)
+        full = _form(H, kernel, x1, x2, U, W, theta, split=1, fill=0.0)
+        assert np.array_equal(full, _form(H, kernel, x1, x2, U, W, theta, split=1, fill=float("nan")))
+        for k in (0, 2, 3):
+            assert np.array_equal(full, _form(H, kernel, x1, x2, U, W, theta, split=k, fill=CANARY)), (d, k)
+        small = H.empty((1 + (n1 + 63) // 64) * 17)               # no room for the chunk sums: one workgroup walks the chunks
+        assert np.array_equal(full, _form(H, kernel, x1, x2, U, W, theta, split=3, work=small, fill=CANARY)), d
     # zero columns change nothing: 9 columns against the same 9 inside wider arrays is not a contract, but U = 0 columns are
     U0, W0 = U.copy(), W.copy()
     U0[:, 8] = 0.0
