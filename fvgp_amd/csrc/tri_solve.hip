@@ -216,11 +216,12 @@ int fvgp_hip_potrs(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, doub
     if (!B) return -5;
     if (nrhs <= 0) return -6;
     if (ldb < nrhs) return -7;
+    // refused before anything is written: the padding rows of B keep their bits
+    if (nrhs > FVGP_MAX_RHS_VEC && (nrhs % 128 || (ldb & 1) || ((uintptr_t)B & 15))) { fvgp_set_error("potrs with nrhs > 8 needs nrhs % 128 == 0, even ldb, 16-byte aligned B"); return -6; }
     HIPCHK(hipSetDevice(h->device));
     const int64_t np = pad128(n);
     if (np > n) { rc = launch_copy_cols(h, B, ldb, B + n * ldb, ldb, 0, 0, np - n, nrhs); if (rc) return rc; }
     if (nrhs <= FVGP_MAX_RHS_VEC) return potrs_vec(h, L, n, ldl, B, nrhs, ldb, true);
-    if (nrhs % 128 || (ldb & 1) || ((uintptr_t)B & 15)) { fvgp_set_error("potrs with nrhs > 8 needs nrhs % 128 == 0, even ldb, 16-byte aligned B"); return -6; }
     rc = trsm_fwd_gemm(h, L, n, ldl, B, nrhs, ldb);
     if (rc) return rc;
     return trsm_bwd_gemm(h, L, n, ldl, B, nrhs, ldb);
@@ -252,11 +253,12 @@ int fvgp_hip_trsm_lower(fvgp_handle *h, const double *L, int64_t n, int64_t ldl,
     if (!B) return -5;
     if (nrhs <= 0) return -6;
     if (ldb < nrhs) return -7;
+    // refused before anything is written: the padding rows of B keep their bits
+    if (nrhs > FVGP_MAX_RHS_VEC && (nrhs % 128 || (ldb & 1) || ((uintptr_t)B & 15))) { fvgp_set_error("trsm with nrhs > 8 needs nrhs % 128 == 0, even ldb, 16-byte aligned B"); return -6; }
     HIPCHK(hipSetDevice(h->device));
     const int64_t np = pad128(n);
     if (np > n) { rc = launch_copy_cols(h, B, ldb, B + n * ldb, ldb, 0, 0, np - n, nrhs); if (rc) return rc; }
     if (nrhs <= FVGP_MAX_RHS_VEC) return potrs_vec(h, L, n, ldl, B, nrhs, ldb, false);
-    if (nrhs % 128 || (ldb & 1) || ((uintptr_t)B & 15)) { fvgp_set_error("trsm with nrhs > 8 needs nrhs % 128 == 0, even ldb, 16-byte aligned B"); return -6; }
     if (h->block_inverses && nrhs <= 1024 && np >= 2048) {
         // few columns against a long factor (the new rows of an append, gp_lin_alg.py:1310-1477; the callables' posterior): the
         // posterior's block sweep on the TRANSPOSED right-hand sides (N / 1024 steps with inverted diagonal blocks instead of
