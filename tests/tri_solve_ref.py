@@ -83,7 +83,9 @@ def factor_w(n, seed):
     return L
 
 
-def factor_g(n, seed, ell, noise):
+def covariance_g(n, seed, ell, noise):
+    """the RBF covariance exp(-|x - x'|^2 / (2 l^2)) + noise I on n uniform points of the unit square (symmetric in its bits); shared
+    with tests/chol_ref.py, whose fixtures are this matrix before it is factored"""
     rng = np.random.default_rng(seed)
     x = rng.random((n, 2))
     sq = np.sum(x * x, axis=1)
@@ -91,7 +93,11 @@ def factor_g(n, seed, ell, noise):
     K = np.exp(-r2 / (2.0 * ell * ell))
     K = 0.5 * (K + K.T)
     K[np.arange(n), np.arange(n)] = 1.0 + noise
-    return np.linalg.cholesky(K)
+    return K
+
+
+def factor_g(n, seed, ell, noise):
+    return np.linalg.cholesky(covariance_g(n, seed, ell, noise))
 
 
 def scaling_s(n, seed):
