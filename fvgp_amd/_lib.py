@@ -21,31 +21,6 @@ PAD_NONE, PAD_IDENTITY, PAD_ZERO = 0, 1, 2
 TILE = 128
 MAX_RHS_VEC = 8
 
-# every symbol include/fvgp_hip.h declares (tests check the library exports each of them)
-SYMBOLS = [
-    "fvgp_hip_version", "fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_loglik_dim", "fvgp_hip_workspace_bytes", "fvgp_hip_create",
-    "fvgp_hip_destroy", "fvgp_hip_sync", "fvgp_hip_stream_create", "fvgp_hip_stream_destroy", "fvgp_hip_set_option", "fvgp_hip_get_profile", "fvgp_hip_chain_verify_counts", "fvgp_hip_kmat",
-    "fvgp_hip_potrf", "fvgp_hip_potrf_dev", "fvgp_hip_potrs", "fvgp_hip_logdet", "fvgp_hip_potri", "fvgp_hip_trsm_lower",
-    "fvgp_hip_loglik", "fvgp_hip_loglik_grad", "fvgp_hip_grad_trace", "fvgp_hip_posterior", "fvgp_hip_gemm",
-    "fvgp_hip_mfma_selftest", "fvgp_hip_mfma_peak", "fvgp_hip_symmetrize", "fvgp_hip_add_lower", "fvgp_hip_trace_dot", "fvgp_hip_colsumsq", "fvgp_hip_add_matrix", "fvgp_hip_dot", "fvgp_hip_coldot",
-    "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_invalidate_factor", "fvgp_hip_trsm_lower_t", "fvgp_hip_panel_trsm", "fvgp_hip_panel_potrf_dev", "fvgp_hip_syrk_rowshard",
-    "fvgp_hip_grad_trace_cols", "fvgp_hip_comm_unique_id", "fvgp_hip_comm_init", "fvgp_hip_comm_init_callbacks", "fvgp_hip_comm_destroy", "fvgp_hip_ipc_window", "fvgp_hip_comm_init_ipc", "fvgp_hip_all_reduce",
-    "fvgp_hip_all_gather", "fvgp_hip_comm_profile", "fvgp_hip_dist_workspace", "fvgp_hip_loglik_dist", "fvgp_hip_dist_scratch", "fvgp_hip_solve_dist",
-    "fvgp_hip_posterior_dist", "fvgp_hip_grad_dist", "fvgp_hip_loglik_rows", "fvgp_hip_get_profile_ex", "fvgp_hip_comm_info", "fvgp_hip_comm_check", "fvgp_hip_posterior_prepare",
-    "fvgp_hip_loglik_batch", "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes",
-    "fvgp_hip_loglik_grad_batch", "fvgp_hip_loglik_grad_batch_workspace_bytes",
-    "fvgp_hip_posterior_batch", "fvgp_hip_posterior_batch_workspace_bytes",
-    "fvgp_hip_posterior_grad", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_potrs_cols",
-    "fvgp_hip_loo", "fvgp_hip_loo_workspace_bytes",
-    "fvgp_hip_normal_fill", "fvgp_hip_mvn_sample", "fvgp_hip_mvn_sample_workspace_bytes",
-    "fvgp_hip_select_batch", "fvgp_hip_select_workspace_bytes",
-    "fvgp_hip_loglik_hess", "fvgp_hip_loglik_hess_workspace_bytes",
-    "fvgp_hip_kmatvec", "fvgp_hip_kmatvec_workspace_bytes", "fvgp_hip_pchol", "fvgp_hip_pchol_workspace_bytes",
-    "fvgp_hip_precond_factor", "fvgp_hip_precond_workspace_bytes", "fvgp_hip_pcg", "fvgp_hip_pcg_workspace_bytes",
-    "fvgp_hip_kgrad_form", "fvgp_hip_kgrad_form_workspace_bytes", "fvgp_hip_precond_probes", "fvgp_hip_precond_apply",
-    "fvgp_hip_precond_apply_workspace_bytes", "fvgp_hip_pcg_lanczos", "fvgp_hip_pcg_lanczos_workspace_bytes",
-    "fvgp_hip_chol_update", "fvgp_hip_chol_delete", "fvgp_hip_chol_update_workspace_bytes",
-]
 MATVEC_CHUNK = 4096       # FVGP_MATVEC_CHUNK: rows of x2 per chunk sum of fvgp_hip_kmatvec
 PCG_MAX_RHS = 16          # FVGP_PCG_MAX_RHS
 PCG_MAX_RANK = 1024       # FVGP_PCG_MAX_RANK
@@ -53,59 +28,175 @@ LANCZOS_MAX_STEPS = 256   # FVGP_LANCZOS_MAX_STEPS: most CG coefficients per col
 CHOL_UPDATE_MAX_RANK = 16 # FVGP_CHOL_UPDATE_MAX_RANK: columns of W per pass of fvgp_hip_chol_update
 CHOL_UPDATE_TABLE_BYTES = 128 * CHOL_UPDATE_MAX_RANK * 2 * 8   # FVGP_CHOL_UPDATE_TABLE_BYTES: all of the workspace the update itself uses
 BATCH_MAX_DIM = 4096      # FVGP_BATCH_MAX_DIM: largest per-problem square fvgp_hip_loglik_batch takes
+# options a new Handle takes from the environment, FVGP_<KEY>=<integer> (tuning overrides, e.g. FVGP_OUTER_BLOCK=512)
+OPTION_KEYS = (
+    "schedule", "lookahead", "outer_block", "outer_block_big", "big_threshold", "inner_block", "small_tile_max", "small_tile_max_update",
+    "tile_tables", "block_inverses", "k128_kernels", "leaf_tiles", "leaf_tiles_rows", "panel_recursive", "potri_kminor", "leaf_yield",
+    "chain_yield", "lookahead_min", "posterior_halves", "posterior_block", "outer_block_small", "small_threshold", "panel_chain",
+    "panel_chain_min", "cols_split", "cols_split_rows", "bwd_sweep", "fwd_sweep", "chain_verify", "chain_wide", "wide_block",
+    "wide_block_big", "wide_threshold", "wide_inner", "wide_inner_rows", "chain_sleep_rows", "chain_single_rows", "chain_ahead",
+    "select_block", "matvec_split")
 
 
-# ---- row-sharded entry points: structures of include/fvgp_hip.h ---------------------------------------------------
-ALL_GATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
-ALL_REDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
+# ---- the C ABI as ctypes sees it: structures and signatures of include/fvgp_hip.h ------------------------------------
+# device pointers are c_void_p (callers pass _ptr(tensor) or None), host out-parameters typed POINTERs (callers pass ctypes arrays,
+# byref() or ndarray.ctypes.data_as)
+c_i, c_l, c_u, c_d = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
+c_p, c_s = ctypes.c_void_p, ctypes.c_char_p
+P_i, P_l, P_d, P_p, P_u32 = (ctypes.POINTER(t) for t in (c_i, c_l, c_d, c_p, ctypes.c_uint32))
+
+ALL_GATHER_FN = ctypes.CFUNCTYPE(c_i, c_p, c_p, c_p, c_l, c_p)
+ALL_REDUCE_FN = ctypes.CFUNCTYPE(c_i, c_p, c_p, c_l, c_p)
 
 
 class Collectives(ctypes.Structure):
-    _fields_ = [("ctx", ctypes.c_void_p), ("all_gather", ALL_GATHER_FN), ("all_reduce_sum", ALL_REDUCE_FN)]
+    _fields_ = [("ctx", c_p), ("all_gather", ALL_GATHER_FN), ("all_reduce_sum", ALL_REDUCE_FN)]
 
 
 class DistDesc(ctypes.Structure):
-    _fields_ = [("n", ctypes.c_int64), ("d", ctypes.c_int), ("ncol", ctypes.c_int), ("panel", ctypes.c_int64),
-                ("rank", ctypes.c_int), ("nranks", ctypes.c_int), ("kernel_id", ctypes.c_int),
-                ("x_all", ctypes.c_void_p), ("vdiag", ctypes.c_void_p), ("zt", ctypes.c_void_p),
-                ("A", ctypes.c_void_p), ("T", ctypes.c_void_p * 2), ("recv", ctypes.c_void_p * 2), ("Dfac", ctypes.c_void_p),
-                ("gather", ctypes.c_void_p), ("info_dev", ctypes.c_void_p), ("logdet_dev", ctypes.c_void_p),
-                ("keep_factor", ctypes.c_int), ("force_general", ctypes.c_int), ("preassembled", ctypes.c_int)]
+    _fields_ = [("n", c_l), ("d", c_i), ("ncol", c_i), ("panel", c_l), ("rank", c_i), ("nranks", c_i), ("kernel_id", c_i),
+                ("x_all", c_p), ("vdiag", c_p), ("zt", c_p), ("A", c_p), ("T", c_p * 2), ("recv", c_p * 2), ("Dfac", c_p),
+                ("gather", c_p), ("info_dev", c_p), ("logdet_dev", c_p),
+                ("keep_factor", c_i), ("force_general", c_i), ("preassembled", c_i)]
 
 
-def bind_dist(L):
-    """argument types of the row-sharded entry points on a loaded library that implements them (libfvgp_hip.so; the
-    tests bind the CPU twin of the ABI the same way)"""
-    c_i, c_l, c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
-    P_d = ctypes.POINTER(ctypes.c_double)
-    P_i = ctypes.POINTER(ctypes.c_int)
-    if hasattr(L, "fvgp_hip_comm_unique_id"):
-        L.fvgp_hip_comm_unique_id.argtypes = [c_p]
-        L.fvgp_hip_comm_init.argtypes = [c_p, c_p, c_i, c_i]
-        L.fvgp_hip_comm_profile.argtypes = [c_p, P_d]
-    if hasattr(L, "fvgp_hip_comm_info"):
-        L.fvgp_hip_comm_info.argtypes = [c_p, ctypes.POINTER(c_l)]
-        L.fvgp_hip_comm_check.argtypes = [c_p]
-        L.fvgp_hip_comm_info.restype = L.fvgp_hip_comm_check.restype = c_i
-    L.fvgp_hip_comm_init_callbacks.argtypes = [c_p, ctypes.POINTER(Collectives), c_i, c_i]
-    if hasattr(L, "fvgp_hip_ipc_window"):
-        L.fvgp_hip_ipc_window.argtypes = [c_p, c_l, c_p]
-        L.fvgp_hip_comm_init_ipc.argtypes = [c_p, c_p, ctypes.c_char_p, c_i, c_i]
-    L.fvgp_hip_comm_destroy.argtypes = [c_p]
-    L.fvgp_hip_all_reduce.argtypes = [c_p, c_p, c_l]
-    L.fvgp_hip_all_gather.argtypes = [c_p, c_p, c_p, c_l]
-    L.fvgp_hip_dist_workspace.argtypes = [ctypes.POINTER(DistDesc), ctypes.POINTER(c_l)]
-    L.fvgp_hip_loglik_dist.argtypes = [c_p, ctypes.POINTER(DistDesc), P_d, c_i, P_d, P_i]
-    L.fvgp_hip_dist_scratch.argtypes = [ctypes.POINTER(DistDesc), c_i, c_l, c_l]
-    L.fvgp_hip_dist_scratch.restype = c_l
-    L.fvgp_hip_solve_dist.argtypes = [c_p, ctypes.POINTER(DistDesc), c_p, c_p]
-    L.fvgp_hip_posterior_dist.argtypes = [c_p, ctypes.POINTER(DistDesc), P_d, c_i, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p]
-    L.fvgp_hip_grad_dist.argtypes = [c_p, ctypes.POINTER(DistDesc), P_d, c_i, c_p, c_i, c_l, P_d, c_p, c_p]
-    for s in ("fvgp_hip_solve_dist", "fvgp_hip_posterior_dist", "fvgp_hip_grad_dist", "fvgp_hip_comm_unique_id", "fvgp_hip_comm_init", "fvgp_hip_comm_profile", "fvgp_hip_comm_init_callbacks", "fvgp_hip_comm_destroy",
-              "fvgp_hip_all_reduce", "fvgp_hip_all_gather", "fvgp_hip_dist_workspace", "fvgp_hip_loglik_dist"):
-        if hasattr(L, s):
-            getattr(L, s).restype = c_i
+P_coll, P_desc = ctypes.POINTER(Collectives), ctypes.POINTER(DistDesc)
+_PCG_ARGS = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_i, c_d, c_i, c_i, c_i,
+             c_p, c_l, P_i, P_d, P_i]
+
+# name -> (restype, [argtypes]) for every prototype of include/fvgp_hip.h, in the header's order under its section comments
+# (tests/test_host_logic.py::test_abi_table_matches_header parses the header and holds this table to it)
+_ABI = {
+    "fvgp_hip_version": (c_i, []),
+    "fvgp_hip_last_error_string": (c_s, []),
+    "fvgp_hip_padded_dim": (c_l, [c_l]),
+    "fvgp_hip_loglik_dim": (c_l, [c_l, c_i]),
+    "fvgp_hip_workspace_bytes": (c_l, [c_l, c_l]),
+    "fvgp_hip_create": (c_i, [P_p, c_i, c_p]),
+    "fvgp_hip_destroy": (c_i, [c_p]),
+    "fvgp_hip_sync": (c_i, [c_p]),
+    "fvgp_hip_stream_create": (c_i, [P_p, c_i, c_i, P_u32, c_i]),
+    "fvgp_hip_stream_destroy": (c_i, [c_p]),
+    "fvgp_hip_set_option": (c_i, [c_p, c_s, c_l]),
+    "fvgp_hip_chain_verify_counts": (c_i, [c_p, P_l]),
+    "fvgp_hip_get_profile": (c_i, [c_p, P_d]),
+    "fvgp_hip_get_profile_ex": (c_i, [c_p, P_d]),
+    "fvgp_hip_invalidate_factor": (c_i, [c_p]),
+    # ---- covariance assembly
+    "fvgp_hip_kmat": (c_i, [c_p, c_i, c_p, c_l, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_l, c_i, c_i]),
+    # ---- dense Cholesky
+    "fvgp_hip_potrf": (c_i, [c_p, c_p, c_l, c_l, P_i]),
+    "fvgp_hip_potrf_dev": (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p]),
+    "fvgp_hip_potrs": (c_i, [c_p, c_p, c_l, c_l, c_p, c_l, c_l]),
+    "fvgp_hip_logdet": (c_i, [c_p, c_p, c_l, c_l, P_d]),
+    "fvgp_hip_potri": (c_i, [c_p, c_p, c_l, c_l, c_p, c_l]),
+    "fvgp_hip_trsm_lower": (c_i, [c_p, c_p, c_l, c_l, c_p, c_l, c_l]),
+    "fvgp_hip_trsm_lower_t": (c_i, [c_p, c_p, c_l, c_l, c_p, c_l, c_l]),
+    # ---- row-sharded (multi-GPU) building blocks: the gp2Scale partitioning pattern
+    "fvgp_hip_panel_trsm": (c_i, [c_p, c_p, c_l, c_l, c_p, c_l, c_l]),
+    # ---- row-sharded (multi-GPU) evaluation: one process per GPU, RCCL over xGMI
+    "fvgp_hip_comm_unique_id": (c_i, [c_p]),
+    "fvgp_hip_comm_init": (c_i, [c_p, c_p, c_i, c_i]),
+    "fvgp_hip_comm_init_callbacks": (c_i, [c_p, P_coll, c_i, c_i]),
+    "fvgp_hip_comm_destroy": (c_i, [c_p]),
+    "fvgp_hip_ipc_window": (c_i, [c_p, c_l, c_p]),
+    "fvgp_hip_comm_init_ipc": (c_i, [c_p, c_p, c_s, c_i, c_i]),
+    "fvgp_hip_all_reduce": (c_i, [c_p, c_p, c_l]),
+    "fvgp_hip_all_gather": (c_i, [c_p, c_p, c_p, c_l]),
+    "fvgp_hip_comm_profile": (c_i, [c_p, P_d]),
+    "fvgp_hip_comm_info": (c_i, [c_p, P_l]),
+    "fvgp_hip_comm_check": (c_i, [c_p]),
+    "fvgp_hip_dist_workspace": (c_i, [P_desc, P_l]),
+    "fvgp_hip_loglik_dist": (c_i, [c_p, P_desc, P_d, c_i, P_d, P_i]),
+    "fvgp_hip_dist_scratch": (c_l, [P_desc, c_i, c_l, c_l]),
+    "fvgp_hip_solve_dist": (c_i, [c_p, P_desc, c_p, c_p]),
+    "fvgp_hip_posterior_dist": (c_i, [c_p, P_desc, P_d, c_i, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "fvgp_hip_grad_dist": (c_i, [c_p, P_desc, P_d, c_i, c_p, c_i, c_l, P_d, c_p, c_p]),
+    "fvgp_hip_panel_potrf_dev": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p]),
+    "fvgp_hip_syrk_rowshard": (c_i, [c_p, c_l, c_l, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_i, c_i]),
+    # ---- fused evaluations
+    "fvgp_hip_loglik": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_i, c_p, c_l, c_p, P_d, P_i]),
+    "fvgp_hip_loglik_rows": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_i, c_p, c_l, c_l, c_p, P_d, P_i]),
+    "fvgp_hip_loglik_batch": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, P_d, P_i]),
+    "fvgp_hip_loglik_batch_dim": (c_l, [c_l, c_i]),
+    "fvgp_hip_loglik_batch_workspace_bytes": (c_l, [c_l, c_i, c_l]),
+    "fvgp_hip_loglik_grad_batch": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_l, c_p, c_l, c_p, c_l, c_i, c_i, c_p, c_l, c_l,
+                                         c_p, c_l, c_l, P_d, P_d, P_i, c_p, c_p]),
+    "fvgp_hip_loglik_grad_batch_workspace_bytes": (c_l, [c_l, c_i, c_l]),
+    "fvgp_hip_posterior_batch": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l,
+                                       c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_l, c_l, P_d, P_i]),
+    "fvgp_hip_posterior_batch_workspace_bytes": (c_l, [c_l, c_i, c_l, c_l]),
+    "fvgp_hip_loglik_grad": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]),
+    "fvgp_hip_loglik_hess_workspace_bytes": (c_l, [c_l, c_i]),
+    "fvgp_hip_loglik_hess": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, P_d, P_d]),
+    "fvgp_hip_grad_trace": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, P_d]),
+    "fvgp_hip_grad_trace_cols": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_l, c_l, c_p, c_l, c_p, P_d]),
+    "fvgp_hip_posterior_prepare": (c_i, [c_p, c_p, c_l, c_l]),
+    "fvgp_hip_posterior": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_l]),
+    "fvgp_hip_posterior_grad": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_i, c_p, c_l, c_i,
+                                      c_p, c_l, c_p, c_p, c_p, c_p]),
+    "fvgp_hip_posterior_grad_workspace_bytes": (c_l, [c_l, c_l, c_i]),
+    "fvgp_hip_potrs_cols": (c_i, [c_p, c_p, c_l, c_l, c_p, c_l, c_l]),
+    "fvgp_hip_loo": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, c_p, c_l,
+                           P_d, c_p, c_p, P_d, c_p, c_p]),
+    "fvgp_hip_loo_workspace_bytes": (c_l, [c_l]),
+    # ---- sampling
+    "fvgp_hip_normal_fill": (c_i, [c_p, c_u, c_u, c_l, c_l, c_p, c_l, c_l, c_l]),
+    "fvgp_hip_mvn_sample": (c_i, [c_p, c_p, c_l, c_l, c_p, c_u, c_u, c_l, c_l, c_p, c_l, c_p, c_l, c_p, c_l]),
+    "fvgp_hip_select_batch": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_d,
+                                    c_p, c_l, c_p, c_p, c_p, c_l]),
+    "fvgp_hip_select_workspace_bytes": (c_l, [c_l, c_l, c_i]),
+    "fvgp_hip_mvn_sample_workspace_bytes": (c_l, [c_l, c_l]),
+    # ---- matrix-free solves
+    "fvgp_hip_kmatvec": (c_i, [c_p, c_i, c_p, c_l, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_l]),
+    "fvgp_hip_kmatvec_workspace_bytes": (c_l, [c_l, c_l, c_i]),
+    "fvgp_hip_pchol": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_i, c_d, c_p, c_l, c_p, c_p, c_p, c_l, P_i]),
+    "fvgp_hip_pchol_workspace_bytes": (c_l, [c_l, c_i]),
+    "fvgp_hip_precond_factor": (c_i, [c_p, c_p, c_l, c_i, c_l, c_p, c_p, c_l, c_p, c_l, P_i]),
+    "fvgp_hip_precond_workspace_bytes": (c_l, [c_l, c_i]),
+    "fvgp_hip_pcg": (c_i, _PCG_ARGS),
+    "fvgp_hip_pcg_workspace_bytes": (c_l, [c_l, c_i]),
+    # ---- the stochastic log-likelihood on the matrix-free path
+    "fvgp_hip_kgrad_form": (c_i, [c_p, c_i, c_p, c_l, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_i, c_p, c_l, P_d]),
+    "fvgp_hip_kgrad_form_workspace_bytes": (c_l, [c_l, c_l]),
+    "fvgp_hip_precond_probes": (c_i, [c_p, c_u, c_u, c_l, c_p, c_l, c_i, c_l, c_p, c_p, c_l, c_i]),
+    "fvgp_hip_precond_apply": (c_i, [c_p, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_l]),
+    "fvgp_hip_precond_apply_workspace_bytes": (c_l, [c_l, c_i]),
+    "fvgp_hip_pcg_lanczos": (c_i, _PCG_ARGS + [c_i, P_d, P_d, P_i, P_d]),
+    "fvgp_hip_pcg_lanczos_workspace_bytes": (c_l, [c_l, c_i, c_i]),
+    # ---- rank-k update of a resident factor, removal of data points
+    "fvgp_hip_chol_update": (c_i, [c_p, c_p, c_l, c_l, c_p, c_l, c_l, c_l, c_p, c_l]),
+    "fvgp_hip_chol_delete": (c_i, [c_p, c_p, c_l, c_l, P_l, c_l, c_p, c_l]),
+    "fvgp_hip_chol_update_workspace_bytes": (c_l, [c_l, c_l]),
+    # ---- building blocks exported for the parity tests
+    "fvgp_hip_gemm": (c_i, [c_p, c_i, c_i, c_i, c_l, c_l, c_l, c_d, c_p, c_l, c_p, c_l, c_d, c_p, c_l]),
+    "fvgp_hip_mfma_selftest": (c_i, [c_p, c_p, c_p, c_p]),
+    "fvgp_hip_debug_tile_map": (c_l, [c_i, c_i, c_i, c_i, c_i, P_i, P_i, c_l]),
+    "fvgp_hip_debug_tile_table": (c_l, [c_i, c_i, c_i, c_i, c_i, P_i, c_l]),
+    "fvgp_hip_debug_chain_ticket": (c_i, [c_i, c_i, c_i, c_i, P_i]),
+    "fvgp_hip_mfma_peak": (c_i, [c_p, c_p, c_i, c_i]),
+    "fvgp_hip_add_lower": (c_i, [c_p, c_p, c_l, c_l, c_p, c_l, c_d]),
+    "fvgp_hip_trace_dot": (c_i, [c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_l, P_d]),
+    "fvgp_hip_dot": (c_i, [c_p, c_p, c_l, c_p, c_l, c_l, c_i, P_d]),
+    "fvgp_hip_coldot": (c_i, [c_p, c_p, c_l, c_p, c_l, c_l, c_l, c_p]),
+    "fvgp_hip_colsumsq": (c_i, [c_p, c_p, c_l, c_l, c_l, c_p]),
+    "fvgp_hip_add_matrix": (c_i, [c_p, c_p, c_l, c_p, c_l, c_l, c_l, c_d]),
+    "fvgp_hip_symmetrize": (c_i, [c_p, c_p, c_l, c_l]),
+}
+SYMBOLS = list(_ABI)      # every symbol include/fvgp_hip.h declares (tests check the library exports each of them)
+
+
+def bind(L):
+    """set restype and argtypes of every entry of _ABI that the loaded library `L` exports (libfvgp_hip.so exports all of them; the
+    tests bind the CPU twin of the ABI, which implements a subset, the same way); returns L"""
+    for name, (restype, argtypes) in _ABI.items():
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, list(argtypes)
     return L
+
+
+bind_dist = bind          # the name the row-sharded tests' CPU stand-in binds through
 
 
 class DistCalls:
@@ -174,74 +265,79 @@ def loglik_batch_dim(n, ncol=1):
     return d if d <= BATCH_MAX_DIM else 0
 
 
+def _workspace_bytes(name, *sizes):
+    """the *_workspace_bytes query `name` of the library at integer arguments"""
+    return int(getattr(lib(), name)(*map(int, sizes)))
+
+
 def posterior_batch_workspace_bytes(n, ncol, B, P_chunk):
     """device bytes the handle allocates for Handle.posterior_batch (fvgp_hip_posterior_batch_workspace_bytes); <= 0: invalid arguments"""
-    return int(lib().fvgp_hip_posterior_batch_workspace_bytes(int(n), int(ncol), int(B), int(P_chunk)))
+    return _workspace_bytes("fvgp_hip_posterior_batch_workspace_bytes", n, ncol, B, P_chunk)
 
 
 def posterior_grad_workspace_bytes(n, P, n_dirs):
     """bytes of the caller-owned scratch of Handle.posterior_grad (fvgp_hip_posterior_grad_workspace_bytes); <= 0: invalid arguments"""
-    return int(lib().fvgp_hip_posterior_grad_workspace_bytes(int(n), int(P), int(n_dirs)))
+    return _workspace_bytes("fvgp_hip_posterior_grad_workspace_bytes", n, P, n_dirs)
 
 
 def loo_workspace_bytes(n):
     """bytes of the caller-owned vector scratch of Handle.loo (fvgp_hip_loo_workspace_bytes); -1 for n < 1"""
-    return int(lib().fvgp_hip_loo_workspace_bytes(int(n)))
+    return _workspace_bytes("fvgp_hip_loo_workspace_bytes", n)
 
 
 def mvn_sample_workspace_bytes(n, nsamp):
     """bytes of the caller-owned scratch of Handle.mvn_sample (fvgp_hip_mvn_sample_workspace_bytes); -1 for n < 1 or nsamp < 1"""
-    return int(lib().fvgp_hip_mvn_sample_workspace_bytes(int(n), int(nsamp)))
+    return _workspace_bytes("fvgp_hip_mvn_sample_workspace_bytes", n, nsamp)
 
 
 def select_workspace_bytes(n, P, q):
     """bytes of the caller-owned workspace of Handle.select_batch (fvgp_hip_select_workspace_bytes); -1 for n, P or q < 1"""
-    return int(lib().fvgp_hip_select_workspace_bytes(int(n), int(P), int(q)))
+    return _workspace_bytes("fvgp_hip_select_workspace_bytes", n, P, q)
 
 
 def kmatvec_workspace_bytes(n1, n2, s):
     """bytes of the split form's scratch of Handle.kmatvec (fvgp_hip_kmatvec_workspace_bytes); -1 for n1, n2 or s < 1"""
-    return int(lib().fvgp_hip_kmatvec_workspace_bytes(int(n1), int(n2), int(s)))
+    return _workspace_bytes("fvgp_hip_kmatvec_workspace_bytes", n1, n2, s)
 
 
 def pchol_workspace_bytes(n, q):
     """bytes of the caller-owned workspace of Handle.pchol (fvgp_hip_pchol_workspace_bytes); -1 for n or q < 1"""
-    return int(lib().fvgp_hip_pchol_workspace_bytes(int(n), int(q)))
+    return _workspace_bytes("fvgp_hip_pchol_workspace_bytes", n, q)
 
 
 def precond_workspace_bytes(n, q):
     """bytes of the caller-owned workspace of Handle.precond_factor (fvgp_hip_precond_workspace_bytes); -1 for n or q < 1"""
-    return int(lib().fvgp_hip_precond_workspace_bytes(int(n), int(q)))
+    return _workspace_bytes("fvgp_hip_precond_workspace_bytes", n, q)
 
 
 def pcg_workspace_bytes(n, q):
     """bytes of the caller-owned workspace of Handle.pcg (fvgp_hip_pcg_workspace_bytes); -1 for n < 1 or q < 0"""
-    return int(lib().fvgp_hip_pcg_workspace_bytes(int(n), int(q)))
+    return _workspace_bytes("fvgp_hip_pcg_workspace_bytes", n, q)
 
 
 def pcg_lanczos_workspace_bytes(n, q, lanczos_steps):
     """bytes of the caller-owned workspace of Handle.pcg_lanczos (fvgp_hip_pcg_lanczos_workspace_bytes); -1 for bad arguments"""
-    return int(lib().fvgp_hip_pcg_lanczos_workspace_bytes(int(n), int(q), int(lanczos_steps)))
+    return _workspace_bytes("fvgp_hip_pcg_lanczos_workspace_bytes", n, q, lanczos_steps)
 
 
 def kgrad_form_workspace_bytes(n1, n2):
     """bytes of the caller-owned workspace of Handle.kgrad_form (fvgp_hip_kgrad_form_workspace_bytes); -1 for n1 or n2 < 1"""
-    return int(lib().fvgp_hip_kgrad_form_workspace_bytes(int(n1), int(n2)))
+    return _workspace_bytes("fvgp_hip_kgrad_form_workspace_bytes", n1, n2)
 
 
 def precond_apply_workspace_bytes(n, q):
     """bytes of the caller-owned workspace of Handle.precond_apply (fvgp_hip_precond_apply_workspace_bytes); -1 for n < 1 or q < 0"""
-    return int(lib().fvgp_hip_precond_apply_workspace_bytes(int(n), int(q)))
+    return _workspace_bytes("fvgp_hip_precond_apply_workspace_bytes", n, q)
 
 
 def chol_update_workspace_bytes(n, k):
     """bytes of the caller-owned workspace of Handle.chol_update / chol_delete (fvgp_hip_chol_update_workspace_bytes); -1 for n or k < 1"""
-    return int(lib().fvgp_hip_chol_update_workspace_bytes(int(n), int(k)))
+    return _workspace_bytes("fvgp_hip_chol_update_workspace_bytes", n, k)
 
 
 def loglik_hess_workspace_bytes(n, d):
     """bytes of the caller-owned scratch of Handle.loglik_hess (fvgp_hip_loglik_hess_workspace_bytes); -1 for n < 1 or d outside 1..16"""
-    return int(lib().fvgp_hip_loglik_hess_workspace_bytes(int(n), int(d)))
+    return _workspace_bytes("fvgp_hip_loglik_hess_workspace_bytes", n, d)
 
 
 def lib():
@@ -263,132 +359,11 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {e}") from e
-    c_i, c_l, c_d, c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
-    P_d = ctypes.POINTER(ctypes.c_double)
-    P_i = ctypes.POINTER(ctypes.c_int)
-    L.fvgp_hip_version.restype = c_i
-    L.fvgp_hip_last_error_string.restype = ctypes.c_char_p
-    L.fvgp_hip_padded_dim.restype = c_l
-    L.fvgp_hip_padded_dim.argtypes = [c_l]
-    L.fvgp_hip_loglik_dim.argtypes = [c_l, c_i]
-    L.fvgp_hip_loglik_dim.restype = c_l
-    L.fvgp_hip_workspace_bytes.argtypes = [c_l, c_l]
-    L.fvgp_hip_workspace_bytes.restype = c_l
-    L.fvgp_hip_create.argtypes = [ctypes.POINTER(c_p), c_i, c_p]
-    L.fvgp_hip_destroy.argtypes = [c_p]
-    L.fvgp_hip_sync.argtypes = [c_p]
-    L.fvgp_hip_stream_create.argtypes = [ctypes.POINTER(c_p), c_i, c_i, ctypes.POINTER(ctypes.c_uint32), c_i]
-    L.fvgp_hip_stream_destroy.argtypes = [c_p]
-    L.fvgp_hip_set_option.argtypes = [c_p, ctypes.c_char_p, c_l]
-    L.fvgp_hip_get_profile.argtypes = [c_p, P_d]
-    L.fvgp_hip_chain_verify_counts.argtypes = [c_p, ctypes.POINTER(ctypes.c_int64)]
-    L.fvgp_hip_invalidate_factor.argtypes = [c_p]
-    L.fvgp_hip_kmat.argtypes = [c_p, c_i, c_p, c_l, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_l, c_i, c_i]
-    L.fvgp_hip_potrf.argtypes = [c_p, c_p, c_l, c_l, P_i]
-    L.fvgp_hip_potrf_dev.argtypes = [c_p, c_p, c_l, c_l, c_l, c_p, c_p]
-    L.fvgp_hip_potrs.argtypes = [c_p, c_p, c_l, c_l, c_p, c_l, c_l]
-    L.fvgp_hip_trsm_lower.argtypes = [c_p, c_p, c_l, c_l, c_p, c_l, c_l]
-    L.fvgp_hip_logdet.argtypes = [c_p, c_p, c_l, c_l, P_d]
-    L.fvgp_hip_potri.argtypes = [c_p, c_p, c_l, c_l, c_p, c_l]
-    L.fvgp_hip_loglik.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_i, c_p, c_l, c_p, P_d, P_i]
-    L.fvgp_hip_loglik_rows.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_i, c_p, c_l, c_l, c_p, P_d, P_i]
-    L.fvgp_hip_get_profile_ex.argtypes = [c_p, P_d]
-    L.fvgp_hip_loglik_batch.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, P_d, P_i]
-    L.fvgp_hip_loglik_batch_dim.argtypes = [c_l, c_i]
-    L.fvgp_hip_loglik_batch_dim.restype = c_l
-    L.fvgp_hip_loglik_batch_workspace_bytes.argtypes = [c_l, c_i, c_l]
-    L.fvgp_hip_loglik_batch_workspace_bytes.restype = c_l
-    L.fvgp_hip_loglik_grad_batch.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_l, c_p, c_l, c_p, c_l, c_i, c_i, c_p, c_l, c_l,
-                                             c_p, c_l, c_l, P_d, P_d, P_i, c_p, c_p]
-    L.fvgp_hip_loglik_grad_batch_workspace_bytes.argtypes = [c_l, c_i, c_l]
-    L.fvgp_hip_loglik_grad_batch_workspace_bytes.restype = c_l
-    L.fvgp_hip_posterior_batch.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l,
-                                           c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_l, c_l, P_d, P_i]
-    L.fvgp_hip_posterior_batch_workspace_bytes.argtypes = [c_l, c_i, c_l, c_l]
-    L.fvgp_hip_posterior_batch_workspace_bytes.restype = c_l
-    L.fvgp_hip_posterior_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_i, c_p, c_l, c_i,
-                                          c_p, c_l, c_p, c_p, c_p, c_p]
-    L.fvgp_hip_posterior_grad_workspace_bytes.argtypes = [c_l, c_l, c_i]
-    L.fvgp_hip_posterior_grad_workspace_bytes.restype = c_l
-    L.fvgp_hip_potrs_cols.argtypes = [c_p, c_p, c_l, c_l, c_p, c_l, c_l]
-    L.fvgp_hip_loo.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, c_p, c_l,
-                               P_d, c_p, c_p, P_d, c_p, c_p]
-    L.fvgp_hip_loo_workspace_bytes.argtypes = [c_l]
-    L.fvgp_hip_loo_workspace_bytes.restype = c_l
-    c_u = ctypes.c_uint64
-    L.fvgp_hip_normal_fill.argtypes = [c_p, c_u, c_u, c_l, c_l, c_p, c_l, c_l, c_l]
-    L.fvgp_hip_mvn_sample.argtypes = [c_p, c_p, c_l, c_l, c_p, c_u, c_u, c_l, c_l, c_p, c_l, c_p, c_l, c_p, c_l]
-    L.fvgp_hip_mvn_sample_workspace_bytes.argtypes = [c_l, c_l]
-    L.fvgp_hip_mvn_sample_workspace_bytes.restype = c_l
-    L.fvgp_hip_select_batch.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_d,
-                                        c_p, c_l, c_p, c_p, c_p, c_l]
-    L.fvgp_hip_select_workspace_bytes.argtypes = [c_l, c_l, c_i]
-    L.fvgp_hip_select_workspace_bytes.restype = c_l
-    L.fvgp_hip_kmatvec.argtypes = [c_p, c_i, c_p, c_l, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_l]
-    L.fvgp_hip_kmatvec_workspace_bytes.argtypes = [c_l, c_l, c_i]
-    L.fvgp_hip_pchol.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_i, c_d, c_p, c_l, c_p, c_p, c_p, c_l, P_i]
-    L.fvgp_hip_pchol_workspace_bytes.argtypes = [c_l, c_i]
-    L.fvgp_hip_precond_factor.argtypes = [c_p, c_p, c_l, c_i, c_l, c_p, c_p, c_l, c_p, c_l, P_i]
-    L.fvgp_hip_precond_workspace_bytes.argtypes = [c_l, c_i]
-    L.fvgp_hip_pcg.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_i,
-                               c_d, c_i, c_i, c_i, c_p, c_l, P_i, P_d, P_i]
-    L.fvgp_hip_pcg_workspace_bytes.argtypes = [c_l, c_i]
-    L.fvgp_hip_pcg_lanczos.argtypes = L.fvgp_hip_pcg.argtypes + [c_i, P_d, P_d, P_i, P_d]
-    L.fvgp_hip_pcg_lanczos_workspace_bytes.argtypes = [c_l, c_i, c_i]
-    L.fvgp_hip_kgrad_form.argtypes = [c_p, c_i, c_p, c_l, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_i, c_p, c_l, P_d]
-    L.fvgp_hip_kgrad_form_workspace_bytes.argtypes = [c_l, c_l]
-    L.fvgp_hip_precond_probes.argtypes = [c_p, c_u, c_u, c_l, c_p, c_l, c_i, c_l, c_p, c_p, c_l, c_i]
-    L.fvgp_hip_precond_apply.argtypes = [c_p, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_l]
-    L.fvgp_hip_precond_apply_workspace_bytes.argtypes = [c_l, c_i]
-    for name in ("fvgp_hip_kmatvec_workspace_bytes", "fvgp_hip_pchol_workspace_bytes", "fvgp_hip_precond_workspace_bytes",
-                 "fvgp_hip_pcg_workspace_bytes", "fvgp_hip_pcg_lanczos_workspace_bytes", "fvgp_hip_kgrad_form_workspace_bytes",
-                 "fvgp_hip_precond_apply_workspace_bytes"):
-        getattr(L, name).restype = c_l
-    L.fvgp_hip_chol_update.argtypes = [c_p, c_p, c_l, c_l, c_p, c_l, c_l, c_l, c_p, c_l]
-    L.fvgp_hip_chol_delete.argtypes = [c_p, c_p, c_l, c_l, ctypes.POINTER(c_l), c_l, c_p, c_l]
-    L.fvgp_hip_chol_update_workspace_bytes.argtypes = [c_l, c_l]
-    L.fvgp_hip_chol_update_workspace_bytes.restype = c_l
-    L.fvgp_hip_loglik_grad.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, P_d]
-    L.fvgp_hip_loglik_hess.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_i, c_i, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, P_d, P_d]
-    L.fvgp_hip_loglik_hess_workspace_bytes.argtypes = [c_l, c_i]
-    L.fvgp_hip_loglik_hess_workspace_bytes.restype = c_l
-    L.fvgp_hip_grad_trace.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_l, c_p, P_d]
-    L.fvgp_hip_posterior.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_p, c_i, c_p, c_l,
-                                     c_p, c_l, c_p, c_p, c_p, c_l]
-    L.fvgp_hip_posterior_prepare.argtypes = [c_p, c_p, c_l, c_l]
-    L.fvgp_hip_gemm.argtypes = [c_p, c_i, c_i, c_i, c_l, c_l, c_l, c_d, c_p, c_l, c_p, c_l, c_d, c_p, c_l]
-    L.fvgp_hip_mfma_selftest.argtypes = [c_p, c_p, c_p, c_p]
-    L.fvgp_hip_symmetrize.argtypes = [c_p, c_p, c_l, c_l]
-    L.fvgp_hip_add_lower.argtypes = [c_p, c_p, c_l, c_l, c_p, c_l, c_d]
-    L.fvgp_hip_trace_dot.argtypes = [c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_l, P_d]
-    L.fvgp_hip_colsumsq.argtypes = [c_p, c_p, c_l, c_l, c_l, c_p]
-    L.fvgp_hip_add_matrix.argtypes = [c_p, c_p, c_l, c_p, c_l, c_l, c_l, c_d]
-    L.fvgp_hip_dot.argtypes = [c_p, c_p, c_l, c_p, c_l, c_l, c_i, P_d]
-    L.fvgp_hip_coldot.argtypes = [c_p, c_p, c_l, c_p, c_l, c_l, c_l, c_p]
-    L.fvgp_hip_mfma_peak.argtypes = [c_p, c_p, c_i, c_i]
-    L.fvgp_hip_trsm_lower_t.argtypes = [c_p, c_p, c_l, c_l, c_p, c_l, c_l]
-    L.fvgp_hip_panel_trsm.argtypes = [c_p, c_p, c_l, c_l, c_p, c_l, c_l]
-    L.fvgp_hip_panel_potrf_dev.argtypes = [c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p]
-    L.fvgp_hip_syrk_rowshard.argtypes = [c_p, c_l, c_l, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_i, c_i]
-    L.fvgp_hip_debug_tile_map.argtypes = [c_i, c_i, c_i, c_i, c_i, P_i, P_i, c_l]
-    L.fvgp_hip_debug_tile_map.restype = c_l
-    L.fvgp_hip_debug_chain_ticket.argtypes = [c_i, c_i, c_i, c_i, P_i]
-    L.fvgp_hip_debug_chain_ticket.restype = c_i
-    L.fvgp_hip_debug_tile_table.argtypes = [c_i, c_i, c_i, c_i, c_i, P_i, c_l]
-    L.fvgp_hip_debug_tile_table.restype = c_l
-    L.fvgp_hip_grad_trace_cols.argtypes = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_l, c_l, c_p, c_l, c_p, P_d]
-    bind_dist(L)
-    for s in SYMBOLS:
-        if s not in ("fvgp_hip_last_error_string", "fvgp_hip_padded_dim", "fvgp_hip_debug_tile_map", "fvgp_hip_debug_tile_table", "fvgp_hip_debug_chain_ticket", "fvgp_hip_workspace_bytes", "fvgp_hip_dist_scratch",
-                     "fvgp_hip_loglik_batch_dim", "fvgp_hip_loglik_batch_workspace_bytes", "fvgp_hip_loglik_grad_batch_workspace_bytes",
-                     "fvgp_hip_posterior_batch_workspace_bytes", "fvgp_hip_posterior_grad_workspace_bytes", "fvgp_hip_loo_workspace_bytes",
-                     "fvgp_hip_mvn_sample_workspace_bytes", "fvgp_hip_select_workspace_bytes", "fvgp_hip_loglik_hess_workspace_bytes",
-                     "fvgp_hip_kmatvec_workspace_bytes", "fvgp_hip_pchol_workspace_bytes", "fvgp_hip_precond_workspace_bytes",
-                     "fvgp_hip_pcg_workspace_bytes", "fvgp_hip_pcg_lanczos_workspace_bytes", "fvgp_hip_kgrad_form_workspace_bytes",
-                     "fvgp_hip_precond_apply_workspace_bytes", "fvgp_hip_chol_update_workspace_bytes"):
-            getattr(L, s).restype = c_i
-    _lib = L
-    return L
+    missing = [s for s in _ABI if not hasattr(L, s)]
+    if missing:
+        raise HipExtensionError(f"{LIB_PATH} does not export {', '.join(missing)}: not a build of this ABI")
+    _lib = bind(L)
+    return _lib
 
 
 def _check(rc, what):
@@ -399,12 +374,27 @@ def _check(rc, what):
 
 def _theta(theta):
     t = np.ascontiguousarray(np.asarray(theta, dtype=np.float64))
-    return t, t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(t.size)
+    return t, t.ctypes.data_as(P_d), int(t.size)
 
 
 def _ptr(t):
     """device pointer of a torch tensor (or None)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _batch_operands(who, x, thetas, vdiag, ymean):
+    """the operands the batched entries share, as Handle method `who` passes them on: thetas as a contiguous (B, ntheta) array, vdiag as
+    (1 or B, n) and ymean as (1 or B, n, ncol) with their per-problem strides in doubles (0 = one shared by every problem)"""
+    t = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+    if t.ndim != 2:
+        raise ValueError(f"{who}: thetas must be (B, ntheta)")
+    B, n = t.shape[0], x.shape[0]
+    vd = vdiag.reshape(1, n) if vdiag.dim() == 1 else vdiag
+    ym = ymean.reshape(1, *ymean.shape) if ymean.dim() == 2 else ymean
+    for name, a in (("vdiag", vd), ("ymean", ym)):
+        if a.shape[0] not in (1, B) or not a.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous with a leading dimension of 1 or B = {B}, got {tuple(a.shape)}")
+    return t, vd, n if vd.shape[0] > 1 else 0, ym, n * ym.shape[2] if ym.shape[0] > 1 else 0
 
 
 def comm_unique_id():
@@ -448,7 +438,7 @@ class Handle(DistCalls):
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         _check(lib().fvgp_hip_create(ctypes.byref(self._h), self.device, ctypes.c_void_p(stream)), "fvgp_hip_create")
-        for key in ("schedule", "lookahead", "outer_block", "outer_block_big", "big_threshold", "inner_block", "small_tile_max", "small_tile_max_update", "tile_tables", "block_inverses", "k128_kernels", "leaf_tiles", "leaf_tiles_rows", "panel_recursive", "potri_kminor", "leaf_yield", "chain_yield", "lookahead_min", "posterior_halves", "posterior_block", "outer_block_small", "small_threshold", "panel_chain", "panel_chain_min", "cols_split", "cols_split_rows", "bwd_sweep", "fwd_sweep", "chain_verify", "chain_wide", "wide_block", "wide_block_big", "wide_threshold", "wide_inner", "wide_inner_rows", "chain_sleep_rows", "chain_single_rows", "chain_ahead", "select_block", "matvec_split"):        # tuning overrides, e.g. FVGP_OUTER_BLOCK=512
+        for key in OPTION_KEYS:
             val = os.environ.get("FVGP_" + key.upper())
             if val is not None:
                 self.set_option(key, int(val))
@@ -465,6 +455,10 @@ class Handle(DistCalls):
             pass
 
     # -- helpers -------------------------------------------------------------------------------
+    def _call(self, name, *args):
+        """the ABI entry `name` on this handle; a non-zero status raises"""
+        _check(getattr(lib(), name)(self._h, *args), name)
+
     def empty(self, *shape):
         return self.torch.empty(*shape, dtype=self.torch.float64, device=f"cuda:{self.device}")
 
@@ -488,77 +482,71 @@ class Handle(DistCalls):
         return out.numpy()
 
     def sync(self):
-        _check(lib().fvgp_hip_sync(self._h), "fvgp_hip_sync")
+        self._call("fvgp_hip_sync")
 
     def set_option(self, key, value):
-        _check(lib().fvgp_hip_set_option(self._h, key.encode(), int(value)), "fvgp_hip_set_option")
+        self._call("fvgp_hip_set_option", key.encode(), int(value))
 
     def invalidate_factor(self):
         """Forget the cached diagonal-block inverses: call after writing a factor buffer by anything but potrf."""
-        _check(lib().fvgp_hip_invalidate_factor(self._h), "fvgp_hip_invalidate_factor")
+        self._call("fvgp_hip_invalidate_factor")
 
     def get_profile(self):
         out = (ctypes.c_double * 16)()
-        _check(lib().fvgp_hip_get_profile_ex(self._h, out), "fvgp_hip_get_profile_ex")
+        self._call("fvgp_hip_get_profile_ex", out)
         return {"launches": out[0], "ms": out[1], "flops": out[2], "potrf_ms": out[3],
                 "kmat_ms": out[4], "kmat_bytes": out[5], "tail_ms": out[6], "host_enqueue_ms": out[7], "bytes": out[8]}
 
     def chain_verify_counts(self):
         """(mismatches, comparisons) of the resident panel kernel's hand-off checksums since the last call (option "chain_verify")"""
         out = (ctypes.c_int64 * 2)()
-        _check(lib().fvgp_hip_chain_verify_counts(self._h, out), "fvgp_hip_chain_verify_counts")
+        self._call("fvgp_hip_chain_verify_counts", out)
         return int(out[0]), int(out[1])
 
     # -- ABI calls -----------------------------------------------------------------------------
     def kmat(self, kernel_id, x1, x2, theta, K, vdiag=None, uplo=FULL, pad=PAD_NONE):
         t, tp, nt = _theta(theta)
-        _check(lib().fvgp_hip_kmat(self._h, int(kernel_id), _ptr(x1), x1.shape[0], _ptr(x2), x2.shape[0],
-                                   x1.shape[1], tp, nt, _ptr(vdiag), _ptr(K), K.stride(0), int(uplo), int(pad)),
-               "fvgp_hip_kmat")
+        self._call("fvgp_hip_kmat", int(kernel_id), _ptr(x1), x1.shape[0], _ptr(x2), x2.shape[0],
+                   x1.shape[1], tp, nt, _ptr(vdiag), _ptr(K), K.stride(0), int(uplo), int(pad))
 
     def potrf(self, A, n):
         info = ctypes.c_int(0)
-        _check(lib().fvgp_hip_potrf(self._h, _ptr(A), int(n), A.stride(0), ctypes.byref(info)), "fvgp_hip_potrf")
+        self._call("fvgp_hip_potrf", _ptr(A), int(n), A.stride(0), ctypes.byref(info))
         return info.value
 
     def potrs(self, L, n, B, nrhs):
-        _check(lib().fvgp_hip_potrs(self._h, _ptr(L), int(n), L.stride(0), _ptr(B), int(nrhs), B.stride(0)),
-               "fvgp_hip_potrs")
+        self._call("fvgp_hip_potrs", _ptr(L), int(n), L.stride(0), _ptr(B), int(nrhs), B.stride(0))
 
     def trsm_lower(self, L, n, B, nrhs):
-        _check(lib().fvgp_hip_trsm_lower(self._h, _ptr(L), int(n), L.stride(0), _ptr(B), int(nrhs), B.stride(0)),
-               "fvgp_hip_trsm_lower")
+        self._call("fvgp_hip_trsm_lower", _ptr(L), int(n), L.stride(0), _ptr(B), int(nrhs), B.stride(0))
 
     def trsm_lower_t(self, L, n, B, nrhs):
-        _check(lib().fvgp_hip_trsm_lower_t(self._h, _ptr(L), int(n), L.stride(0), _ptr(B), int(nrhs), B.stride(0)),
-               "fvgp_hip_trsm_lower_t")
+        self._call("fvgp_hip_trsm_lower_t", _ptr(L), int(n), L.stride(0), _ptr(B), int(nrhs), B.stride(0))
 
     def panel_trsm(self, D, nd, P, rows):
-        _check(lib().fvgp_hip_panel_trsm(self._h, _ptr(D), int(nd), D.stride(0), _ptr(P), int(rows), P.stride(0)),
-               "fvgp_hip_panel_trsm")
+        self._call("fvgp_hip_panel_trsm", _ptr(D), int(nd), D.stride(0), _ptr(P), int(rows), P.stride(0))
 
     def syrk_rowshard(self, M, N, K, A, B, C, scale, off, b_ranks=1, b_blocks=0, b_off=0):
-        _check(lib().fvgp_hip_syrk_rowshard(self._h, int(M), int(N), int(K), _ptr(A), A.stride(0), _ptr(B), B.stride(0),
-                                            _ptr(C), C.stride(0), int(scale), int(off), int(b_ranks), int(b_blocks),
-                                            int(b_off)), "fvgp_hip_syrk_rowshard")
+        self._call("fvgp_hip_syrk_rowshard", int(M), int(N), int(K), _ptr(A), A.stride(0), _ptr(B), B.stride(0),
+                   _ptr(C), C.stride(0), int(scale), int(off), int(b_ranks), int(b_blocks), int(b_off))
 
     def panel_potrf_dev(self, T, w, rows, n_valid, info_dev, logdet_dev):
         """Enqueue-only factorisation of a tall panel (diagonal block on top, this rank's rows below)."""
-        _check(lib().fvgp_hip_panel_potrf_dev(self._h, _ptr(T), int(w), int(rows), T.stride(0), int(n_valid), _ptr(info_dev),
-                                              _ptr(logdet_dev) if logdet_dev is not None else None), "fvgp_hip_panel_potrf_dev")
+        self._call("fvgp_hip_panel_potrf_dev", _ptr(T), int(w), int(rows), T.stride(0), int(n_valid), _ptr(info_dev),
+                   _ptr(logdet_dev) if logdet_dev is not None else None)
 
     def potrf_dev(self, A, n, n_logdet, info_dev, logdet_dev):
         """Enqueue-only potrf: info (int32 tensor) and log-det (float64 tensor) stay on the device."""
-        _check(lib().fvgp_hip_potrf_dev(self._h, _ptr(A), int(n), A.stride(0), int(n_logdet), _ptr(info_dev),
-                                        _ptr(logdet_dev) if logdet_dev is not None else None), "fvgp_hip_potrf_dev")
+        self._call("fvgp_hip_potrf_dev", _ptr(A), int(n), A.stride(0), int(n_logdet), _ptr(info_dev),
+                   _ptr(logdet_dev) if logdet_dev is not None else None)
 
     def logdet(self, L, n):
         out = ctypes.c_double(0.0)
-        _check(lib().fvgp_hip_logdet(self._h, _ptr(L), int(n), L.stride(0), ctypes.byref(out)), "fvgp_hip_logdet")
+        self._call("fvgp_hip_logdet", _ptr(L), int(n), L.stride(0), ctypes.byref(out))
         return out.value
 
     def potri(self, L, n, work):
-        _check(lib().fvgp_hip_potri(self._h, _ptr(L), int(n), L.stride(0), _ptr(work), work.stride(0)), "fvgp_hip_potri")
+        self._call("fvgp_hip_potri", _ptr(L), int(n), L.stride(0), _ptr(work), work.stride(0))
 
     def loglik(self, kernel_id, x, theta, vdiag, ymean, KV, alpha):
         """fvgp_hip_loglik_rows: the scratch's ROWS are passed as the tensor has them (KV.shape[0]), never inferred from its stride --
@@ -571,9 +559,8 @@ class Handle(DistCalls):
             raise ValueError(f"loglik: KV must be a row-major 2-d tensor of at least {pad128(n)} x {pad128(n)}, got {tuple(KV.shape)} strides {KV.stride()}")
         # the extra block row is only claimed when the tensor owns those rows AND columns (a column slice with a wide stride does not)
         rows = KV.shape[0] if KV.shape[1] >= loglik_dim(n, ymean.shape[1]) else pad128(n)
-        _check(lib().fvgp_hip_loglik_rows(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(vdiag), _ptr(ymean),
-                                          ymean.shape[1], _ptr(KV), rows, KV.stride(0), _ptr(alpha), out, ctypes.byref(info)),
-               "fvgp_hip_loglik_rows")
+        self._call("fvgp_hip_loglik_rows", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(vdiag), _ptr(ymean),
+                   ymean.shape[1], _ptr(KV), rows, KV.stride(0), _ptr(alpha), out, ctypes.byref(info))
         return out[0], out[1], out[2], info.value
 
     def loglik_batch(self, kernel_id, x, thetas, vdiag, ymean, KV):
@@ -581,25 +568,15 @@ class Handle(DistCalls):
         vdiag (1, n) / ymean (1, n, ncol) -- or 1-d / 2-d -- are shared by every problem; (B, n) / (B, n, ncol) give each its own.
         KV: (B, dim, ld) device scratch, dim = loglik_batch_dim(n, ncol) (or any tensor whose first dimension strides the squares).
         Returns (out (B, 3) ndarray of {log-likelihood, log|KV|, quad / ncol}, NaN where the factorisation failed; info (B,) ints)."""
-        t = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
-        if t.ndim != 2:
-            raise ValueError("loglik_batch: thetas must be (B, ntheta)")
-        B, nt = t.shape
-        n, d = x.shape
-        vd = vdiag.reshape(1, n) if vdiag.dim() == 1 else vdiag
-        ym = ymean.reshape(1, *ymean.shape) if ymean.dim() == 2 else ymean
-        ncol = ym.shape[2]
-        for name, a in (("vdiag", vd), ("ymean", ym)):
-            if a.shape[0] not in (1, B) or not a.is_contiguous():
-                raise ValueError(f"loglik_batch: {name} must be contiguous with a leading dimension of 1 or B = {B}, got {tuple(a.shape)}")
+        t, vd, vd_stride, ym, ym_stride = _batch_operands("loglik_batch", x, thetas, vdiag, ymean)
+        (B, nt), (n, d), ncol = t.shape, x.shape, ym.shape[2]
         if KV.dim() != 3 or KV.stride(2) != 1 or (B > 1 and KV.shape[0] < B):
             raise ValueError(f"loglik_batch: KV must be a (B, dim, ld) tensor with unit column stride, got {tuple(KV.shape)}")
         out = np.empty((B, 3), dtype=np.float64)
         info = np.zeros(B, dtype=np.int32)
-        _check(lib().fvgp_hip_loglik_batch(self._h, int(kernel_id), _ptr(x), n, d, t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), nt, B,
-                                           _ptr(vd), n if vd.shape[0] > 1 else 0, _ptr(ym), n * ncol if ym.shape[0] > 1 else 0, ncol,
-                                           _ptr(KV), KV.stride(1), KV.stride(0), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                           info.ctypes.data_as(ctypes.POINTER(ctypes.c_int))), "fvgp_hip_loglik_batch")
+        self._call("fvgp_hip_loglik_batch", int(kernel_id), _ptr(x), n, d, t.ctypes.data_as(P_d), nt, B,
+                   _ptr(vd), vd_stride, _ptr(ym), ym_stride, ncol,
+                   _ptr(KV), KV.stride(1), KV.stride(0), out.ctypes.data_as(P_d), info.ctypes.data_as(P_i))
         return out, info
 
     def loglik_grad_batch(self, kernel_id, x, thetas, vdiag, ymean, KV, work, component=0, b_out=None, diag_out=None):
@@ -607,17 +584,8 @@ class Handle(DistCalls):
         vdiag / ymean / KV as loglik_batch; work: (B, rows, ldw) second device scratch, rows >= pad128(n).  b_out / diag_out: optional
         (B, n) device tensors for b = KV^-1 (y - m)[:, component] and diag(KV^-1).  Returns (out (B, 3), grad (B, ntheta), info (B,)):
         NaN rows where the factorisation failed."""
-        t = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
-        if t.ndim != 2:
-            raise ValueError("loglik_grad_batch: thetas must be (B, ntheta)")
-        B, nt = t.shape
-        n, d = x.shape
-        vd = vdiag.reshape(1, n) if vdiag.dim() == 1 else vdiag
-        ym = ymean.reshape(1, *ymean.shape) if ymean.dim() == 2 else ymean
-        ncol = ym.shape[2]
-        for name, a in (("vdiag", vd), ("ymean", ym)):
-            if a.shape[0] not in (1, B) or not a.is_contiguous():
-                raise ValueError(f"loglik_grad_batch: {name} must be contiguous with a leading dimension of 1 or B = {B}, got {tuple(a.shape)}")
+        t, vd, vd_stride, ym, ym_stride = _batch_operands("loglik_grad_batch", x, thetas, vdiag, ymean)
+        (B, nt), (n, d), ncol = t.shape, x.shape, ym.shape[2]
         for name, a in (("KV", KV), ("work", work)):
             if a.dim() != 3 or a.stride(2) != 1 or (B > 1 and a.shape[0] < B):
                 raise ValueError(f"loglik_grad_batch: {name} must be a (B, rows, ld) tensor with unit column stride, got {tuple(a.shape)}")
@@ -627,12 +595,11 @@ class Handle(DistCalls):
         out = np.empty((B, 3), dtype=np.float64)
         grad = np.empty((B, nt), dtype=np.float64)
         info = np.zeros(B, dtype=np.int32)
-        dp = ctypes.POINTER(ctypes.c_double)
-        _check(lib().fvgp_hip_loglik_grad_batch(self._h, int(kernel_id), _ptr(x), n, d, t.ctypes.data_as(dp), nt, B,
-                                                _ptr(vd), n if vd.shape[0] > 1 else 0, _ptr(ym), n * ncol if ym.shape[0] > 1 else 0, ncol,
-                                                int(component), _ptr(KV), KV.stride(1), KV.stride(0), _ptr(work), work.stride(1), work.stride(0),
-                                                out.ctypes.data_as(dp), grad.ctypes.data_as(dp), info.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                _ptr(b_out), _ptr(diag_out)), "fvgp_hip_loglik_grad_batch")
+        self._call("fvgp_hip_loglik_grad_batch", int(kernel_id), _ptr(x), n, d, t.ctypes.data_as(P_d), nt, B,
+                   _ptr(vd), vd_stride, _ptr(ym), ym_stride, ncol,
+                   int(component), _ptr(KV), KV.stride(1), KV.stride(0), _ptr(work), work.stride(1), work.stride(0),
+                   out.ctypes.data_as(P_d), grad.ctypes.data_as(P_d), info.ctypes.data_as(P_i),
+                   _ptr(b_out), _ptr(diag_out))
         return out, grad, info
 
     def posterior_batch(self, kernel_id, x, thetas, vdiag, ymean, xpred, KV, mean_out, var_out=None, S_out=None, want_loglik=False):
@@ -642,17 +609,8 @@ class Handle(DistCalls):
         (B, >= pad128(P), lds) or None: device tensors that receive V^T z (no prior mean), the unclipped variance and the full symmetric
         covariance (S_out needs P <= P_chunk).  Returns (out, info): out the (B, 3) array loglik_batch returns (None unless want_loglik),
         info (B,) ints; rows with info > 0 hold NaN."""
-        t = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
-        if t.ndim != 2:
-            raise ValueError("posterior_batch: thetas must be (B, ntheta)")
-        B, nt = t.shape
-        n, d = x.shape
-        vd = vdiag.reshape(1, n) if vdiag.dim() == 1 else vdiag
-        ym = ymean.reshape(1, *ymean.shape) if ymean.dim() == 2 else ymean
-        ncol = ym.shape[2]
-        for name, a in (("vdiag", vd), ("ymean", ym)):
-            if a.shape[0] not in (1, B) or not a.is_contiguous():
-                raise ValueError(f"posterior_batch: {name} must be contiguous with a leading dimension of 1 or B = {B}, got {tuple(a.shape)}")
+        t, vd, vd_stride, ym, ym_stride = _batch_operands("posterior_batch", x, thetas, vdiag, ymean)
+        (B, nt), (n, d), ncol = t.shape, x.shape, ym.shape[2]
         if xpred.dim() != 2 or xpred.shape[1] != d or not xpred.is_contiguous():
             raise ValueError(f"posterior_batch: xpred must be a contiguous (P, {d}) tensor, got {tuple(xpred.shape)}")
         P = xpred.shape[0]
@@ -666,23 +624,20 @@ class Handle(DistCalls):
             raise ValueError(f"posterior_batch: S_out must be a (B, >= {pad128(P)}, lds) tensor with unit column stride, got {tuple(S_out.shape)}")
         out = np.empty((B, 3), dtype=np.float64) if want_loglik else None
         info = np.zeros(B, dtype=np.int32)
-        dp = ctypes.POINTER(ctypes.c_double)
-        _check(lib().fvgp_hip_posterior_batch(self._h, int(kernel_id), _ptr(x), n, d, t.ctypes.data_as(dp), nt, B,
-                                              _ptr(vd), n if vd.shape[0] > 1 else 0, _ptr(ym), n * ncol if ym.shape[0] > 1 else 0, ncol,
-                                              _ptr(xpred), P, _ptr(KV), KV.shape[1], KV.stride(1), KV.stride(0),
-                                              _ptr(mean_out), _ptr(var_out), _ptr(S_out),
-                                              0 if S_out is None else S_out.stride(1), 0 if S_out is None else S_out.stride(0),
-                                              None if out is None else out.ctypes.data_as(dp), info.ctypes.data_as(ctypes.POINTER(ctypes.c_int))),
-               "fvgp_hip_posterior_batch")
+        self._call("fvgp_hip_posterior_batch", int(kernel_id), _ptr(x), n, d, t.ctypes.data_as(P_d), nt, B,
+                   _ptr(vd), vd_stride, _ptr(ym), ym_stride, ncol,
+                   _ptr(xpred), P, _ptr(KV), KV.shape[1], KV.stride(1), KV.stride(0),
+                   _ptr(mean_out), _ptr(var_out), _ptr(S_out),
+                   0 if S_out is None else S_out.stride(1), 0 if S_out is None else S_out.stride(0),
+                   None if out is None else out.ctypes.data_as(P_d), info.ctypes.data_as(P_i))
         return out, info
 
     def loglik_grad(self, kernel_id, x, theta, alpha, ncol, component, KV, work):
         t, tp, nt = _theta(theta)
         g = (ctypes.c_double * nt)()
         n, d = x.shape
-        _check(lib().fvgp_hip_loglik_grad(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(alpha), int(ncol),
-                                          int(component), _ptr(KV), KV.stride(0), _ptr(work), work.stride(0), g),
-               "fvgp_hip_loglik_grad")
+        self._call("fvgp_hip_loglik_grad", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(alpha), int(ncol),
+                   int(component), _ptr(KV), KV.stride(0), _ptr(work), work.stride(0), g)
         return np.array(g[:], dtype=np.float64)
 
     def loglik_hess(self, kernel_id, x, theta, alpha, ncol, component, KV, work, work2, ws):
@@ -695,9 +650,9 @@ class Handle(DistCalls):
         nk = 2 if int(kernel_id) in _ISO_IDS else d + 1
         g = (ctypes.c_double * nt)()
         hs = (ctypes.c_double * (nk * nk))()
-        _check(lib().fvgp_hip_loglik_hess(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(alpha), int(ncol), int(component),
-                                          _ptr(KV), KV.stride(0), _ptr(work), work.stride(0), _ptr(work2), work2.stride(0),
-                                          _ptr(ws), ws.numel() * ws.element_size(), g, hs), "fvgp_hip_loglik_hess")
+        self._call("fvgp_hip_loglik_hess", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(alpha), int(ncol), int(component),
+                   _ptr(KV), KV.stride(0), _ptr(work), work.stride(0), _ptr(work2), work2.stride(0),
+                   _ptr(ws), ws.numel() * ws.element_size(), g, hs)
         return np.array(g[:], dtype=np.float64), np.array(hs[:], dtype=np.float64).reshape(nk, nk)
 
     def grad_trace(self, kernel_id, x, theta, W, b, partial):
@@ -707,8 +662,8 @@ class Handle(DistCalls):
         t, tp, nt = _theta(theta)
         g = (ctypes.c_double * nt)()
         n, d = x.shape
-        _check(lib().fvgp_hip_grad_trace(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(W), W.stride(0),
-                                         _ptr(b), 1 if b is None else b.stride(0), _ptr(partial), g), "fvgp_hip_grad_trace")
+        self._call("fvgp_hip_grad_trace", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(W), W.stride(0),
+                   _ptr(b), 1 if b is None else b.stride(0), _ptr(partial), g)
         return np.array(g[:], dtype=np.float64)
 
     def grad_trace_cols(self, kernel_id, x, theta, W, col0, ncols, b, partial):
@@ -717,39 +672,39 @@ class Handle(DistCalls):
         t, tp, nt = _theta(theta)
         g = (ctypes.c_double * nt)()
         n, d = x.shape
-        _check(lib().fvgp_hip_grad_trace_cols(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(W), W.stride(0), int(col0), int(ncols),
-                                              _ptr(b), 1 if b is None else b.stride(0), _ptr(partial), g), "fvgp_hip_grad_trace_cols")
+        self._call("fvgp_hip_grad_trace_cols", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(W), W.stride(0), int(col0), int(ncols),
+                   _ptr(b), 1 if b is None else b.stride(0), _ptr(partial), g)
         return np.array(g[:], dtype=np.float64)
 
     # -- row-sharded evaluation (include/fvgp_hip.h: fvgp_hip_comm_* / fvgp_hip_loglik_dist) ---------------------------
     def comm_init(self, unique_id, rank, nranks):
         """bind RCCL: unique_id = the 128 bytes of comm_unique_id() on rank 0, handed to every rank by the caller"""
         buf = ctypes.create_string_buffer(bytes(unique_id), 128)
-        _check(lib().fvgp_hip_comm_init(self._h, buf, int(rank), int(nranks)), "fvgp_hip_comm_init")
+        self._call("fvgp_hip_comm_init", buf, int(rank), int(nranks))
 
     def comm_init_callbacks(self, coll, rank, nranks):
         self._coll = coll                                          # the callbacks must outlive the handle's use of them
-        _check(lib().fvgp_hip_comm_init_callbacks(self._h, ctypes.byref(coll), int(rank), int(nranks)), "fvgp_hip_comm_init_callbacks")
+        self._call("fvgp_hip_comm_init_callbacks", ctypes.byref(coll), int(rank), int(nranks))
 
     def ipc_window(self, window_bytes):
         """allocate this rank's window of the direct (IPC) collectives; returns its 64-byte handle"""
         buf = ctypes.create_string_buffer(64)
-        _check(lib().fvgp_hip_ipc_window(self._h, int(window_bytes), buf), "fvgp_hip_ipc_window")
+        self._call("fvgp_hip_ipc_window", int(window_bytes), buf)
         return buf.raw
 
     def comm_init_ipc(self, all_handles, shm_name, rank, nranks):
         """bind the direct collectives: all_handles = the ranks' 64-byte window handles in rank order"""
         blob = ctypes.create_string_buffer(b"".join(bytes(hd) for hd in all_handles), 64 * int(nranks))
-        _check(lib().fvgp_hip_comm_init_ipc(self._h, blob, shm_name.encode(), int(rank), int(nranks)), "fvgp_hip_comm_init_ipc")
+        self._call("fvgp_hip_comm_init_ipc", blob, shm_name.encode(), int(rank), int(nranks))
 
     def comm_destroy(self):
-        _check(lib().fvgp_hip_comm_destroy(self._h), "fvgp_hip_comm_destroy")
+        self._call("fvgp_hip_comm_destroy")
 
     def all_reduce(self, t):
-        _check(lib().fvgp_hip_all_reduce(self._h, _ptr(t), t.numel()), "fvgp_hip_all_reduce")
+        self._call("fvgp_hip_all_reduce", _ptr(t), t.numel())
 
     def all_gather(self, send, recv):
-        _check(lib().fvgp_hip_all_gather(self._h, _ptr(send), _ptr(recv), send.numel()), "fvgp_hip_all_gather")
+        self._call("fvgp_hip_all_gather", _ptr(send), _ptr(recv), send.numel())
 
     def _dist_lib(self):
         return lib()
@@ -761,18 +716,18 @@ class Handle(DistCalls):
     def comm_info(self):
         """the handle's communicator as it reports itself (fvgp_hip_comm_info)"""
         out = (ctypes.c_int64 * 8)()
-        _check(lib().fvgp_hip_comm_info(self._h, out), "fvgp_hip_comm_info")
+        self._call("fvgp_hip_comm_info", out)
         info = {"kind": {0: "none", 1: "rccl", 2: "ipc", 3: "callbacks"}[int(out[0])], "nranks_bound": int(out[1]), "rank_bound": int(out[2])}
         if out[0] == 1:
             info.update(nccl_comm_count=int(out[3]), nccl_comm_user_rank=int(out[4]), nccl_comm_cu_device=int(out[5]), rccl_version=int(out[6]))
         return info
 
     def comm_check(self):
-        _check(lib().fvgp_hip_comm_check(self._h), "fvgp_hip_comm_check")
+        self._call("fvgp_hip_comm_check")
 
     def comm_profile(self):
         out = (ctypes.c_double * 6)()
-        _check(lib().fvgp_hip_comm_profile(self._h, out), "fvgp_hip_comm_profile")
+        self._call("fvgp_hip_comm_profile", out)
         return {"all_gather": (int(out[0]), out[2], out[4]), "all_reduce": (int(out[1]), out[3], out[5])}
 
     def dist_workspace(self, desc):
@@ -784,16 +739,15 @@ class Handle(DistCalls):
         t, tp, nt = _theta(theta)
         out = (ctypes.c_double * 3)()
         info = ctypes.c_int(0)
-        _check(lib().fvgp_hip_loglik_dist(self._h, ctypes.byref(desc), tp, nt, out, ctypes.byref(info)), "fvgp_hip_loglik_dist")
+        self._call("fvgp_hip_loglik_dist", ctypes.byref(desc), tp, nt, out, ctypes.byref(info))
         return out[0], out[1], out[2], info.value
 
     def posterior(self, kernel_id, x, theta, L, alpha, ncol, xpred, kx, mean_out=None, var_out=None, S_out=None):
         t, tp, nt = _theta(theta)
         n, d = x.shape
-        _check(lib().fvgp_hip_posterior(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(L), L.stride(0),
-                                        _ptr(alpha), int(ncol), _ptr(xpred), xpred.shape[0], _ptr(kx), kx.stride(0),
-                                        _ptr(mean_out), _ptr(var_out), _ptr(S_out),
-                                        0 if S_out is None else S_out.stride(0)), "fvgp_hip_posterior")
+        self._call("fvgp_hip_posterior", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(L), L.stride(0),
+                   _ptr(alpha), int(ncol), _ptr(xpred), xpred.shape[0], _ptr(kx), kx.stride(0),
+                   _ptr(mean_out), _ptr(var_out), _ptr(S_out), 0 if S_out is None else S_out.stride(0))
 
     def posterior_grad(self, kernel_id, x, theta, xpred, alpha, ncol, component, W, n_dirs, work, A_out, q_out, dm_out, dv_out):
         """fvgp_hip_posterior_grad: A = k^T alpha[:, component], q = sum_i k_i W_i and their exact derivatives dm, dv (P, n_dirs) in the
@@ -801,10 +755,10 @@ class Handle(DistCalls):
         work: a tensor of at least posterior_grad_workspace_bytes(n, P, n_dirs) bytes.  Asynchronous."""
         t, tp, nt = _theta(theta)
         n, d = x.shape
-        _check(lib().fvgp_hip_posterior_grad(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(xpred), xpred.shape[0],
-                                             _ptr(alpha), int(ncol), int(component), _ptr(W), 0 if W is None else W.stride(0),
-                                             int(n_dirs), _ptr(work), work.numel() * work.element_size(),
-                                             _ptr(A_out), _ptr(q_out), _ptr(dm_out), _ptr(dv_out)), "fvgp_hip_posterior_grad")
+        self._call("fvgp_hip_posterior_grad", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(xpred), xpred.shape[0],
+                   _ptr(alpha), int(ncol), int(component), _ptr(W), 0 if W is None else W.stride(0),
+                   int(n_dirs), _ptr(work), work.numel() * work.element_size(),
+                   _ptr(A_out), _ptr(q_out), _ptr(dm_out), _ptr(dv_out))
 
     def loo(self, kernel_id, x, theta, alpha, ncol, component, KV, work, ws, resid_out, var_out, u_out=None, mdiag_out=None, n=None):
         """fvgp_hip_loo on the factor in KV (destroyed, as `work`): returns (out, grad) with out = [L_LOO, sum resid^2, sum log q_i,
@@ -820,17 +774,16 @@ class Handle(DistCalls):
             tp, nt, g, d = None, 0, None, 0 if x is None else x.shape[1]
             n = int(x.shape[0] if n is None else n)
         out = (ctypes.c_double * 4)()
-        _check(lib().fvgp_hip_loo(self._h, int(kernel_id or 0), _ptr(x), n, d, tp, nt, _ptr(alpha), int(ncol), int(component),
-                                  _ptr(KV), KV.stride(0), _ptr(work), work.stride(0), _ptr(ws), ws.numel() * ws.element_size(),
-                                  out, _ptr(resid_out), _ptr(var_out), g, _ptr(u_out), _ptr(mdiag_out)), "fvgp_hip_loo")
+        self._call("fvgp_hip_loo", int(kernel_id or 0), _ptr(x), n, d, tp, nt, _ptr(alpha), int(ncol), int(component),
+                   _ptr(KV), KV.stride(0), _ptr(work), work.stride(0), _ptr(ws), ws.numel() * ws.element_size(),
+                   out, _ptr(resid_out), _ptr(var_out), g, _ptr(u_out), _ptr(mdiag_out))
         return np.array(out[:], dtype=np.float64), (None if g is None else np.array(g[:], dtype=np.float64))
 
     def normal_fill(self, Z, seed=0, stream=0, row0=0, col0=0):
         """fvgp_hip_normal_fill: Z[r][c] = z(seed, stream, row0 + r, col0 + c) over the whole 2-d device tensor Z (a view with a
         larger row stride is fine: only its rows x cols entries are written).  Asynchronous."""
         assert Z.dim() == 2 and Z.stride(1) == 1, "Z must be a 2-d tensor with contiguous rows"
-        _check(lib().fvgp_hip_normal_fill(self._h, int(seed), int(stream), int(row0), int(col0), _ptr(Z), Z.shape[0], Z.shape[1],
-                                          Z.stride(0)), "fvgp_hip_normal_fill")
+        self._call("fvgp_hip_normal_fill", int(seed), int(stream), int(row0), int(col0), _ptr(Z), Z.shape[0], Z.shape[1], Z.stride(0))
 
     def mvn_sample(self, L, n, Y, mean=None, seed=0, stream=0, samp0=0, Z_out=None, work=None):
         """fvgp_hip_mvn_sample: Y[s] = mean + tril(L) z(seed, stream, :, samp0 + s) for the Y.shape[0] rows of the device tensor Y
@@ -840,9 +793,9 @@ class Handle(DistCalls):
         nsamp = int(Y.shape[0])
         if work is None:
             work = self.empty(max(1, mvn_sample_workspace_bytes(n, nsamp)) // 8)
-        _check(lib().fvgp_hip_mvn_sample(self._h, _ptr(L), int(n), L.stride(0), _ptr(mean), int(seed), int(stream), int(samp0), nsamp,
-                                         _ptr(Y), Y.stride(0), _ptr(Z_out), 0 if Z_out is None else Z_out.stride(0),
-                                         _ptr(work), work.numel() * 8), "fvgp_hip_mvn_sample")
+        self._call("fvgp_hip_mvn_sample", _ptr(L), int(n), L.stride(0), _ptr(mean), int(seed), int(stream), int(samp0), nsamp,
+                   _ptr(Y), Y.stride(0), _ptr(Z_out), 0 if Z_out is None else Z_out.stride(0),
+                   _ptr(work), work.numel() * 8)
 
     def select_batch(self, kernel_id, x, theta, L, xcand, var, q, idx_out, pick_var_out, noise=None, criterion=0, allow_repeats=False,
                      tol=1e-12, G_out=None, work=None):
@@ -856,10 +809,10 @@ class Handle(DistCalls):
         P = int(xcand.shape[0])
         if work is None:
             work = self.empty(max(1, select_workspace_bytes(n, P, q)) // 8)
-        _check(lib().fvgp_hip_select_batch(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(L), L.stride(0), _ptr(xcand), P,
-                                           _ptr(noise), _ptr(var), int(q), int(criterion), int(bool(allow_repeats)), float(tol),
-                                           _ptr(work), work.numel() * 8, _ptr(idx_out), _ptr(pick_var_out), _ptr(G_out),
-                                           0 if G_out is None else G_out.stride(0)), "fvgp_hip_select_batch")
+        self._call("fvgp_hip_select_batch", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(L), L.stride(0), _ptr(xcand), P,
+                   _ptr(noise), _ptr(var), int(q), int(criterion), int(bool(allow_repeats)), float(tol),
+                   _ptr(work), work.numel() * 8, _ptr(idx_out), _ptr(pick_var_out), _ptr(G_out),
+                   0 if G_out is None else G_out.stride(0))
 
     def kmatvec(self, kernel_id, x1, x2, theta, B, Y, vdiag=None, s=None, work=None):
         """fvgp_hip_kmatvec: Y[:, :s] = K(x1, x2) B[:, :s] + diag(vdiag) B[:, :s] without K.  B (n2, >= s), Y (n1, >= s) device
@@ -867,9 +820,9 @@ class Handle(DistCalls):
         (kmatvec_workspace_bytes).  Asynchronous."""
         t, tp, nt = _theta(theta)
         s = int(B.shape[1] if s is None else s)
-        _check(lib().fvgp_hip_kmatvec(self._h, int(kernel_id), _ptr(x1), x1.shape[0], _ptr(x2), x2.shape[0], x1.shape[1], tp, nt,
-                                      _ptr(vdiag), _ptr(B), B.stride(0), s, _ptr(Y), Y.stride(0), _ptr(work),
-                                      0 if work is None else work.numel() * 8), "fvgp_hip_kmatvec")
+        self._call("fvgp_hip_kmatvec", int(kernel_id), _ptr(x1), x1.shape[0], _ptr(x2), x2.shape[0], x1.shape[1], tp, nt,
+                   _ptr(vdiag), _ptr(B), B.stride(0), s, _ptr(Y), Y.stride(0), _ptr(work),
+                   0 if work is None else work.numel() * 8)
 
     def pchol(self, kernel_id, x, theta, q, G, piv_out, tol=0.0, resid_diag_out=None, work=None):
         """fvgp_hip_pchol: the greedy pivoted Cholesky of K(x, x), rank <= q, into G (q, >= n); piv_out an int64 device (q,) tensor
@@ -879,9 +832,8 @@ class Handle(DistCalls):
         if work is None:
             work = self.empty(max(1, pchol_workspace_bytes(n, q)) // 8)
         rank = ctypes.c_int(0)
-        _check(lib().fvgp_hip_pchol(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, int(q), float(tol), _ptr(G), G.stride(0),
-                                    _ptr(piv_out), _ptr(resid_diag_out), _ptr(work), work.numel() * 8, ctypes.byref(rank)),
-               "fvgp_hip_pchol")
+        self._call("fvgp_hip_pchol", int(kernel_id), _ptr(x), n, d, tp, nt, int(q), float(tol), _ptr(G), G.stride(0),
+                   _ptr(piv_out), _ptr(resid_diag_out), _ptr(work), work.numel() * 8, ctypes.byref(rank))
         return int(rank.value)
 
     def precond_factor(self, G, q, n, vdiag, C, work=None):
@@ -889,8 +841,8 @@ class Handle(DistCalls):
         if work is None:
             work = self.empty(max(1, precond_workspace_bytes(n, q)) // 8)
         info = ctypes.c_int(0)
-        _check(lib().fvgp_hip_precond_factor(self._h, _ptr(G), G.stride(0), int(q), int(n), _ptr(vdiag), _ptr(C), C.stride(0),
-                                             _ptr(work), work.numel() * 8, ctypes.byref(info)), "fvgp_hip_precond_factor")
+        self._call("fvgp_hip_precond_factor", _ptr(G), G.stride(0), int(q), int(n), _ptr(vdiag), _ptr(C), C.stride(0),
+                   _ptr(work), work.numel() * 8, ctypes.byref(info))
         return int(info.value)
 
     def pcg(self, kernel_id, x, theta, vdiag, B, X, G=None, q=0, C=None, s=None, warm=False, tol=1e-10, max_iter=1000, check_every=8,
@@ -907,13 +859,11 @@ class Handle(DistCalls):
         iters = np.zeros(max(s, 1), dtype=np.int32)
         status = np.zeros(max(s, 1), dtype=np.int32)
         relres = np.zeros(max(s, 1), dtype=np.float64)
-        _check(lib().fvgp_hip_pcg(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(vdiag), _ptr(G),
-                                  0 if G is None else G.stride(0), q, _ptr(C), 0 if C is None else C.stride(0),
-                                  _ptr(B), B.stride(0), s, _ptr(X), X.stride(0), int(bool(warm)), float(tol), int(max_iter),
-                                  int(check_every), int(max_restarts), _ptr(work), work.numel() * 8,
-                                  iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                  relres.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                  status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))), "fvgp_hip_pcg")
+        self._call("fvgp_hip_pcg", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(vdiag), _ptr(G),
+                   0 if G is None else G.stride(0), q, _ptr(C), 0 if C is None else C.stride(0),
+                   _ptr(B), B.stride(0), s, _ptr(X), X.stride(0), int(bool(warm)), float(tol), int(max_iter),
+                   int(check_every), int(max_restarts), _ptr(work), work.numel() * 8,
+                   iters.ctypes.data_as(P_i), relres.ctypes.data_as(P_d), status.ctypes.data_as(P_i))
         return iters[:s], relres[:s], status[:s]
 
     def pcg_lanczos(self, kernel_id, x, theta, vdiag, B, X, lanczos_steps, G=None, q=0, C=None, s=None, warm=False, tol=1e-10,
@@ -932,14 +882,13 @@ class Handle(DistCalls):
         relres = np.zeros(max(s, 1), dtype=np.float64)
         alpha, beta = np.zeros((max(s, 1), max(L, 1))), np.zeros((max(s, 1), max(L, 1)))
         steps, rho0 = np.zeros(max(s, 1), dtype=np.int32), np.zeros(max(s, 1))
-        P_d, P_i = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
-        _check(lib().fvgp_hip_pcg_lanczos(self._h, int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(vdiag), _ptr(G),
-                                          0 if G is None else G.stride(0), q, _ptr(C), 0 if C is None else C.stride(0),
-                                          _ptr(B), B.stride(0), s, _ptr(X), X.stride(0), int(bool(warm)), float(tol), int(max_iter),
-                                          int(check_every), int(max_restarts), _ptr(work), work.numel() * 8,
-                                          iters.ctypes.data_as(P_i), relres.ctypes.data_as(P_d), status.ctypes.data_as(P_i), L,
-                                          alpha.ctypes.data_as(P_d), beta.ctypes.data_as(P_d), steps.ctypes.data_as(P_i),
-                                          rho0.ctypes.data_as(P_d)), "fvgp_hip_pcg_lanczos")
+        self._call("fvgp_hip_pcg_lanczos", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(vdiag), _ptr(G),
+                   0 if G is None else G.stride(0), q, _ptr(C), 0 if C is None else C.stride(0),
+                   _ptr(B), B.stride(0), s, _ptr(X), X.stride(0), int(bool(warm)), float(tol), int(max_iter),
+                   int(check_every), int(max_restarts), _ptr(work), work.numel() * 8,
+                   iters.ctypes.data_as(P_i), relres.ctypes.data_as(P_d), status.ctypes.data_as(P_i), L,
+                   alpha.ctypes.data_as(P_d), beta.ctypes.data_as(P_d), steps.ctypes.data_as(P_i),
+                   rho0.ctypes.data_as(P_d))
         if L == 0:
             return iters[:s], relres[:s], status[:s], alpha[:s, :0], beta[:s, :0], steps[:0], rho0[:0]
         return iters[:s], relres[:s], status[:s], alpha[:s], beta[:s], steps[:s], rho0[:s]
@@ -953,17 +902,16 @@ class Handle(DistCalls):
         if work is None:
             work = self.empty(max(1, kgrad_form_workspace_bytes(n1, n2)) // 8)
         out = np.zeros(max(nt, 1), dtype=np.float64)
-        _check(lib().fvgp_hip_kgrad_form(self._h, int(kernel_id), _ptr(x1), n1, _ptr(x2), n2, x1.shape[1], tp, nt, _ptr(U), U.stride(0),
-                                         _ptr(W), W.stride(0), s, _ptr(work), work.numel() * 8,
-                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "fvgp_hip_kgrad_form")
+        self._call("fvgp_hip_kgrad_form", int(kernel_id), _ptr(x1), n1, _ptr(x2), n2, x1.shape[1], tp, nt, _ptr(U), U.stride(0),
+                   _ptr(W), W.stride(0), s, _ptr(work), work.numel() * 8, out.ctypes.data_as(P_d))
         return out
 
     def precond_probes(self, Z, vdiag, G=None, q=0, seed=0, stream=0, col0=0):
         """fvgp_hip_precond_probes: Z[:, c] = D^1/2 z(seed, 2 stream, :, col0 + c) + G^T z(seed, 2 stream + 1, :, col0 + c) over the
         columns of the device tensor Z (n, s <= PCG_MAX_RHS): probes with covariance G^T G + D.  Asynchronous."""
         q = 0 if G is None else int(q)
-        _check(lib().fvgp_hip_precond_probes(self._h, int(seed), int(stream), int(col0), _ptr(G), 0 if G is None else G.stride(0), q,
-                                             Z.shape[0], _ptr(vdiag), _ptr(Z), Z.stride(0), Z.shape[1]), "fvgp_hip_precond_probes")
+        self._call("fvgp_hip_precond_probes", int(seed), int(stream), int(col0), _ptr(G), 0 if G is None else G.stride(0), q,
+                   Z.shape[0], _ptr(vdiag), _ptr(Z), Z.stride(0), Z.shape[1])
 
     def precond_apply(self, R, W, vdiag, G=None, q=0, C=None, s=None, work=None):
         """fvgp_hip_precond_apply: W[:, :s] = (G^T G + D)^-1 R[:, :s] with the factor C of precond_factor (G None: D^-1 R), by the
@@ -973,13 +921,13 @@ class Handle(DistCalls):
         q = 0 if G is None else int(q)
         if work is None:
             work = self.empty(max(1, precond_apply_workspace_bytes(n, q)) // 8)
-        _check(lib().fvgp_hip_precond_apply(self._h, _ptr(G), 0 if G is None else G.stride(0), q, _ptr(C),
-                                            0 if C is None else C.stride(0), n, _ptr(vdiag), _ptr(R), R.stride(0), s, _ptr(W),
-                                            W.stride(0), _ptr(work), work.numel() * 8), "fvgp_hip_precond_apply")
+        self._call("fvgp_hip_precond_apply", _ptr(G), 0 if G is None else G.stride(0), q, _ptr(C),
+                   0 if C is None else C.stride(0), n, _ptr(vdiag), _ptr(R), R.stride(0), s, _ptr(W),
+                   W.stride(0), _ptr(work), work.numel() * 8)
 
     def potrs_cols(self, L, n, B, nrhs):
         """Handle.potrs for nrhs % 128 == 0 columns whose bits do not depend on nrhs (fvgp_hip_potrs_cols)"""
-        _check(lib().fvgp_hip_potrs_cols(self._h, _ptr(L), n, L.stride(0), _ptr(B), nrhs, B.stride(0)), "fvgp_hip_potrs_cols")
+        self._call("fvgp_hip_potrs_cols", _ptr(L), n, L.stride(0), _ptr(B), nrhs, B.stride(0))
 
     def chol_update(self, L, n, W, k=None, row0=0, work=None):
         """fvgp_hip_chol_update: L <- chol(L L^T + W[:, :k] W[:, :k]^T) in place on the n leading rows; W (n, >= k) device, destroyed, its
@@ -987,8 +935,7 @@ class Handle(DistCalls):
         k = int(W.shape[1] if k is None else k)
         if work is None:
             work = self.empty(CHOL_UPDATE_TABLE_BYTES // 8)
-        _check(lib().fvgp_hip_chol_update(self._h, _ptr(L), int(n), L.stride(0), _ptr(W), k, W.stride(0), int(row0), _ptr(work),
-                                          work.numel() * 8), "fvgp_hip_chol_update")
+        self._call("fvgp_hip_chol_update", _ptr(L), int(n), L.stride(0), _ptr(W), k, W.stride(0), int(row0), _ptr(work), work.numel() * 8)
 
     def chol_delete(self, L, n, idx, work=None):
         """fvgp_hip_chol_delete: the factor of the points that remain when the strictly increasing indices `idx` (host) leave, in the same
@@ -996,52 +943,50 @@ class Handle(DistCalls):
         idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).ravel())
         if work is None:
             work = self.empty(max(1, chol_update_workspace_bytes(n, len(idx))) // 8)
-        _check(lib().fvgp_hip_chol_delete(self._h, _ptr(L), int(n), L.stride(0), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(idx),
-                                          _ptr(work), work.numel() * 8), "fvgp_hip_chol_delete")
+        self._call("fvgp_hip_chol_delete", _ptr(L), int(n), L.stride(0), idx.ctypes.data_as(P_l), len(idx),
+                   _ptr(work), work.numel() * 8)
 
     def posterior_prepare(self, L, n):
         """enqueue the inverted diagonal blocks the posterior's sweep substitutes with (fvgp_hip_posterior_prepare)"""
-        _check(lib().fvgp_hip_posterior_prepare(self._h, _ptr(L), int(n), L.stride(0)), "fvgp_hip_posterior_prepare")
+        self._call("fvgp_hip_posterior_prepare", _ptr(L), int(n), L.stride(0))
 
     def gemm(self, a_kmajor, b_nmajor, lower, M, N, K, alpha, A, B, beta, C):
-        _check(lib().fvgp_hip_gemm(self._h, int(a_kmajor), int(b_nmajor), int(lower), M, N, K, float(alpha),
-                                   _ptr(A), A.stride(0), _ptr(B), B.stride(0), float(beta), _ptr(C), C.stride(0)),
-               "fvgp_hip_gemm")
+        self._call("fvgp_hip_gemm", int(a_kmajor), int(b_nmajor), int(lower), M, N, K, float(alpha),
+                   _ptr(A), A.stride(0), _ptr(B), B.stride(0), float(beta), _ptr(C), C.stride(0))
 
     def mfma_selftest(self, A, B, D):
-        _check(lib().fvgp_hip_mfma_selftest(self._h, _ptr(A), _ptr(B), _ptr(D)), "fvgp_hip_mfma_selftest")
+        self._call("fvgp_hip_mfma_selftest", _ptr(A), _ptr(B), _ptr(D))
 
     def mfma_peak(self, out, blocks, iters):
-        _check(lib().fvgp_hip_mfma_peak(self._h, _ptr(out), int(blocks), int(iters)), "fvgp_hip_mfma_peak")
+        self._call("fvgp_hip_mfma_peak", _ptr(out), int(blocks), int(iters))
 
     def add_lower(self, A, n, B, alpha=1.0):
         """A[:n, :n] += alpha * B[:n, :n] on the lower triangle (K + V with a matrix-valued noise model)."""
-        _check(lib().fvgp_hip_add_lower(self._h, _ptr(A), int(n), A.stride(0), _ptr(B), B.stride(0), float(alpha)), "fvgp_hip_add_lower")
+        self._call("fvgp_hip_add_lower", _ptr(A), int(n), A.stride(0), _ptr(B), B.stride(0), float(alpha))
 
     def trace_dot(self, W, D, b, n):
         """sum_ij (W_ij - b_i b_j) D_ij over the full n x n arrays (W symmetric, both triangles valid); b a 1-d view or None."""
         out = ctypes.c_double(0.0)
-        _check(lib().fvgp_hip_trace_dot(self._h, _ptr(W), W.stride(0), _ptr(D), D.stride(0), _ptr(b),
-                                        1 if b is None else b.stride(0), int(n), ctypes.byref(out)), "fvgp_hip_trace_dot")
+        self._call("fvgp_hip_trace_dot", _ptr(W), W.stride(0), _ptr(D), D.stride(0), _ptr(b),
+                   1 if b is None else b.stride(0), int(n), ctypes.byref(out))
         return out.value
 
     def add_matrix(self, A, B, alpha=1.0):
         """A += alpha * B on the rectangle of B's shape"""
-        _check(lib().fvgp_hip_add_matrix(self._h, _ptr(A), A.stride(0), _ptr(B), B.stride(0), B.shape[0], B.shape[1], float(alpha)),
-               "fvgp_hip_add_matrix")
+        self._call("fvgp_hip_add_matrix", _ptr(A), A.stride(0), _ptr(B), B.stride(0), B.shape[0], B.shape[1], float(alpha))
 
     def dot(self, a, b, n):
         """sum of the elementwise products of the first n rows of two (rows, c) arrays"""
         out = ctypes.c_double(0.0)
-        _check(lib().fvgp_hip_dot(self._h, _ptr(a), a.stride(0), _ptr(b), b.stride(0), int(n), a.shape[1], ctypes.byref(out)), "fvgp_hip_dot")
+        self._call("fvgp_hip_dot", _ptr(a), a.stride(0), _ptr(b), b.stride(0), int(n), a.shape[1], ctypes.byref(out))
         return out.value
 
     def coldot(self, A, B, rows, cols, out):
-        _check(lib().fvgp_hip_coldot(self._h, _ptr(A), A.stride(0), _ptr(B), B.stride(0), int(rows), int(cols), _ptr(out)), "fvgp_hip_coldot")
+        self._call("fvgp_hip_coldot", _ptr(A), A.stride(0), _ptr(B), B.stride(0), int(rows), int(cols), _ptr(out))
 
     def colsumsq(self, V, out):
         """out[p] = sum_i V[i][p]^2 over the rows of V"""
-        _check(lib().fvgp_hip_colsumsq(self._h, _ptr(V), V.shape[0], V.stride(0), V.shape[1], _ptr(out)), "fvgp_hip_colsumsq")
+        self._call("fvgp_hip_colsumsq", _ptr(V), V.shape[0], V.stride(0), V.shape[1], _ptr(out))
 
     def symmetrize(self, A, n):
-        _check(lib().fvgp_hip_symmetrize(self._h, _ptr(A), int(n), A.stride(0)), "fvgp_hip_symmetrize")
+        self._call("fvgp_hip_symmetrize", _ptr(A), int(n), A.stride(0))

@@ -32,8 +32,6 @@ def cpu_abi():
         if not os.path.exists(path):
             subprocess.run(["make", "-C", os.path.join(ROOT, "oracle")], check=True, capture_output=True)
         _CPU = _lib.bind_dist(ctypes.CDLL(path))
-        _CPU.fvgp_hip_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p]
-        _CPU.fvgp_hip_last_error_string.restype = ctypes.c_char_p
     return _CPU
 
 

@@ -31,6 +31,147 @@ def test_header_symbols_are_exported(L):
     assert L.fvgp_hip_padded_dim(1) == 128 and L.fvgp_hip_padded_dim(128) == 128 and L.fvgp_hip_padded_dim(50000) == 50048
 
 
+_C_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "double": ctypes.c_double}
+
+
+def _c_decl(text):
+    """one C parameter or return type, identifier already removed -> its category: a scalar's name, "char*" / "<struct>*" where the
+    binding must use one given ctypes type, "*" for every other pointer"""
+    words = text.replace("*", " * ").split()
+    base = [w for w in words if w not in ("const", "*")]
+    assert len(base) == 1, f"cannot read the C type {text!r}"
+    if "*" in words:
+        return base[0] + "*" if base[0] in ("char", "fvgp_dist_desc", "fvgp_collectives") else "*"
+    assert base[0] in _C_SCALARS, f"cannot read the C type {text!r}"
+    return base[0]
+
+
+def _c_params(text):
+    """the parameter list between a prototype's parentheses -> [category]"""
+    if text.strip() == "void":
+        return []
+    out = []
+    for p in text.split(","):
+        m = re.fullmatch(r"\s*(.*?[\s*])\w+\s*", p, re.S)
+        assert m, f"cannot read the parameter {p!r}"
+        out.append(_c_decl(m.group(1)).replace("char*", "*"))              # a string is pinned to c_char_p only where it is returned
+    return out
+
+
+def _parse_header(hdr):
+    """include/fvgp_hip.h -> ({name: (return category, [parameter categories])} in the header's order,
+    {struct name: [(field, category, array length or None)]}); anything that looks like a declaration and cannot be read raises"""
+    text = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M).replace('extern "C" {', " ")
+    text = re.sub(r"\benum\s+\w+\s*\{[^}]*\}\s*;", " ", text)
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        fields = structs[name] = []
+        for decl in filter(None, (s.strip() for s in body.split(";"))):
+            fp = re.fullmatch(r"(.+?)\(\s*\*\s*(\w+)\s*\)\s*\((.*)\)", decl, re.S)
+            if fp:                                            # a function pointer: its own return type and parameters
+                fields.append((fp.group(2), (_c_decl(fp.group(1)), _c_params(fp.group(3))), None))
+                continue
+            m = re.fullmatch(r"((?:const\s+)?\w+)\s+(.+)", decl, re.S)
+            assert m, f"cannot read the field {decl!r}"
+            for item in m.group(2).split(","):
+                dm = re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[(\d+)\])?\s*", item)
+                assert dm, f"cannot read the declarator {item!r}"
+                fields.append((dm.group(2), _c_decl(m.group(1) + dm.group(1)), int(dm.group(3)) if dm.group(3) else None))
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    protos = {}
+    for stmt in filter(None, (s.strip() for s in text.split(";"))):
+        if "fvgp_hip_" not in stmt:
+            assert re.fullmatch(r"typedef\s+struct\s+\w+\s+\w+|\}", stmt), f"cannot read the statement {stmt!r}"
+            continue
+        m = re.fullmatch(r"(.+?[\s*])(fvgp_hip_\w+)\s*\((.*)\)", stmt, re.S)
+        assert m, f"cannot read the prototype {stmt!r}"
+        assert m.group(2) not in protos, f"{m.group(2)} is declared twice"
+        protos[m.group(2)] = (_c_decl(m.group(1)), _c_params(m.group(3)))
+    return protos, structs
+
+
+def _agrees(cat, ct, _lib):
+    """does the ctypes type `ct` stand for the C category `cat`?"""
+    if isinstance(cat, tuple):                               # function pointer: a CFUNCTYPE of the same signature
+        return (isinstance(ct, type) and issubclass(ct, ctypes._CFuncPtr) and _agrees(cat[0], ct._restype_, _lib)
+                and len(ct._argtypes_) == len(cat[1]) and all(_agrees(c, a, _lib) for c, a in zip(cat[1], ct._argtypes_)))
+    if cat in _C_SCALARS:
+        return ct is _C_SCALARS[cat]
+    if cat == "char*":
+        return ct is ctypes.c_char_p
+    if cat == "fvgp_dist_desc*":
+        return ct is ctypes.POINTER(_lib.DistDesc)
+    if cat == "fvgp_collectives*":
+        return ct is ctypes.POINTER(_lib.Collectives)
+    return ct in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(ct, type) and issubclass(ct, (ctypes._Pointer, ctypes._CFuncPtr)))
+
+
+def _abi_differences(protos, abi, _lib):
+    """[(name, where)] for every disagreement between the header's prototypes and a name -> (restype, [argtypes]) table:
+    where = "missing", "count", "restype" or the 0-based position of the argument"""
+    bad = []
+    for name, (ret, params) in protos.items():
+        if name not in abi:
+            bad.append((name, "missing"))
+            continue
+        restype, argtypes = abi[name]
+        if not _agrees(ret, restype, _lib):
+            bad.append((name, "restype"))
+        if len(argtypes) != len(params):
+            bad.append((name, "count"))
+            continue
+        bad += [(name, i) for i, (c, a) in enumerate(zip(params, argtypes)) if not _agrees(c, a, _lib)]
+    return bad
+
+
+def _struct_differences(fields, struct, _lib):
+    """[(field or position, why)] between a parsed typedef struct body and a ctypes.Structure"""
+    got = list(struct._fields_)
+    if [f[0] for f in fields] != [g[0] for g in got]:
+        return [("names", ([f[0] for f in fields], [g[0] for g in got]))]
+    bad = []
+    for (name, cat, count), (_, ct) in zip(fields, got):
+        if count is not None:
+            if not (issubclass(ct, ctypes.Array) and ct._length_ == count and _agrees(cat, ct._type_, _lib)):
+                bad.append((name, "array"))
+        elif not _agrees(cat, ct, _lib):
+            bad.append((name, "type"))
+    return bad
+
+
+def test_abi_table_matches_header(L):
+    """_lib._ABI against every prototype of include/fvgp_hip.h: argument count, each argument and the return type (int, int64_t,
+    uint64_t, double exactly; a pointer to a ctypes pointer type, the two structures and `const char *` to their own), the two
+    structures field by field, and what bind() left on the loaded library."""
+    from fvgp_amd import _lib
+    protos, structs = _parse_header(open(os.path.join(ROOT, "include", "fvgp_hip.h")).read())
+    assert set(protos) == set(_lib._ABI) and len(protos) == 100
+    assert list(protos) == list(_lib._ABI) == _lib.SYMBOLS, "the table is written in the header's order"
+    assert _abi_differences(protos, _lib._ABI, _lib) == []
+    # the comparison can fail: one int64_t in the middle of a 26-argument list declared as int
+    mutant = {k: (r, list(a)) for k, (r, a) in _lib._ABI.items()}
+    args = mutant["fvgp_hip_posterior_batch"][1]
+    assert len(args) == 26 and args[14] is ctypes.c_int64
+    args[14] = ctypes.c_int
+    assert _abi_differences(protos, mutant, _lib) == [("fvgp_hip_posterior_batch", 14)]
+    mutant["fvgp_hip_loglik_dim"] = (ctypes.c_int, mutant["fvgp_hip_loglik_dim"][1])
+    del mutant["fvgp_hip_loo"]
+    mutant["fvgp_hip_potrf"][1].pop()
+    assert _abi_differences(protos, mutant, _lib) == [("fvgp_hip_loglik_dim", "restype"), ("fvgp_hip_potrf", "count"),
+                                                      ("fvgp_hip_posterior_batch", 14), ("fvgp_hip_loo", "missing")]
+    assert set(structs) == {"fvgp_collectives", "fvgp_dist_desc"}
+    assert _struct_differences(structs["fvgp_dist_desc"], _lib.DistDesc, _lib) == []
+    assert _struct_differences(structs["fvgp_collectives"], _lib.Collectives, _lib) == []
+
+    class Narrow(ctypes.Structure):
+        _fields_ = [(f, ctypes.c_void_p * 3 if f == "T" else ctypes.c_int if f == "panel" else t) for f, t in _lib.DistDesc._fields_]
+    assert _struct_differences(structs["fvgp_dist_desc"], Narrow, _lib) == [("panel", "type"), ("T", "array")]
+    for name, (restype, argtypes) in _lib._ABI.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+
 def test_no_gpu_means_loud_failure():
     import torch
     if torch.cuda.is_available():
