@@ -185,14 +185,27 @@ _ABI = {
 }
 SYMBOLS = list(_ABI)      # every symbol include/fvgp_hip.h declares (tests check the library exports each of them)
 
+# the same for include/fvgp_hip_nn.h, the nearest-neighbour (Vecchia) entries (tests/test_vecchia_host.py holds this table to that header)
+_ABI_NN = {
+    "fvgp_hip_nn_search": (c_i, [c_p, c_p, c_l, c_p, c_l, c_i, P_d, c_i, c_l, c_p, c_l]),
+    "fvgp_hip_nn_conditionals": (c_i, [c_p, c_i, c_p, c_l, c_p, c_l, c_i, P_d, c_i, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p,
+                                       c_p, c_l, P_l]),
+    "fvgp_hip_nn_loglik": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_l, P_d, P_l]),
+    "fvgp_hip_nn_workspace_bytes": (c_l, [c_i, c_l, c_i]),
+}
+SYMBOLS_NN = list(_ABI_NN)
+NN_MAX_NEIGHBORS = 64     # FVGP_NN_MAX_NEIGHBORS
+NN_SEARCH, NN_CONDITIONALS, NN_LOGLIK = 0, 1, 2   # FVGP_NN_*: the call fvgp_hip_nn_workspace_bytes sizes
+
 
 def bind(L):
-    """set restype and argtypes of every entry of _ABI that the loaded library `L` exports (libfvgp_hip.so exports all of them; the
-    tests bind the CPU twin of the ABI, which implements a subset, the same way); returns L"""
-    for name, (restype, argtypes) in _ABI.items():
-        if hasattr(L, name):
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, list(argtypes)
+    """set restype and argtypes of every entry of _ABI and _ABI_NN that the loaded library `L` exports (libfvgp_hip.so exports all of
+    them; the tests bind the CPU twin of the ABI, which implements a subset, the same way); returns L"""
+    for table in (_ABI, _ABI_NN):
+        for name, (restype, argtypes) in table.items():
+            if hasattr(L, name):
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, list(argtypes)
     return L
 
 
@@ -335,6 +348,12 @@ def chol_update_workspace_bytes(n, k):
     return _workspace_bytes("fvgp_hip_chol_update_workspace_bytes", n, k)
 
 
+def nn_workspace_bytes(what, nq, B=1):
+    """bytes of the caller-owned workspace of Handle.nn_conditionals (what = NN_CONDITIONALS) / nn_loglik (NN_LOGLIK) for nq rows and B
+    hyperparameter vectors (fvgp_hip_nn_workspace_bytes; NN_SEARCH takes none: 0); -1 for bad arguments"""
+    return _workspace_bytes("fvgp_hip_nn_workspace_bytes", what, nq, B)
+
+
 def loglik_hess_workspace_bytes(n, d):
     """bytes of the caller-owned scratch of Handle.loglik_hess (fvgp_hip_loglik_hess_workspace_bytes); -1 for n < 1 or d outside 1..16"""
     return _workspace_bytes("fvgp_hip_loglik_hess_workspace_bytes", n, d)
@@ -359,7 +378,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise HipExtensionError(f"cannot load {LIB_PATH}: {e}") from e
-    missing = [s for s in _ABI if not hasattr(L, s)]
+    missing = [s for s in SYMBOLS + SYMBOLS_NN if not hasattr(L, s)]
     if missing:
         raise HipExtensionError(f"{LIB_PATH} does not export {', '.join(missing)}: not a build of this ABI")
     _lib = bind(L)
@@ -945,6 +964,65 @@ class Handle(DistCalls):
             work = self.empty(max(1, chol_update_workspace_bytes(n, len(idx))) // 8)
         self._call("fvgp_hip_chol_delete", _ptr(L), int(n), L.stride(0), idx.ctypes.data_as(P_l), len(idx),
                    _ptr(work), work.numel() * 8)
+
+    # -- nearest-neighbour (Vecchia) path (include/fvgp_hip_nn.h) ---------------------------------------------------------------
+    def nn_search(self, xq, xr, m, idx_out, scales=None, c0=-1):
+        """fvgp_hip_nn_search: idx_out (nq, >= m) int32 device tensor <- per row of xq the m nearest candidates among the rows of xr,
+        sorted by (distance, index), -1 past the candidate count; scales None or d positive numbers (host); c0 < 0: every row of xr is
+        a candidate, c0 >= 0: rows j < min(nr, c0 + i) for query i.  Asynchronous."""
+        if idx_out.dim() != 2 or idx_out.stride(1) != 1 or idx_out.dtype != self.torch.int32 or idx_out.shape[0] < xq.shape[0]:
+            raise ValueError(f"nn_search: idx_out must be an int32 (nq, >= m) tensor with unit column stride, got {tuple(idx_out.shape)}")
+        sp = None
+        if scales is not None:
+            sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
+            if sc.shape != (xq.shape[1],):
+                raise ValueError(f"nn_search: scales must be {xq.shape[1]} numbers")
+            sp = sc.ctypes.data_as(P_d)
+        self._call("fvgp_hip_nn_search", _ptr(xq), xq.shape[0], _ptr(xr), xr.shape[0], xq.shape[1], sp, int(m), int(c0),
+                   _ptr(idx_out), idx_out.stride(0))
+
+    def _nn_operands(self, who, thetas, idx, nq, m, mu, var):
+        t = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+        t = t.reshape(1, -1) if t.ndim == 1 else t
+        if t.ndim != 2:
+            raise ValueError(f"{who}: thetas must be (B, ntheta)")
+        B = t.shape[0]
+        if idx.dim() != 2 or idx.stride(1) != 1 or idx.dtype != self.torch.int32 or idx.shape[0] < nq or idx.shape[1] < m:
+            raise ValueError(f"{who}: idx must be an int32 (nq, >= m) tensor with unit column stride, got {tuple(idx.shape)}")
+        for name, a in (("mu", mu), ("var", var)):
+            if not a.is_contiguous() or a.numel() < B * nq:
+                raise ValueError(f"{who}: {name} must be a contiguous (B, nq) tensor, got {tuple(a.shape)}")
+        return t, B
+
+    def nn_conditionals(self, kernel_id, xq, xr, thetas, idx, m, r, v, mu, var, s=None, work=None):
+        """fvgp_hip_nn_conditionals: mu, var (B, nq) device tensors <- the conditional mean (without prior mean) and variance of every
+        row of xq given its neighbours idx[i][:m] among the rows of xr, at the B rows of `thetas` (host, B x ntheta or one vector).
+        r, v (nr): centred data and noise of the reference rows; s (nq) or None: added to every row's variance.  Returns info: 0, or
+        1 + b nq + i of the first (b, i) whose variance is not positive (a failed pivot leaves NaN).  Synchronous."""
+        nq = xq.shape[0]
+        t, B = self._nn_operands("nn_conditionals", thetas, idx, nq, m, mu, var)
+        if work is None:
+            work = self.empty(max(1, nn_workspace_bytes(NN_CONDITIONALS, nq, B)) // 8)
+        info = ctypes.c_int64(0)
+        self._call("fvgp_hip_nn_conditionals", int(kernel_id), _ptr(xq), nq, _ptr(xr), xr.shape[0], xq.shape[1], t.ctypes.data_as(P_d),
+                   t.shape[1], B, _ptr(idx), idx.stride(0), int(m), _ptr(r), _ptr(v), _ptr(s), _ptr(mu), _ptr(var),
+                   _ptr(work), work.numel() * 8, ctypes.byref(info))
+        return int(info.value)
+
+    def nn_loglik(self, kernel_id, x, thetas, idx, m, r, v, mu, var, work=None):
+        """fvgp_hip_nn_loglik: the nearest-neighbour log-likelihood of the rows of x in their order (idx: nn_search of x on itself with
+        c0 = 0) at the B rows of `thetas`.  Returns (out (B, 3) ndarray of {log p, sum (r - mu)^2 / var, sum log var}, info as
+        nn_conditionals); mu, var (B, n) keep the per-row conditionals.  Synchronous."""
+        n = x.shape[0]
+        t, B = self._nn_operands("nn_loglik", thetas, idx, n, m, mu, var)
+        if work is None:
+            work = self.empty(max(1, nn_workspace_bytes(NN_LOGLIK, n, B)) // 8)
+        out = np.empty((B, 3), dtype=np.float64)
+        info = ctypes.c_int64(0)
+        self._call("fvgp_hip_nn_loglik", int(kernel_id), _ptr(x), n, x.shape[1], t.ctypes.data_as(P_d), t.shape[1], B,
+                   _ptr(idx), idx.stride(0), int(m), _ptr(r), _ptr(v), _ptr(mu), _ptr(var), _ptr(work), work.numel() * 8,
+                   out.ctypes.data_as(P_d), ctypes.byref(info))
+        return out, int(info.value)
 
     def posterior_prepare(self, L, n):
         """enqueue the inverted diagonal blocks the posterior's sweep substitutes with (fvgp_hip_posterior_prepare)"""

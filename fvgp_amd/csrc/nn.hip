@@ -1,0 +1,428 @@
+// The nearest-neighbour (Vecchia) path (include/fvgp_hip_nn.h): n independent m x m problems, m <= 64, instead of one n x n.
+// fvgp_hip_nn_search        brute-force m nearest candidates of every query: a wavefront per 64 queries, a lane per query, the reference
+//     rows staged through LDS in slices (every lane reads the same row: broadcast reads), each lane's running top-m kept sorted in LDS
+//     (slot-major, so lanes touching the same slot never meet on a bank) by insertion from the end.  Rows are walked in ascending index
+//     and an entry moves only for a strictly smaller distance: ties stay with the lower index.
+// fvgp_hip_nn_conditionals  one wavefront per (row, b), NN_WAVES of them per workgroup and nothing shared between them: lane l owns
+//     neighbour l.  Assembly: for column j the lanes read x_j from lane j's registers (v_readlane, j is uniform) and lanes l >= j store
+//     K(x_l, x_j) into the packed lower triangle held COLUMN-major in LDS (column j: rows j .. M - 1, consecutive lanes on consecutive
+//     addresses).  Factorisation: left-looking, column by column, lane l accumulating its entry of the column over the earlier columns
+//     (own entries conflict-free, row j's entries broadcast); the pivot leaves lane j by v_readlane, and both right-hand sides (k and
+//     r_c, a register each) are substituted in the same step.  Padded lanes are identity rows.
+// fvgp_hip_nn_loglik        the conditionals on the data itself, then the two sums: slices of 256 rows by a halving tree in LDS, the
+//     slices to 0 in ascending order by one thread per b.  No atomics anywhere.
+#include "radial.h"
+#include "kernel_family.h"
+#include "../../include/fvgp_hip_nn.h"
+#include <math.h>
+#include <vector>
+
+namespace {
+
+constexpr int NN_WAVES = 4;                       // conditionals: waves (problems) per workgroup
+constexpr int NN_TAB = 1 + FVGP_MAX_DIM;          // theta table row: sigma^2, then 1 / l per dimension
+constexpr int NN_SEARCH_ROWS = 128;               // reference rows per staged slice of the search
+constexpr int NN_SEARCH_QUERIES = 65536;          // queries per launch of the search
+constexpr int NN_SUM_ROWS = 256;                 // rows per slice of the likelihood's sums
+
+// LDS traffic between the lanes of ONE wave: the wave's DS operations execute in order, the fences keep the compiler from moving them
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// lane j's v in every lane (j wave-uniform)
+__device__ __forceinline__ double lane_value(const double v, const int j) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), j), hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
+    return __hiloint2double(hi, lo);
+}
+
+// lane 0 <- the 64 lanes' values by the halving tree (lane i += lane i + 32, 16, .. 1)
+__device__ __forceinline__ double wave_tree_sum(double w) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
+    return w;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ search
+struct NsArgs {
+    const double *xq, *xr;
+    int *out;
+    long nq, nr, ld, c0;
+    int d, m;
+    double is[FVGP_MAX_DIM];                       // 1 / scale per dimension (1: unscaled)
+};
+
+template <int D, int M>      // D == 0: runtime dimension (<= FVGP_MAX_DIM); M: list capacity, m <= M
+__global__ __launch_bounds__(64) void nn_search_kernel(NsArgs a) {
+    constexpr int DD = D ? D : FVGP_MAX_DIM;
+    __shared__ double sx[NN_SEARCH_ROWS * DD];
+    __shared__ double sd[M * 64];                  // [slot][lane]
+    __shared__ int si[M * 64];
+    const int d = D ? D : a.d, m = a.m;
+    const int lane = threadIdx.x;
+    const long q0 = (long)blockIdx.x * 64, q = q0 + lane;
+    const long qi = q < a.nq ? q : a.nq - 1;
+    double u[DD], is[DD];
+#pragma unroll
+    for (int k = 0; k < DD; ++k) { u[k] = k < d ? a.xq[qi * d + k] : 0.0; is[k] = a.is[k]; }
+    // candidates of this lane [0, lim) and of the block [0, top)
+    long lim = a.nr, top = a.nr;
+    if (a.c0 >= 0) {
+        lim = a.c0 + q < a.nr ? a.c0 + q : a.nr;
+        const long ql = q0 + 63 < a.nq ? q0 + 63 : a.nq - 1;
+        top = a.c0 + ql < a.nr ? a.c0 + ql : a.nr;
+    }
+    if (q >= a.nq) lim = 0;
+    int cnt = 0;
+    double worst = INFINITY;                       // the list's last distance once it is full
+
+    for (long row0 = 0; row0 < top; row0 += NN_SEARCH_ROWS) {
+        __syncthreads();                           // the last slice has been read
+        const int rows = top - row0 < NN_SEARCH_ROWS ? (int)(top - row0) : NN_SEARCH_ROWS;
+        for (int e = lane; e < rows * d; e += 64) {
+            const int rr = e / d, kk = e - rr * d;
+            sx[rr * DD + kk] = a.xr[(row0 + rr) * d + kk];
+        }
+        __syncthreads();
+        for (int r = 0; r < rows; ++r) {
+            const double *xr = sx + r * DD;
+            double dist = 0.0;
+#pragma unroll
+            for (int k = 0; k < DD; ++k)
+                if (k < d) { const double e = (u[k] - xr[k]) * is[k]; dist = fma(e, e, dist); }
+            const long j = row0 + r;
+            if (j < lim && (cnt < m || dist < worst)) {
+                int p = cnt < m ? cnt : m - 1;     // the slot that opens: behind the list, or its last entry drops out
+                while (p > 0 && sd[(p - 1) * 64 + lane] > dist) {
+                    sd[p * 64 + lane] = sd[(p - 1) * 64 + lane];
+                    si[p * 64 + lane] = si[(p - 1) * 64 + lane];
+                    --p;
+                }
+                sd[p * 64 + lane] = dist;
+                si[p * 64 + lane] = (int)j;
+                if (cnt < m) ++cnt;
+                if (cnt == m) worst = sd[(m - 1) * 64 + lane];
+            }
+        }
+    }
+    if (q >= a.nq) return;
+    for (int p = 0; p < m; ++p) a.out[q * a.ld + p] = p < cnt ? si[p * 64 + lane] : -1;
+}
+
+// f(std::integral_constant<int, D>) with the dimensions that have an instantiation of their own (those of dispatch_kind_dim)
+template <class F>
+inline void dispatch_dim(int d, F &&f) {
+    switch (d) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, 0>{}); break;
+    }
+}
+
+// f(std::integral_constant<int, M>) for the padded size of m neighbours
+template <class F>
+inline void dispatch_pad(int m, F &&f) {
+    if (m <= 16) f(std::integral_constant<int, 16>{});
+    else if (m <= 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
+// ------------------------------------------------------------------------------------------------------------ conditionals
+struct NcArgs {
+    const double *xq, *xr, *r, *v, *s, *tab;       // tab (B, NN_TAB)
+    const int *idx;
+    double *mu, *var;
+    long nq, nr, ld;
+    int d, m;
+};
+
+template <int KIND, int D, int M>   // D == 0: runtime dimension; M: the padded block, m <= M
+__global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
+    constexpr int DD = D ? D : FVGP_MAX_DIM;
+    constexpr int TRI = M * (M + 1) / 2;
+    __shared__ double sm_all[NN_WAVES * TRI];
+    const int d = D ? D : a.d;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long row = (long)blockIdx.x * NN_WAVES + wave;
+    if (row >= a.nq) return;                       // (no workgroup barrier below: the waves share nothing)
+    const long b = blockIdx.y;
+    double *sm = sm_all + wave * TRI;
+    const double *tab = a.tab + b * NN_TAB;
+    const double sig = tab[0];
+    double il[DD], u[DD], xi[DD];
+#pragma unroll
+    for (int k = 0; k < DD; ++k) { il[k] = k < d ? tab[1 + k] : 0.0; xi[k] = k < d ? a.xq[row * d + k] : 0.0; }
+    // lane l's neighbour; a lane without one (past m, or an index outside the reference rows) is an identity row
+    long c = -1;
+    if (lane < a.m) c = a.idx[row * a.ld + lane];
+    const bool valid = c >= 0 && c < a.nr;
+    const long cc = valid ? c : 0;
+#pragma unroll
+    for (int k = 0; k < DD; ++k) u[k] = k < d ? a.xr[cc * d + k] : 0.0;
+    const double vc = valid ? a.v[cc] : 0.0;
+    double tz = valid ? a.r[cc] : 0.0;             // becomes z_l
+    double tw = 0.0;                               // k_l = k(x_c, x_i), becomes w_l
+    {
+        double r2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < DD; ++k)
+            if (k < d) { const double e = (u[k] - xi[k]) * il[k]; r2 = fma(e, e, r2); }
+        const double kv = radial<KIND>(r2, sig);
+        if (valid) tw = kv;
+    }
+    const unsigned long long vmask = __ballot(valid);
+
+    // assembly: column j of the lower triangle at sm[col + l], col = off(j) - j, off(j) = j M - j (j - 1) / 2
+    for (int j = 0, col = 0; j < M; col += M - j - 1, ++j) {
+        double r2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < DD; ++k)
+            if (k < d) { const double e = (u[k] - lane_value(u[k], j)) * il[k]; r2 = fma(e, e, r2); }
+        double kv = radial<KIND>(r2, sig);
+        const bool vj = (vmask >> j) & 1ull;
+        if (lane == j) kv = valid ? kv + vc : 1.0;
+        else if (!(valid && vj)) kv = 0.0;
+        if (lane >= j && lane < M) sm[col + lane] = kv;
+    }
+    wave_sync();
+
+    // factorisation and both substitutions
+    bool fail = false;
+    for (int j = 0, col = 0; j < M; col += M - j - 1, ++j) {
+        const int lr = lane < j ? j : (lane < M ? lane : M - 1);       // (lanes outside the column repeat a row of it: every read stays inside the triangle)
+        double sacc = sm[col + lr];
+        for (int k = 0, ck = 0; k < j; ck += M - k - 1, ++k) sacc = fma(-sm[ck + lr], sm[ck + j], sacc);
+        double p = lane_value(sacc, j);
+        if (!(p > 0.0)) { fail = true; p = 1.0; }
+        const double ljj = sqrt(p), inv = 1.0 / ljj;
+        const double lc = sacc * inv;
+        if (lane > j && lane < M) sm[col + lane] = lc;
+        const double wj = lane_value(tw, j) * inv, zj = lane_value(tz, j) * inv;
+        if (lane == j) { tw = wj; tz = zj; }
+        else if (lane > j) { tw = fma(-lc, wj, tw); tz = fma(-lc, zj, tz); }
+        wave_sync();
+    }
+    if (lane >= M) { tw = 0.0; tz = 0.0; }
+    const double mu = wave_tree_sum(tw * tz), ww = wave_tree_sum(tw * tw);
+    if (lane == 0) {
+        double kxx = radial<KIND>(0.0, sig);
+        if (a.s) kxx += a.s[row];
+        a.mu[b * a.nq + row] = fail ? NAN : mu;
+        a.var[b * a.nq + row] = fail ? NAN : kxx - ww;
+    }
+}
+
+// info <- 0 or 1 + the first e in [0, total) with var[e] not positive: one workgroup, each thread the smallest of its stride, then a
+// halving tree of minima
+__global__ __launch_bounds__(256) void nn_info_kernel(const double *var, long total, long long *info) {
+    __shared__ long long sm[256];
+    const int tid = threadIdx.x;
+    long long first = 0x7fffffffffffffffLL;
+    for (long e = tid; e < total; e += 256)
+        if (!(var[e] > 0.0)) { first = e; break; }
+    sm[tid] = first;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off && sm[tid + off] < sm[tid]) sm[tid] = sm[tid + off];
+        __syncthreads();
+    }
+    if (tid == 0) *info = sm[0] == 0x7fffffffffffffffLL ? 0 : sm[0] + 1;
+}
+
+// ------------------------------------------------------------------------------------------------------ the likelihood's sums
+// part[(b * nslices + slice) * 2 + {0, 1}] = the slice's sums of (r - mu)^2 / var and log var: a halving tree over 256 rows
+__global__ __launch_bounds__(NN_SUM_ROWS) void nn_terms_kernel(const double *r, const double *mu, const double *var, long n, double *part) {
+    __shared__ double sf[NN_SUM_ROWS], sl[NN_SUM_ROWS];
+    const int tid = threadIdx.x;
+    const long i = (long)blockIdx.x * NN_SUM_ROWS + tid, b = blockIdx.y;
+    double f = 0.0, l = 0.0;
+    if (i < n) {
+        const double dv = var[b * n + i], e = r[i] - mu[b * n + i];
+        f = e * e / dv;
+        l = log(dv);
+    }
+    sf[tid] = f; sl[tid] = l;
+    __syncthreads();
+    for (int off = NN_SUM_ROWS / 2; off > 0; off >>= 1) {
+        if (tid < off) { sf[tid] += sf[tid + off]; sl[tid] += sl[tid + off]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double *o = part + (b * gridDim.x + blockIdx.x) * 2;
+        o[0] = sf[0]; o[1] = sl[0];
+    }
+}
+
+// out[b] = {log p, fit, logdet}: the slices added to 0 in ascending order, one thread per b
+__global__ __launch_bounds__(64) void nn_total_kernel(const double *part, long nslices, long n, int B, double *out) {
+    const long b = (long)blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    double f = 0.0, l = 0.0;
+    for (long s = 0; s < nslices; ++s) { f += part[(b * nslices + s) * 2]; l += part[(b * nslices + s) * 2 + 1]; }
+    out[b * 3] = -0.5 * (f + l + (double)n * 1.8378770664093454836);       // log 2 pi
+    out[b * 3 + 1] = f;
+    out[b * 3 + 2] = l;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+inline int64_t nn_slices(int64_t n) { return (n + NN_SUM_ROWS - 1) / NN_SUM_ROWS; }
+// work, in doubles: [0] the info word, [2 ..) the theta table, then (likelihood) the results and the slices' sums
+inline int64_t nn_tab_off() { return 2; }
+inline int64_t nn_out_off(int B) { return nn_tab_off() + even_up((int64_t)B * NN_TAB); }
+inline int64_t nn_part_off(int B) { return nn_out_off(B) + even_up((int64_t)B * 3); }
+inline int64_t nn_work_doubles(int what, int64_t nq, int B) {
+    if (what == FVGP_NN_SEARCH) return 0;
+    if (what == FVGP_NN_CONDITIONALS) return nn_out_off(B);
+    return nn_part_off(B) + 2 * (int64_t)B * nn_slices(nq);
+}
+
+// the theta table of B hyperparameter vectors into work, the conditionals over it and the info word; nothing is read back
+int nn_run_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t nq, const double *xr, int64_t nr, int d,
+                        const double *thetas, int ntheta, int B, const int *idx, int64_t ld, int m, const double *r, const double *v,
+                        const double *s, double *mu, double *var, double *work) {
+    std::vector<double> tab((size_t)B * NN_TAB);
+    KmatDesc k{};
+    for (int b = 0; b < B; ++b) {
+        const int rc = kmat_desc_from_theta(kernel_id, d, thetas + (size_t)b * ntheta, ntheta, &k);
+        if (rc) return rc;
+        tab[(size_t)b * NN_TAB] = k.sig;
+        for (int i = 0; i < FVGP_MAX_DIM; ++i) tab[(size_t)b * NN_TAB + 1 + i] = k.invl[i];
+    }
+    double *tab_dev = work + nn_tab_off();
+    HIPCHK(hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));       // (the table leaves this frame)
+    NcArgs a;
+    a.xq = xq; a.xr = xr; a.r = r; a.v = v; a.s = s; a.tab = tab_dev; a.idx = idx; a.mu = mu; a.var = var;
+    a.nq = nq; a.nr = nr; a.ld = ld; a.d = d; a.m = m;
+    const dim3 grid((unsigned)((nq + NN_WAVES - 1) / NN_WAVES), (unsigned)B), block(64 * NN_WAVES);
+    dispatch_kind_dim(k.kind, d, [&](auto KIND, auto D) {
+        dispatch_pad(m, [&](auto M) {
+            hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value>), grid, block, 0, h->stream, a);
+        });
+    });
+    HIPCHK(hipGetLastError());
+    HIPLAUNCH(nn_info_kernel, dim3(1), dim3(256), h->stream, (const double *)var, (long)(nq * B), (long long *)work);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t fvgp_hip_nn_workspace_bytes(int what, int64_t nq, int B) {
+    if (what < FVGP_NN_SEARCH || what > FVGP_NN_LOGLIK || nq < 1 || B < 1) return -1;
+    return nn_work_doubles(what, nq, B) * (int64_t)sizeof(double);
+}
+
+int fvgp_hip_nn_search(fvgp_handle *h, const double *xq, int64_t nq, const double *xr, int64_t nr, int d, const double *scales_host,
+                       int m, int64_t c0, int *idx_out, int64_t ld) {
+    if (!h) return -1;
+    if (!xq) return -2;
+    if (nq < 1 || (nq + 63) / 64 > 0x7fffffffLL) return -3;
+    if (!xr) return -4;
+    if (nr < 1 || nr > 0x7fffffffLL) return -5;
+    if (d < 1 || d > FVGP_MAX_DIM) { fvgp_set_error("input dimension out of range"); return -6; }
+    NsArgs a;
+    for (int k = 0; k < FVGP_MAX_DIM; ++k) a.is[k] = 1.0;
+    if (scales_host)
+        for (int k = 0; k < d; ++k) {
+            if (!(scales_host[k] > 0.0) || !std::isfinite(scales_host[k])) { fvgp_set_error("nn_search: scales must be positive and finite"); return -7; }
+            a.is[k] = 1.0 / scales_host[k];
+        }
+    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error("nn_search: 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -8; }
+    if (!idx_out) return -10;
+    if (ld < m) return -11;
+    HIPCHK(hipSetDevice(h->device));
+    a.xr = xr; a.nr = nr; a.ld = ld; a.d = d; a.m = m;
+    // a launch per NN_SEARCH_QUERIES queries (a row's result does not depend on the cut): no single launch walks 10^6 x 10^6 pairs
+    for (int64_t q0 = 0; q0 < nq; q0 += NN_SEARCH_QUERIES) {
+        a.xq = xq + q0 * d; a.out = idx_out + q0 * ld;
+        a.nq = nq - q0 < NN_SEARCH_QUERIES ? nq - q0 : NN_SEARCH_QUERIES;
+        a.c0 = c0 < 0 ? -1 : c0 + q0;
+        const dim3 grid((unsigned)((a.nq + 63) / 64)), block(64);
+        dispatch_dim(d, [&](auto D) {
+            dispatch_pad(m, [&](auto M) {
+                hipLaunchKernelGGL((nn_search_kernel<decltype(D)::value, decltype(M)::value>), grid, block, 0, h->stream, a);
+            });
+        });
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+int fvgp_hip_nn_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t nq, const double *xr, int64_t nr, int d,
+                             const double *thetas_host, int ntheta, int B, const int *idx, int64_t ld, int m,
+                             const double *r, const double *v, const double *s_or_null, double *mu, double *var,
+                             double *work, int64_t work_bytes, int64_t *info_host) {
+    if (!h) return -1;
+    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
+    if (!xq) return -3;
+    if (nq < 1 || (nq + NN_WAVES - 1) / NN_WAVES > 0x7fffffffLL) return -4;
+    if (!xr) return -5;
+    if (nr < 1 || nr > 0x7fffffffLL) return -6;
+    int rc = check_kernel_args(kernel_id, d, thetas_host, ntheta, 7, 8, 9); if (rc) return rc;
+    if (B < 1 || B > 65535) { fvgp_set_error("nn_conditionals: 1 .. 65535 hyperparameter vectors per call"); return -10; }
+    if (!idx) return -11;
+    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error("nn_conditionals: 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -13; }
+    if (ld < m) return -12;
+    if (!r) return -14;
+    if (!v) return -15;
+    if (!mu) return -17;
+    if (!var) return -18;
+    if (!work || ((uintptr_t)work & 7)) return -19;
+    if (work_bytes < nn_work_doubles(FVGP_NN_CONDITIONALS, nq, B) * (int64_t)sizeof(double)) {
+        fvgp_set_error("nn_conditionals: work smaller than fvgp_hip_nn_workspace_bytes(FVGP_NN_CONDITIONALS, nq, B)"); return -20;
+    }
+    if (!info_host) return -21;
+    HIPCHK(hipSetDevice(h->device));
+    rc = nn_run_conditionals(h, kernel_id, xq, nq, xr, nr, d, thetas_host, ntheta, B, idx, ld, m, r, v, s_or_null, mu, var, work);
+    if (rc) return rc;
+    long long info = 0;
+    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *info_host = info;
+    return 0;
+}
+
+int fvgp_hip_nn_loglik(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *thetas_host, int ntheta, int B,
+                       const int *idx, int64_t ld, int m, const double *r, const double *v, double *mu, double *var,
+                       double *work, int64_t work_bytes, double *out_host, int64_t *info_host) {
+    if (!h) return -1;
+    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
+    if (!x) return -3;
+    if (n < 1 || n > 0x7fffffffLL) return -4;
+    int rc = check_kernel_args(kernel_id, d, thetas_host, ntheta, 5, 6, 7); if (rc) return rc;
+    if (B < 1 || B > 65535) { fvgp_set_error("nn_loglik: 1 .. 65535 hyperparameter vectors per call"); return -8; }
+    if (!idx) return -9;
+    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error("nn_loglik: 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -11; }
+    if (ld < m) return -10;
+    if (!r) return -12;
+    if (!v) return -13;
+    if (!mu) return -14;
+    if (!var) return -15;
+    if (!work || ((uintptr_t)work & 7)) return -16;
+    if (work_bytes < nn_work_doubles(FVGP_NN_LOGLIK, n, B) * (int64_t)sizeof(double)) {
+        fvgp_set_error("nn_loglik: work smaller than fvgp_hip_nn_workspace_bytes(FVGP_NN_LOGLIK, n, B)"); return -17;
+    }
+    if (!out_host) return -18;
+    if (!info_host) return -19;
+    HIPCHK(hipSetDevice(h->device));
+    rc = nn_run_conditionals(h, kernel_id, x, n, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, v, mu, var, work);
+    if (rc) return rc;
+    const int64_t ns = nn_slices(n);
+    double *out = work + nn_out_off(B), *part = work + nn_part_off(B);
+    HIPLAUNCH(nn_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, r, (const double *)mu, (const double *)var, (long)n, part);
+    HIPLAUNCH(nn_total_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), h->stream, (const double *)part, (long)ns, (long)n, B, out);
+    long long info = 0;
+    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(out_host, out, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *info_host = info;
+    return 0;
+}
+
+}  // extern "C"

@@ -30,6 +30,7 @@ from .gp_hessian import HessianMixin
 from .gp_lin_alg import NonPositiveDefiniteError, _non_pd_message
 from .gp_loo import LOOMixin
 from .gp_matrix_free import MatrixFreeMixin
+from .gp_vecchia import VecchiaMixin
 from .gp_sampling import SamplingMixin
 from .gp_update import UpdateMixin
 from .gp_validation import ValidationMixin
@@ -84,7 +85,7 @@ def _mixture_moments(m, v, w):
     return mean, within + between, within, between
 
 
-class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin, HessianMixin, MatrixFreeMixin, UpdateMixin):
+class GP(ValidationMixin, LOOMixin, SamplingMixin, DesignMixin, HessianMixin, MatrixFreeMixin, VecchiaMixin, UpdateMixin):
     def __init__(
         self,
         x_data,

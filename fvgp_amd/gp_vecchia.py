@@ -1,0 +1,349 @@
+"""A deterministic likelihood and prediction at sizes where no N x N factor fits: the nearest-neighbour (Vecchia / NNGP "response")
+approximation (include/fvgp_hip_nn.h).
+
+The data are put in an ordering, and the likelihood is written as a product of N small conditionals,
+
+    p(y) ~ prod_i p(y_i | y_c(i)),      c(i) = the m nearest of the points that come EARLIER in the ordering,
+
+each of them an m x m problem: with A = K(x_c, x_c) + diag(v_c), k = K(x_c, x_i), A = L L^T, w = L^-1 k, z = L^-1 (y_c - mean):
+mu_i = mean + w^T z, d_i = k(x_i, x_i) + v_i - w^T w, and log p = -1/2 sum_i [(y_i - mu_i)^2 / d_i + log d_i + log 2 pi].  O(N m^3) time,
+O(N m) memory, no iteration count and no standard error; with m >= N - 1 it IS the exact likelihood, and it approaches the exact GP's
+values as m grows.  Prediction at x* conditions on the m nearest data points: the same small problem.
+
+    big = VecchiaGP(x_all, y_all, hps, noise_all, n_neighbors=32)         # or gp.vecchia(x_all, y_all, noise_all)
+    big.log_likelihood(); big.train(bounds, method="mcmc")
+    big.posterior_mean(x_pred); big.posterior_covariance(x_pred, variance_only=True)
+
+"Nearest" is measured after dividing every coordinate by a scale (args["neighbor_scales"]: the length scales at construction, 1, or a
+vector), and the neighbour lists stay FIXED while the hyperparameters move (set_hyperparameters, training): the likelihood is then a
+smooth function of theta.  refresh_neighbors() rebuilds them.  The gradient of this likelihood, a tree search, a maxmin ordering and
+joint covariances are not built."""
+import warnings
+
+import numpy as np
+
+from . import _lib
+from . import gp_training as _training
+from . import kernels as _kernels
+from .device import default_handle
+from .gp_lin_alg import NonPositiveDefiniteError
+
+_DENSE = "the dense fvgp_amd.GP has it"
+_LOG_2PI = float(np.log(2.0 * np.pi))
+
+
+class VecchiaGP:
+    """The nearest-neighbour GP over x_data (N, D), y_data (N,): hyperparameters in the named kernel's layout, noise_variances (N,) or
+    None (the rule and the warning of GP: (0.01 mean|y|)^2), prior mean = mean(y).
+
+    n_neighbors: m in 1 .. 64.  ordering: "random" (a permutation drawn from `seed`), "given" (the caller's order) or a permutation
+    array; the data are held in that order and everything returned per data point is in the CALLER's order.  args:
+    "neighbor_scales" = "lengthscales" (default: the kernel's length scales at construction), "unit" or a D-vector;
+    "batch_population" (True: train(method="global") scores a generation in one device call)."""
+
+    def __init__(self, x_data, y_data, hyperparameters, noise_variances=None, kernel_function="matern32_ard", n_neighbors=32,
+                 ordering="random", seed=0, args=None):
+        native = _kernels.resolve(kernel_function) if not callable(kernel_function) or isinstance(kernel_function, _kernels.NativeKernel) \
+            else None
+        if native is None:
+            raise NotImplementedError("VecchiaGP evaluates the kernel on the device inside every conditional: only the named kernels of "
+                                      "fvgp_amd.kernels run here; a kernel callable belongs to the dense fvgp_amd.GP")
+        assert isinstance(x_data, np.ndarray) and np.ndim(x_data) == 2, "x_data must be 2-d (n_points x input_dim)"
+        if not isinstance(y_data, np.ndarray) or np.ndim(y_data) != 1:
+            raise NotImplementedError("y_data must be a 1-d np.ndarray: fvGP / x_out outputs are not on the nearest-neighbour path, "
+                                      + _DENSE)
+        assert len(x_data) == len(y_data), "x_data and y_data do not have the same lengths."
+        self.args = {} if args is None else dict(args)
+        if self.args.get("process_group") not in (None, False):
+            raise NotImplementedError("the row-sharded mode (args['process_group']) belongs to the dense fvgp_amd.GP: the "
+                                      "nearest-neighbour path runs on one device")
+        self.args.setdefault("batch_population", True)
+        if int(n_neighbors) != n_neighbors or not 1 <= int(n_neighbors) <= _lib.NN_MAX_NEIGHBORS:
+            raise ValueError(f"n_neighbors must lie in 1 .. {_lib.NN_MAX_NEIGHBORS}, got {n_neighbors!r}")
+        self.n_neighbors = int(n_neighbors)
+        self._native = native
+        self._H = default_handle()
+        if noise_variances is None:
+            warnings.warn("No noise function or measurement noise provided. "
+                          "Noise variances will be set to (0.01 * mean(|y_data|))^2.", stacklevel=2)
+        self._check_dim(x_data)
+        self._hps = self._check_hps(hyperparameters, x_data.shape[1])
+        self._scale_mode = self.args.get("neighbor_scales", "lengthscales")
+        self._scales = self._scales_at(self._hps, x_data.shape[1])
+        self._ordering_rule = (ordering if isinstance(ordering, str) else "given", seed)
+        self._set_data(x_data, y_data, noise_variances, self._make_ordering(ordering, len(x_data), seed))
+        self._search_all()
+
+    # ---- state -----------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_dim(x_data):
+        if x_data.shape[1] > 16:
+            raise NotImplementedError("the device kernels take input dimension <= 16")
+
+    def _check_hps(self, hps, d=None):
+        hps = np.array(hps, dtype=np.float64)
+        d = self.index_set_dim if d is None else d
+        assert hps.shape == (self._native.n_hyperparameters(d),), "wrong number of hyperparameters for this kernel"
+        return hps
+
+    def _scales_at(self, hps, d):
+        mode = self._scale_mode
+        if isinstance(mode, str):
+            if mode == "lengthscales":
+                return np.array(self._native.length_scales(hps, d), dtype=np.float64)
+            if mode == "unit":
+                return None
+            raise ValueError(f"args['neighbor_scales'] must be 'lengthscales', 'unit' or a vector of {d} positive numbers, got {mode!r}")
+        sc = np.array(mode, dtype=np.float64)
+        if sc.shape != (d,) or not np.all(sc > 0.0) or not np.all(np.isfinite(sc)):
+            raise ValueError(f"args['neighbor_scales'] must be 'lengthscales', 'unit' or a vector of {d} positive numbers")
+        return sc
+
+    @staticmethod
+    def _make_ordering(ordering, n, seed):
+        if isinstance(ordering, str):
+            if ordering == "random":
+                return np.random.default_rng(seed).permutation(n).astype(np.int64)
+            if ordering == "given":
+                return np.arange(n, dtype=np.int64)
+            raise ValueError(f"ordering must be 'random', 'given' or a permutation of range({n}), got {ordering!r}")
+        perm = np.array(ordering, dtype=np.int64)
+        if perm.shape != (n,) or not np.array_equal(np.sort(perm), np.arange(n)):
+            raise ValueError(f"ordering must be 'random', 'given' or a permutation of range({n})")
+        return perm
+
+    def _set_data(self, x_data, y_data, noise_variances, perm):
+        """the caller's arrays as they came, and on the device in the ordering `perm` (position p holds the caller's row perm[p])"""
+        H = self._H
+        self._check_dim(x_data)
+        self.x_data = np.ascontiguousarray(x_data, dtype=np.float64)
+        self.y_data = np.ascontiguousarray(y_data, dtype=np.float64)
+        self.point_number, self.index_set_dim = self.x_data.shape
+        if noise_variances is None:
+            V = np.ones(self.point_number) * (np.mean(abs(self.y_data)) / 100.0) ** 2
+        else:
+            V = np.asarray(noise_variances, dtype=np.float64)
+            assert V.shape == (self.point_number,), "noise_variances must be 1-d, one per data point"
+            assert np.all(V > 0.0), "all noise_variances must be positive"
+        self.noise_variances = noise_variances
+        self._V = np.ascontiguousarray(V)
+        self._m = float(np.mean(self.y_data))
+        self.ordering = perm
+        self._x_dev = H.to_device(self.x_data[perm])
+        self._V_dev = H.to_device(self._V[perm])
+        self._r_dev = H.to_device((self.y_data - self._m)[perm])
+
+    def _search(self, xq_dev, c0):
+        """int32 (nq, m) device tensor: the neighbours of the rows of xq_dev among the ordered data under the object's scales"""
+        H = self._H
+        idx = H.torch.empty((xq_dev.shape[0], self.n_neighbors), dtype=H.torch.int32, device=xq_dev.device)
+        H.nn_search(xq_dev, self._x_dev, self.n_neighbors, idx, scales=self._scales, c0=c0)
+        return idx
+
+    def _search_all(self):
+        self._idx = self._search(self._x_dev, 0)
+
+    @property
+    def hyperparameters(self):
+        return self._hps
+
+    def get_hyperparameters(self):
+        return self._hps
+
+    def set_hyperparameters(self, hps):
+        """new hyperparameters; the neighbour lists stay as they are (refresh_neighbors rebuilds them)"""
+        self._hps = self._check_hps(hps)
+
+    def refresh_neighbors(self, hyperparameters=None):
+        """rebuild the neighbour lists: under the length scales of `hyperparameters` (default: the current ones) where
+        args["neighbor_scales"] is "lengthscales", else under the same scales as before"""
+        hps = self._hps if hyperparameters is None else self._check_hps(hyperparameters)
+        self._scales = self._scales_at(hps, self.index_set_dim)
+        self._search_all()
+
+    def neighbors(self):
+        """(N, m) int64: row i lists the neighbours of the caller's data point i as the caller's indices, nearest first, -1 where the
+        ordering leaves fewer than m earlier points"""
+        idx = self._idx.cpu().numpy().astype(np.int64)
+        out = np.full_like(idx, -1)
+        out[self.ordering] = np.where(idx >= 0, self.ordering[np.clip(idx, 0, None)], -1)
+        return out
+
+    def _unorder(self, a):
+        """per-point values in the ordering (last axis) -> the caller's order"""
+        out = np.empty_like(a)
+        out[..., self.ordering] = a
+        return out
+
+    def _not_pd(self, info, nq, what, points=None):
+        b, row = divmod(int(info) - 1, nq)
+        where = f"data point {int(self.ordering[row])}" if points is None else f"prediction point {row}"
+        return NonPositiveDefiniteError(
+            f"{what}: the conditional of {where} (hyperparameter vector {b}) is not positive definite in double precision -- its "
+            f"{self.n_neighbors} x {self.n_neighbors} neighbour block K + V or its conditional variance has a pivot that is not positive; "
+            "duplicated points need positive noise, or rethink the hyperparameters")
+
+    # ---- the likelihood ----------------------------------------------------------------------------------------------------
+    def _loglik(self, thetas):
+        """(out (B, 3), info, mu (B, n), var (B, n)) of one device call at the rows of thetas"""
+        H, n = self._H, self.point_number
+        B = thetas.shape[0]
+        mu, var = H.empty(B, n), H.empty(B, n)
+        out, info = H.nn_loglik(self._native.kernel_id, self._x_dev, thetas, self._idx, self.n_neighbors, self._r_dev, self._V_dev, mu, var)
+        return out, info, mu, var
+
+    def _one(self, hyperparameters):
+        hps = self._hps if hyperparameters is None else self._check_hps(hyperparameters)
+        return hps.reshape(1, -1)
+
+    def log_likelihood(self, hyperparameters=None):
+        """the nearest-neighbour log marginal likelihood at the object's hyperparameters or at `hyperparameters`: deterministic, the
+        same bits on every call"""
+        out, info, _, _ = self._loglik(self._one(hyperparameters))
+        if info:
+            raise self._not_pd(info, self.point_number, "log_likelihood")
+        return float(out[0, 0])
+
+    def neg_log_likelihood(self, hyperparameters=None):
+        return -self.log_likelihood(hyperparameters)
+
+    def log_likelihood_batch(self, thetas):
+        """(B,): the log-likelihood at the B rows of `thetas` in one device call, each equal bit for bit to log_likelihood(thetas[b]);
+        NaN where a conditional is not positive definite"""
+        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+        assert thetas.ndim == 2 and thetas.shape[1] == len(self._hps), "thetas must be (B, number of hyperparameters)"
+        out = np.empty(len(thetas))
+        for a in range(0, len(thetas), 4096):
+            out[a:a + 4096] = self._loglik(thetas[a:a + 4096])[0][:, 0]
+        return out
+
+    def neg_log_likelihood_batch(self, thetas):
+        """-log_likelihood_batch with +inf where it is NaN (what a population optimiser wants to see)"""
+        f = -self.log_likelihood_batch(thetas)
+        return np.where(np.isnan(f), np.inf, f)
+
+    def conditionals(self, hyperparameters=None):
+        """{"mean", "variance", "log_predictive"} (N,) each, in the caller's order: every data point's conditional given its neighbours,
+        the factors of the likelihood (their log_predictive sum to it up to rounding) and the approximation's residual diagnostics"""
+        out, info, mu, var = self._loglik(self._one(hyperparameters))
+        if info:
+            raise self._not_pd(info, self.point_number, "conditionals")
+        mu, var = self._H.to_host(mu)[0], self._H.to_host(var)[0]
+        r = (self.y_data - self._m)[self.ordering]
+        lp = -0.5 * ((r - mu) ** 2 / var + np.log(var) + _LOG_2PI)
+        return {"mean": self._unorder(self._m + mu), "variance": self._unorder(var), "log_predictive": self._unorder(lp)}
+
+    # ---- prediction ----------------------------------------------------------------------------------------------------------
+    def _check_pred(self, x_pred, x_out=None):
+        if x_out is not None:
+            raise NotImplementedError("x_out / fvGP outputs are not on the nearest-neighbour path: " + _DENSE)
+        assert isinstance(x_pred, np.ndarray) and np.ndim(x_pred) == 2, "x_pred must be a 2-d np.ndarray"
+        assert x_pred.shape[1] == self.index_set_dim, "wrong number of columns in x_pred"
+        return self._H.to_device(x_pred)
+
+    def _predict(self, x_pred, hyperparameters, x_out, s=None, what="posterior_mean"):
+        H = self._H
+        xp = self._check_pred(x_pred, x_out)
+        P = xp.shape[0]
+        idx = self._search(xp, -1)
+        mu, var = H.empty(1, P), H.empty(1, P)
+        info = H.nn_conditionals(self._native.kernel_id, xp, self._x_dev, self._one(hyperparameters), idx, self.n_neighbors,
+                                 self._r_dev, self._V_dev, mu, var, s=None if s is None else H.to_device(s))
+        if info:
+            raise self._not_pd(info, P, what, points=x_pred)
+        return H.to_host(mu)[0], H.to_host(var)[0]
+
+    def posterior_mean(self, x_pred, hyperparameters=None, x_out=None):
+        """{"x", "m(x)"}: the mean at every row of x_pred given its n_neighbors nearest data points"""
+        mu, _ = self._predict(x_pred, hyperparameters, x_out)
+        mean = self._m + mu
+        return {"x": x_pred.copy(), "m(x)": mean, "m(x)_flat": mean, "x_pred": x_pred}
+
+    def posterior_covariance(self, x_pred, variance_only=True, add_noise=False, hyperparameters=None, x_out=None):
+        """{"x", "v(x)"}: the variance at every row of x_pred given its n_neighbors nearest data points; add_noise adds the data's
+        noise (point for point when x_pred has as many rows as the data, else its mean)"""
+        if not variance_only:
+            raise NotImplementedError("posterior_covariance(variance_only=False): the nearest-neighbour approximation conditions every "
+                                      "point on its own neighbours and defines no joint covariance; MatrixFreeGP (all the data, matrix-free) "
+                                      "and the dense fvgp_amd.GP have it")
+        s = None
+        if add_noise:
+            s = self._V.copy() if len(x_pred) == self.point_number else np.zeros(len(x_pred)) + np.mean(self._V)
+        _, v = self._predict(x_pred, hyperparameters, x_out, s=s, what="posterior_covariance")
+        if np.any(v < -0.0001):
+            warnings.warn("Negative variances encountered. That normally means that the model is unstable. "
+                          "Rethink the kernel definition, add more noise to the data, "
+                          "or double check the hyperparameter optimization bounds. This will not "
+                          "terminate the algorithm, but expect anomalies.")
+        v = np.where(v < 0.0, 0.0, v)
+        return {"x": x_pred.copy(), "x_pred": x_pred, "v(x)": v, "v_flat": v, "S": None}
+
+    # ---- data ------------------------------------------------------------------------------------------------------------------
+    def update_gp_data(self, x_new, y_new, noise_variances_new=None, append=True):
+        """append=True: the new points go to the END of the ordering and only their neighbours are searched (the old rows' lists stay:
+        the state equals a fresh object with the same ordering and the new rows last); the prior mean is recomputed.  append=False
+        replaces everything (the ordering is made again by the constructor's rule; a permutation array there: the caller's order)."""
+        assert isinstance(x_new, np.ndarray) and np.ndim(x_new) == 2 and isinstance(y_new, np.ndarray) and np.ndim(y_new) == 1
+        assert x_new.shape[1] == self.index_set_dim and len(x_new) == len(y_new), "x_new / y_new do not fit the data"
+        if not append:
+            self._set_data(x_new, y_new, noise_variances_new, self._make_ordering(self._ordering_rule[0], len(x_new), self._ordering_rule[1]))
+            self._search_all()
+            return
+        if (self.noise_variances is None) != (noise_variances_new is None):
+            raise Exception("noise_variances_new must be given exactly when the object was built with noise_variances")
+        n_old, k = self.point_number, len(x_new)
+        if k == 0:
+            return
+        old_idx = self._idx
+        x_all, y_all = np.vstack([self.x_data, x_new]), np.concatenate([self.y_data, y_new])
+        v_all = None if noise_variances_new is None else np.concatenate([self.noise_variances, noise_variances_new])
+        self._set_data(x_all, y_all, v_all, np.concatenate([self.ordering, n_old + np.arange(k, dtype=np.int64)]))
+        self._idx = self._H.torch.cat([old_idx, self._search(self._x_dev[n_old:], n_old)], dim=0)
+
+    # ---- training ----------------------------------------------------------------------------------------------------------------
+    def neg_log_likelihood_gradient(self, hyperparameters=None, component=0):
+        raise NotImplementedError("neg_log_likelihood_gradient: the exact gradient of the nearest-neighbour likelihood is not built yet; "
+                                  "train with method='mcmc' or 'global', or take gradients from the dense fvgp_amd.GP on a subset")
+
+    def train(self, hyperparameter_bounds, init_hyperparameters=None, method="mcmc", pop_size=20, tolerance=1e-4, max_iter=1000,
+              info=False, seed=None, constraints=(), mcmc_prior=None, mcmc_args=None, mcmc_prop_distrs="normal"):
+        """gp_training.train on the deterministic likelihood with the value-only methods: "mcmc" (default), "global" (a generation of
+        the population in one device call unless args["batch_population"] is False) or a callable.  The neighbour lists stay fixed
+        throughout.  Ends with set_hyperparameters(theta) and returns theta."""
+        if method in ("local", "adam", "hgdl", "bo"):
+            raise NotImplementedError(f"train(method={method!r}) needs a gradient, and the exact gradient of the nearest-neighbour "
+                                      "likelihood is not built yet: 'mcmc', 'global' or a callable run here")
+        bounds = np.asarray(hyperparameter_bounds, dtype=np.float64)
+        assert bounds.ndim == 2 and bounds.shape == (len(self._hps), 2), "wrong bounds format"
+        theta0 = np.array(self._hps if init_hyperparameters is None else init_hyperparameters, dtype=np.float64)
+        hps = _training.train(self, bounds, theta0, method=method, pop_size=pop_size, tolerance=tolerance, max_iter=max_iter,
+                              constraints=constraints, info=info, seed=seed, mcmc_prior=mcmc_prior, mcmc_args=mcmc_args,
+                              mcmc_prop_distrs=mcmc_prop_distrs)
+        self.set_hyperparameters(hps)
+        return hps
+
+
+class VecchiaMixin:
+    """Mixed into fvgp_amd.GP: needs _native, _hps, _sharded, _noise_callable, _mean_callable, x_data, y_data, noise_variances."""
+
+    def vecchia(self, x_data=None, y_data=None, noise_variances=None, n_neighbors=32, **kw):
+        """A VecchiaGP with this GP's kernel and CURRENT hyperparameters, over this GP's data or over MORE data than a dense factor can
+        hold (x_data, y_data, noise_variances); kw: ordering, seed, args."""
+        if self._native is None:
+            raise NotImplementedError("vecchia evaluates the kernel on the device: a kernel callable stays with the dense GP "
+                                      "(use one of the named kernels)")
+        if self._noise_callable is not None or self._mean_callable is not None:
+            raise NotImplementedError("vecchia takes noise variances as numbers and the default prior mean: noise and mean "
+                                      "callables stay with the dense GP")
+        if getattr(self, "_sharded", False):
+            raise NotImplementedError("vecchia runs on one device: the row-sharded mode (args['process_group']) stays with the dense GP")
+        if self.y_data.shape[1] != 1:
+            raise NotImplementedError("vecchia takes one column of y (fvGP / x_out: the dense GP has it)")
+        if (x_data is None) != (y_data is None):
+            raise Exception("x_data and y_data come together")
+        if x_data is None:
+            x_data, y_data = self.x_data, self.y_data[:, 0]
+            if noise_variances is None:
+                noise_variances = self.noise_variances
+        return VecchiaGP(x_data, y_data, self._hps.copy(), noise_variances=noise_variances, kernel_function=self._native,
+                         n_neighbors=n_neighbors, **kw)

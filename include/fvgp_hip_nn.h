@@ -1,0 +1,85 @@
+/*
+ * fvgp_hip_nn.h -- the nearest-neighbour (Vecchia / NNGP "response") entries of libfvgp_hip.so (csrc/nn.hip).
+ *
+ * The likelihood of n points as a product of n small conditionals, p(y) ~ prod_i p(y_i | y_c(i)), c(i) the m nearest of the points
+ * that come earlier in the ordering; prediction at x* conditions on the m nearest data points.  O(n m^3) time, O(n m) memory, no
+ * iteration count and no standard error; with m >= n - 1 it is the exact likelihood.
+ *
+ * The conventions of fvgp_hip.h hold: fp64, row-major, device pointers unless the parameter says "host", 0 / -k / >= 1000 as return
+ * value.  Every call here synchronises the stream except fvgp_hip_nn_search.  No call allocates device memory.
+ */
+#ifndef FVGP_HIP_NN_H
+#define FVGP_HIP_NN_H
+
+#include "fvgp_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define FVGP_NN_MAX_NEIGHBORS 64   /* most neighbours per row (one lane of a wavefront each) */
+
+/* which call fvgp_hip_nn_workspace_bytes sizes */
+#define FVGP_NN_SEARCH 0
+#define FVGP_NN_CONDITIONALS 1
+#define FVGP_NN_LOGLIK 2
+
+/* Exact brute-force m-nearest neighbours.  xq (nq, d) query rows, xr (nr, d) reference rows, scales_host NULL or d positive numbers:
+ * the distance of query i and reference j is  sum_k ((xq[i][k] - xr[j][k]) * (1 / scales[k]))^2  (no scales: 1), the products added by
+ * fused multiply-adds in ascending k.  c0 < 0: every reference row is a candidate of every query; c0 >= 0 (causal): the candidates of
+ * query i are the reference rows j < min(nr, c0 + i) -- c0 = 0 with xq == xr is the likelihood's structure, c0 = n_old with the appended
+ * rows as queries the append, c0 < 0 prediction.
+ * idx_out (nq, ld >= m) int32: row i receives its min(m, candidates) nearest candidates sorted by (distance, index) ascending -- ties
+ * go to the lower index -- then -1 up to column m; columns m .. ld are not written.
+ * BIT CONTRACT: a row is a function of its query, the reference rows, the scales, m and its candidate count alone.
+ * Cost O(nq nr d): one wavefront per 64 queries walks every candidate; more than 65536 queries go in several launches.  Asynchronous.
+ * Errors: -1 h, -2 xq, -3 nq < 1, -4 xr, -5 nr < 1 or past 2^31 - 1, -6 d outside 1 .. FVGP_MAX_DIM, -7 a scale that is not positive and
+ * finite, -8 m outside 1 .. FVGP_NN_MAX_NEIGHBORS, -10 idx_out, -11 ld < m. */
+int fvgp_hip_nn_search(fvgp_handle *h, const double *xq, int64_t nq, const double *xr, int64_t nr, int d, const double *scales_host,
+                       int m, int64_t c0, int *idx_out, int64_t ld);
+
+/* The conditionals.  For query row i with the neighbour list c = idx[i][0 .. m) (entries outside 0 .. nr - 1, the -1 of the search among
+ * them, are skipped) and each of the B rows theta_b of thetas_host (B, ntheta):
+ *     A = K(x_c, x_c) + diag(v_c),  k = K(x_c, x_i),  A = L L^T,  w = L^-1 k,  z = L^-1 r_c,
+ *     mu[b][i] = w^T z,     var[b][i] = (k(x_i, x_i) + s_i) - w^T w
+ * r (nr): the caller's centred data on the reference rows, v (nr): their noise, s_or_null (nq): a per-query addend (the row's own noise
+ * in the likelihood, nothing or the prediction noise in prediction).  mu, var (B, nq).  A row without neighbours gives mu = 0,
+ * var = k(x, x) + s.  Kernel entries are computed by the operations of the covariance assembly.
+ * One wavefront per (row, b): the block padded with identity to 16, 32 or 64 rows by m alone, a lane per row, column by column, both
+ * substitutions inside the factorisation, w^T z and w^T w by a halving tree over the lanes.
+ * BIT CONTRACT: mu[b][i], var[b][i] are functions of (x_i, s_i, the listed rows in their listed order, theta_b, m) alone: not of nq, B,
+ * or the position in either.
+ * A pivot that is not positive gives mu = var = NaN for that (b, i); nothing traps.  info_host: 0, or 1 + b nq + i of the first
+ * (b, i) in that order whose var is not positive (NaN included).
+ * work: device, 8-byte aligned, fvgp_hip_nn_workspace_bytes(FVGP_NN_CONDITIONALS, nq, B) bytes.
+ * Errors: -1 h, -2 unknown kernel_id, -3 xq, -4 nq < 1, -5 xr, -6 nr < 1 or past 2^31 - 1, -7 d outside 1 .. FVGP_MAX_DIM, -8 thetas_host,
+ * -9 too few hyperparameters, -10 B outside 1 .. 65535, -11 idx, -12 ld < m, -13 m outside 1 .. FVGP_NN_MAX_NEIGHBORS, -14 r, -15 v,
+ * -17 mu, -18 var, -19 work NULL or misaligned, -20 work_bytes too small, -21 info_host. */
+int fvgp_hip_nn_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t nq, const double *xr, int64_t nr, int d,
+                             const double *thetas_host, int ntheta, int B, const int *idx, int64_t ld, int m,
+                             const double *r, const double *v, const double *s_or_null, double *mu, double *var,
+                             double *work, int64_t work_bytes, int64_t *info_host);
+
+/* The likelihood: the conditionals of x (n, d) on itself (idx from fvgp_hip_nn_search with c0 = 0, s = v), then per b
+ *     out_host[b] = { log p, fit, logdet },  fit = sum_i (r_i - mu_i)^2 / var_i,  logdet = sum_i log var_i,
+ *     log p = -1/2 (fit + logdet + n log 2 pi).
+ * mu, var (B, n) keep the per-row conditionals (the approximation's residual diagnostics).
+ * The sums run in a fixed order: slices of 256 rows added by a halving tree, the slices to 0 in ascending order.  The same call
+ * gives the same bits, and row b's values do not depend on B.  Rows with info (see above) make the sums NaN.
+ * work: fvgp_hip_nn_workspace_bytes(FVGP_NN_LOGLIK, n, B) bytes.
+ * Errors: -1 h, -2 unknown kernel_id, -3 x, -4 n < 1 or past 2^31 - 1, -5 d outside 1 .. FVGP_MAX_DIM, -6 thetas_host, -7 too few
+ * hyperparameters, -8 B outside 1 .. 65535, -9 idx, -10 ld < m, -11 m outside 1 .. FVGP_NN_MAX_NEIGHBORS, -12 r, -13 v, -14 mu, -15 var,
+ * -16 work NULL or misaligned, -17 work_bytes too small, -18 out_host, -19 info_host. */
+int fvgp_hip_nn_loglik(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *thetas_host, int ntheta, int B,
+                       const int *idx, int64_t ld, int m, const double *r, const double *v, double *mu, double *var,
+                       double *work, int64_t work_bytes, double *out_host, int64_t *info_host);
+
+/* bytes of the caller-owned `work` of the call `what` (FVGP_NN_SEARCH: 0, it takes none) for nq query rows and B hyperparameter
+ * vectors: the theta table (B (1 + FVGP_MAX_DIM) doubles) and the info word; for the likelihood also two sums per (b, slice of 256
+ * rows) and the three results per b.  -1 for an unknown `what`, nq < 1 or B < 1. */
+int64_t fvgp_hip_nn_workspace_bytes(int what, int64_t nq, int B);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
