@@ -192,6 +192,9 @@ _ABI_NN = {
                                        c_p, c_l, P_l]),
     "fvgp_hip_nn_loglik": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_l, P_d, P_l]),
     "fvgp_hip_nn_workspace_bytes": (c_l, [c_i, c_l, c_i]),
+    "fvgp_hip_nn_loglik_grad": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_l, P_d, P_d,
+                                      P_l]),
+    "fvgp_hip_nn_grad_workspace_bytes": (c_l, [c_l, c_i, c_i]),
 }
 SYMBOLS_NN = list(_ABI_NN)
 NN_MAX_NEIGHBORS = 64     # FVGP_NN_MAX_NEIGHBORS
@@ -352,6 +355,12 @@ def nn_workspace_bytes(what, nq, B=1):
     """bytes of the caller-owned workspace of Handle.nn_conditionals (what = NN_CONDITIONALS) / nn_loglik (NN_LOGLIK) for nq rows and B
     hyperparameter vectors (fvgp_hip_nn_workspace_bytes; NN_SEARCH takes none: 0); -1 for bad arguments"""
     return _workspace_bytes("fvgp_hip_nn_workspace_bytes", what, nq, B)
+
+
+def nn_grad_workspace_bytes(n, B=1, ntheta=2):
+    """bytes of the caller-owned workspace of Handle.nn_loglik_grad for n rows, B hyperparameter vectors of ntheta numbers
+    (fvgp_hip_nn_grad_workspace_bytes); -1 for bad arguments"""
+    return _workspace_bytes("fvgp_hip_nn_grad_workspace_bytes", n, B, ntheta)
 
 
 def loglik_hess_workspace_bytes(n, d):
@@ -1023,6 +1032,23 @@ class Handle(DistCalls):
                    _ptr(idx), idx.stride(0), int(m), _ptr(r), _ptr(v), _ptr(mu), _ptr(var), _ptr(work), work.numel() * 8,
                    out.ctypes.data_as(P_d), ctypes.byref(info))
         return out, int(info.value)
+
+    def nn_loglik_grad(self, kernel_id, x, thetas, idx, m, r, v, mu, var, score, work=None):
+        """fvgp_hip_nn_loglik_grad: nn_loglik and the exact gradient.  score (B, n, ntheta) device tensor <- every row's
+        d log p(y_i | y_c(i)) / d theta.  Returns (out (B, 3) as nn_loglik, grad (B, ntheta) ndarray = d log p / d theta, info).
+        Synchronous."""
+        n = x.shape[0]
+        t, B = self._nn_operands("nn_loglik_grad", thetas, idx, n, m, mu, var)
+        if not score.is_contiguous() or score.numel() < B * n * t.shape[1]:
+            raise ValueError(f"nn_loglik_grad: score must be a contiguous (B, n, ntheta) tensor, got {tuple(score.shape)}")
+        if work is None:
+            work = self.empty(max(1, nn_grad_workspace_bytes(n, B, t.shape[1])) // 8)
+        out, grad = np.empty((B, 3), dtype=np.float64), np.empty((B, t.shape[1]), dtype=np.float64)
+        info = ctypes.c_int64(0)
+        self._call("fvgp_hip_nn_loglik_grad", int(kernel_id), _ptr(x), n, x.shape[1], t.ctypes.data_as(P_d), t.shape[1], B,
+                   _ptr(idx), idx.stride(0), int(m), _ptr(r), _ptr(v), _ptr(mu), _ptr(var), _ptr(score), _ptr(work), work.numel() * 8,
+                   out.ctypes.data_as(P_d), grad.ctypes.data_as(P_d), ctypes.byref(info))
+        return out, grad, int(info.value)
 
     def posterior_prepare(self, L, n):
         """enqueue the inverted diagonal blocks the posterior's sweep substitutes with (fvgp_hip_posterior_prepare)"""

@@ -11,6 +11,9 @@
 //     r_c, a register each) are substituted in the same step.  Padded lanes are identity rows.
 // fvgp_hip_nn_loglik        the conditionals on the data itself, then the two sums: slices of 256 rows by a halving tree in LDS, the
 //     slices to 0 in ascending order by one thread per b.  No atomics anywhere.
+// fvgp_hip_nn_loglik_grad   the same and the exact gradient in theta: the GRAD variant of the conditionals kernel goes on from
+//     the factor in LDS (a backward pass for A^-1 k and A^-1 r_c, one more sweep over the block's entries with their derivatives) and
+//     writes every row's score; the scores are summed per hyperparameter like the likelihood's terms.
 #include "radial.h"
 #include "kernel_family.h"
 #include "../../include/fvgp_hip_nn.h"
@@ -138,9 +141,15 @@ struct NcArgs {
     double *mu, *var;
     long nq, nr, ld;
     int d, m;
+    double *score;                                 // GRAD: (B, nq, nth), the row's d log p(y_i | y_c) / d theta
+    int nth, iso;                                  // GRAD: columns of score; one length scale for every dimension
 };
 
-template <int KIND, int D, int M>   // D == 0: runtime dimension; M: the padded block, m <= M
+// GRAD: the likelihood's conditionals (xq == xr, s == v) and each row's score.  Everything up to mu and var is the value kernel's code,
+// the same operations in the same order; the factor is still in LDS when they are done, and the score needs no second factorisation:
+// a = L^-T w = A^-1 k and beta = L^-T z = A^-1 r_c by one backward pass, then one more sweep over the kernel entries of the block of
+// (c, i) with their derivatives, each weighted by b_p q_q' + b_q' q_p (include/fvgp_hip_nn.h has the formula).
+template <int KIND, int D, int M, bool GRAD>   // D == 0: runtime dimension; M: the padded block, m <= M
 __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
     constexpr int DD = D ? D : FVGP_MAX_DIM;
     constexpr int TRI = M * (M + 1) / 2;
@@ -192,6 +201,7 @@ __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
 
     // factorisation and both substitutions
     bool fail = false;
+    double linv = 1.0;                             // GRAD: 1 / L_ll (the diagonal slots of sm keep A's diagonal)
     for (int j = 0, col = 0; j < M; col += M - j - 1, ++j) {
         const int lr = lane < j ? j : (lane < M ? lane : M - 1);       // (lanes outside the column repeat a row of it: every read stays inside the triangle)
         double sacc = sm[col + lr];
@@ -201,6 +211,7 @@ __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
         const double ljj = sqrt(p), inv = 1.0 / ljj;
         const double lc = sacc * inv;
         if (lane > j && lane < M) sm[col + lane] = lc;
+        if (GRAD && lane == j) linv = inv;
         const double wj = lane_value(tw, j) * inv, zj = lane_value(tz, j) * inv;
         if (lane == j) { tw = wj; tz = zj; }
         else if (lane > j) { tw = fma(-lc, wj, tw); tz = fma(-lc, zj, tz); }
@@ -213,6 +224,65 @@ __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
         if (a.s) kxx += a.s[row];
         a.mu[b * a.nq + row] = fail ? NAN : mu;
         a.var[b * a.nq + row] = fail ? NAN : kxx - ww;
+    }
+    if constexpr (GRAD) {
+        // L^T a = w and L^T beta = z in one pass, outer-product form: step j takes a_j, beta_j from lane j and the lanes l < j subtract
+        // L[j][l] times them (row j of the factor: lane l reads its own column at row j).  No reduction, the order is j = M - 1 .. 0.
+        const int mycol = lane * M - lane * (lane + 1) / 2;      // (only lanes < j <= M - 1 read)
+        double ta = tw, tb = tz;
+        for (int j = M - 1; j >= 0; --j) {
+            const double aj = lane_value(ta * linv, j), bj = lane_value(tb * linv, j);
+            if (lane == j) { ta = aj; tb = bj; }
+            else if (lane < j) { const double l = sm[mycol + j]; ta = fma(-l, aj, ta); tb = fma(-l, bj, tb); }
+        }
+        double kxx = radial<KIND>(0.0, sig);
+        if (a.s) kxx += a.s[row];
+        const double dv = kxx - lane_value(ww, 0), e = a.r[row] - lane_value(mu, 0);
+        const double ed = e / dv, c2 = 0.5 * (ed * ed - 1.0 / dv);
+        // b = (-a, 1), q = (e / d) (beta, 0) + c2 b: this lane's entries; the entry of x_i itself is (1, c2)
+        const double bl = -ta, ql = fma(ed, tb, c2 * bl);
+        double acc[1 + DD];
+#pragma unroll
+        for (int k = 0; k <= DD; ++k) acc[k] = 0.0;
+        const bool iso = a.iso != 0;
+        // column j < M: the entries (l, j), l > j, of the neighbours' block; column M: those of (l, i).  Lanes without a neighbour and
+        // columns without one take no part.
+        for (int j = 0; j <= M; ++j) {
+            const bool self = j == M;
+            const int jl = self ? 0 : j;           // (a lane to read that exists; its values are not used for x_i's column)
+            if (!self && !((vmask >> j) & 1ull)) continue;
+            const double wgt = self ? fma(bl, c2, ql) : fma(bl, lane_value(ql, jl), lane_value(bl, jl) * ql);
+            double ek[DD], r2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < DD; ++k) {
+                ek[k] = 0.0;
+                if (k < d) { ek[k] = (u[k] - (self ? xi[k] : lane_value(u[k], jl))) * il[k]; r2 = fma(ek[k], ek[k], r2); }
+            }
+            double phi, cf;
+            radial_grad<KIND>(r2, sig, phi, cf);
+            if (valid && (self || lane > j)) {
+                acc[0] = fma(wgt, phi, acc[0]);
+                const double wc = wgt * cf;
+                if (iso) acc[1] = fma(wc, r2 * il[0], acc[1]);
+                else {
+#pragma unroll
+                    for (int k = 0; k < DD; ++k)
+                        if (k < d) acc[1 + k] = fma(wc, ek[k] * ek[k] * il[k], acc[1 + k]);
+                }
+            }
+        }
+        if (valid) acc[0] = fma(bl, ql, acc[0]);   // the diagonal: d Sigma[p][p] = 1 for sigma^2, 0 for the length scales
+        const int np = iso ? 2 : d + 1;
+        double *out = a.score + (b * a.nq + row) * a.nth;
+#pragma unroll
+        for (int h = 0; h <= DD; ++h)
+            if (h < np) {
+                double s = wave_tree_sum(acc[h]);
+                if (h == 0) s += c2;               // the diagonal entry of x_i itself
+                if (lane == 0) out[h] = fail ? NAN : s;
+            }
+        if (lane == 0)
+            for (int h = np; h < a.nth; ++h) out[h] = 0.0;
     }
 }
 
@@ -268,6 +338,34 @@ __global__ __launch_bounds__(64) void nn_total_kernel(const double *part, long n
     out[b * 3 + 2] = l;
 }
 
+// the same pair for ncol columns per row (the scores): part[(b * nslices + slice) * ncol + c] = the slice's sum of src[b][i][c] by the
+// same halving tree over 256 rows ...
+__global__ __launch_bounds__(NN_SUM_ROWS) void nn_col_terms_kernel(const double *src, long n, int ncol, double *part) {
+    __shared__ double sf[NN_SUM_ROWS];
+    const int tid = threadIdx.x;
+    const long i = (long)blockIdx.x * NN_SUM_ROWS + tid, b = blockIdx.y;
+    for (int c = 0; c < ncol; ++c) {
+        sf[tid] = i < n ? src[(b * n + i) * ncol + c] : 0.0;
+        __syncthreads();
+        for (int off = NN_SUM_ROWS / 2; off > 0; off >>= 1) {
+            if (tid < off) sf[tid] += sf[tid + off];
+            __syncthreads();
+        }
+        if (tid == 0) part[(b * gridDim.x + blockIdx.x) * ncol + c] = sf[0];
+        __syncthreads();                           // (sf[0] has been read before the next column overwrites it)
+    }
+}
+
+// ... and out[b][c] = the slices added to 0 in ascending order, one thread per (b, c)
+__global__ __launch_bounds__(64) void nn_col_total_kernel(const double *part, long nslices, int ncol, long count, double *out) {
+    const long e = (long)blockIdx.x * 64 + threadIdx.x;
+    if (e >= count) return;
+    const long b = e / ncol, c = e - b * ncol;
+    double s = 0.0;
+    for (long sl = 0; sl < nslices; ++sl) s += part[(b * nslices + sl) * ncol + c];
+    out[e] = s;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host side
 inline int64_t nn_slices(int64_t n) { return (n + NN_SUM_ROWS - 1) / NN_SUM_ROWS; }
 // work, in doubles: [0] the info word, [2 ..) the theta table, then (likelihood) the results and the slices' sums
@@ -279,11 +377,16 @@ inline int64_t nn_work_doubles(int what, int64_t nq, int B) {
     if (what == FVGP_NN_CONDITIONALS) return nn_out_off(B);
     return nn_part_off(B) + 2 * (int64_t)B * nn_slices(nq);
 }
+// the gradient call: the likelihood's work, then the B x ntheta gradient and the scores' sums per (b, slice, column)
+inline int64_t nn_grad_off(int64_t n, int B) { return even_up(nn_work_doubles(FVGP_NN_LOGLIK, n, B)); }
+inline int64_t nn_gpart_off(int64_t n, int B, int ntheta) { return nn_grad_off(n, B) + even_up((int64_t)B * ntheta); }
+inline int64_t nn_grad_work_doubles(int64_t n, int B, int ntheta) { return nn_gpart_off(n, B, ntheta) + (int64_t)B * nn_slices(n) * ntheta; }
 
-// the theta table of B hyperparameter vectors into work, the conditionals over it and the info word; nothing is read back
+// the theta table of B hyperparameter vectors into work, the conditionals over it and the info word; nothing is read back.
+// score: NULL, or (B, nq, ntheta) for the gradient variant of the kernel (the likelihood's structure only: xq == xr, s == v)
 int nn_run_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t nq, const double *xr, int64_t nr, int d,
                         const double *thetas, int ntheta, int B, const int *idx, int64_t ld, int m, const double *r, const double *v,
-                        const double *s, double *mu, double *var, double *work) {
+                        const double *s, double *mu, double *var, double *work, double *score = nullptr) {
     std::vector<double> tab((size_t)B * NN_TAB);
     KmatDesc k{};
     for (int b = 0; b < B; ++b) {
@@ -298,10 +401,14 @@ int nn_run_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t
     NcArgs a;
     a.xq = xq; a.xr = xr; a.r = r; a.v = v; a.s = s; a.tab = tab_dev; a.idx = idx; a.mu = mu; a.var = var;
     a.nq = nq; a.nr = nr; a.ld = ld; a.d = d; a.m = m;
+    a.score = score; a.nth = ntheta; a.iso = KERNEL_FAMILY[kernel_id].iso ? 1 : 0;
     const dim3 grid((unsigned)((nq + NN_WAVES - 1) / NN_WAVES), (unsigned)B), block(64 * NN_WAVES);
     dispatch_kind_dim(k.kind, d, [&](auto KIND, auto D) {
         dispatch_pad(m, [&](auto M) {
-            hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value>), grid, block, 0, h->stream, a);
+            if (score)
+                hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value, true>), grid, block, 0, h->stream, a);
+            else
+                hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value, false>), grid, block, 0, h->stream, a);
         });
     });
     HIPCHK(hipGetLastError());
@@ -420,6 +527,55 @@ int fvgp_hip_nn_loglik(fvgp_handle *h, int kernel_id, const double *x, int64_t n
     long long info = 0;
     HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(out_host, out, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *info_host = info;
+    return 0;
+}
+
+int64_t fvgp_hip_nn_grad_workspace_bytes(int64_t n, int B, int ntheta) {
+    if (n < 1 || B < 1 || ntheta < 1) return -1;
+    return nn_grad_work_doubles(n, B, ntheta) * (int64_t)sizeof(double);
+}
+
+int fvgp_hip_nn_loglik_grad(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *thetas_host, int ntheta, int B,
+                            const int *idx, int64_t ld, int m, const double *r, const double *v, double *mu, double *var, double *score,
+                            double *work, int64_t work_bytes, double *out_host, double *grad_host, int64_t *info_host) {
+    if (!h) return -1;
+    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
+    if (!x) return -3;
+    if (n < 1 || n > 0x7fffffffLL) return -4;
+    int rc = check_kernel_args(kernel_id, d, thetas_host, ntheta, 5, 6, 7); if (rc) return rc;
+    if (B < 1 || B > 65535) { fvgp_set_error("nn_loglik_grad: 1 .. 65535 hyperparameter vectors per call"); return -8; }
+    if (!idx) return -9;
+    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error("nn_loglik_grad: 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -11; }
+    if (ld < m) return -10;
+    if (!r) return -12;
+    if (!v) return -13;
+    if (!mu) return -14;
+    if (!var) return -15;
+    if (!score) return -16;
+    if (!work || ((uintptr_t)work & 7)) return -17;
+    if (work_bytes < nn_grad_work_doubles(n, B, ntheta) * (int64_t)sizeof(double)) {
+        fvgp_set_error("nn_loglik_grad: work smaller than fvgp_hip_nn_grad_workspace_bytes(n, B, ntheta)"); return -18;
+    }
+    if (!out_host) return -19;
+    if (!grad_host) return -20;
+    if (!info_host) return -21;
+    HIPCHK(hipSetDevice(h->device));
+    rc = nn_run_conditionals(h, kernel_id, x, n, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, v, mu, var, work, score);
+    if (rc) return rc;
+    const int64_t ns = nn_slices(n);
+    double *out = work + nn_out_off(B), *part = work + nn_part_off(B);
+    double *grad = work + nn_grad_off(n, B), *gpart = work + nn_gpart_off(n, B, ntheta);
+    HIPLAUNCH(nn_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, r, (const double *)mu, (const double *)var, (long)n, part);
+    HIPLAUNCH(nn_total_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), h->stream, (const double *)part, (long)ns, (long)n, B, out);
+    HIPLAUNCH(nn_col_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, (const double *)score, (long)n, ntheta, gpart);
+    const long count = (long)B * ntheta;
+    HIPLAUNCH(nn_col_total_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), h->stream, (const double *)gpart, (long)ns, ntheta, count, grad);
+    long long info = 0;
+    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(out_host, out, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(grad_host, grad, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *info_host = info;
     return 0;

@@ -12,12 +12,19 @@ values as m grows.  Prediction at x* conditions on the m nearest data points: th
 
     big = VecchiaGP(x_all, y_all, hps, noise_all, n_neighbors=32)         # or gp.vecchia(x_all, y_all, noise_all)
     big.log_likelihood(); big.train(bounds, method="mcmc")
+    f, g = big.neg_log_likelihood_and_gradient(); big.train_gradient(bounds, method="local")
     big.posterior_mean(x_pred); big.posterior_covariance(x_pred, variance_only=True)
 
 "Nearest" is measured after dividing every coordinate by a scale (args["neighbor_scales"]: the length scales at construction, 1, or a
 vector), and the neighbour lists stay FIXED while the hyperparameters move (set_hyperparameters, training): the likelihood is then a
-smooth function of theta.  refresh_neighbors() rebuilds them.  The gradient of this likelihood, a tree search, a maxmin ordering and
-joint covariances are not built."""
+smooth function of theta.  refresh_neighbors() rebuilds them.
+
+The exact gradient of this likelihood comes from the same device call as its value (fvgp_hip_nn_loglik_grad: two back-substitutions with
+the m x m factor that is already there, and one more sweep over each block's kernel entries with their derivatives):
+neg_log_likelihood_and_gradient, its _batch forms, conditional_scores (the per-point terms that sum to it) and train_gradient ("local":
+scipy's bounded optimisers, "adam": projected Adam, multi-start with args["adam_starts"]) are always there.  The fvgp.GP names
+neg_log_likelihood_gradient and train(method="local" | "adam") take this route with args={"likelihood_gradient": True}.  A tree search, a
+maxmin ordering and joint covariances are not built."""
 import warnings
 
 import numpy as np
@@ -39,7 +46,10 @@ class VecchiaGP:
     n_neighbors: m in 1 .. 64.  ordering: "random" (a permutation drawn from `seed`), "given" (the caller's order) or a permutation
     array; the data are held in that order and everything returned per data point is in the CALLER's order.  args:
     "neighbor_scales" = "lengthscales" (default: the kernel's length scales at construction), "unit" or a D-vector;
-    "batch_population" (True: train(method="global") scores a generation in one device call)."""
+    "batch_population" (True: train(method="global") scores a generation in one device call); "likelihood_gradient" (True: the fvgp.GP
+    names neg_log_likelihood_gradient and train(method="local" | "adam") run the exact gradient); "adam_starts" (S >= 2:
+    train_gradient(method="adam") runs S trajectories in lockstep on the batched gradient); "grad_batch_bytes" (default 1 GiB: the most
+    device memory one batched gradient call may take for its per-row outputs)."""
 
     def __init__(self, x_data, y_data, hyperparameters, noise_variances=None, kernel_function="matern32_ard", n_neighbors=32,
                  ordering="random", seed=0, args=None):
@@ -58,6 +68,7 @@ class VecchiaGP:
             raise NotImplementedError("the row-sharded mode (args['process_group']) belongs to the dense fvgp_amd.GP: the "
                                       "nearest-neighbour path runs on one device")
         self.args.setdefault("batch_population", True)
+        self.likelihood_gradient = bool(self.args.get("likelihood_gradient", False))
         if int(n_neighbors) != n_neighbors or not 1 <= int(n_neighbors) <= _lib.NN_MAX_NEIGHBORS:
             raise ValueError(f"n_neighbors must lie in 1 .. {_lib.NN_MAX_NEIGHBORS}, got {n_neighbors!r}")
         self.n_neighbors = int(n_neighbors)
@@ -233,6 +244,58 @@ class VecchiaGP:
         lp = -0.5 * ((r - mu) ** 2 / var + np.log(var) + _LOG_2PI)
         return {"mean": self._unorder(self._m + mu), "variance": self._unorder(var), "log_predictive": self._unorder(lp)}
 
+    # ---- the gradient --------------------------------------------------------------------------------------------------------
+    def _loglik_grad(self, thetas):
+        """(out (B, 3), grad (B, H) = d log p / d theta, info, score (B, n, H) device) of one device call at the rows of thetas"""
+        H, n = self._H, self.point_number
+        B, nth = thetas.shape
+        mu, var = H.empty(B, n), H.empty(B, n)
+        score = H.torch.empty((B, n, nth), dtype=H.torch.float64, device=mu.device)
+        out, grad, info = H.nn_loglik_grad(self._native.kernel_id, self._x_dev, thetas, self._idx, self.n_neighbors, self._r_dev,
+                                           self._V_dev, mu, var, score)
+        return out, grad, info, score
+
+    def neg_log_likelihood_and_gradient(self, hyperparameters=None):
+        """(f, g (H,)): the negative nearest-neighbour log-likelihood and its exact gradient from one device call; deterministic, the
+        same bits on every call"""
+        out, grad, info, _ = self._loglik_grad(self._one(hyperparameters))
+        if info:
+            raise self._not_pd(info, self.point_number, "neg_log_likelihood_and_gradient")
+        return -float(out[0, 0]), -grad[0]
+
+    def _grad_chunk(self, nth):
+        """hyperparameter vectors per device call: mu, var and score of a call stay under args["grad_batch_bytes"]"""
+        cap = int(self.args.get("grad_batch_bytes", 1 << 30))
+        return int(max(1, min(65535, cap // (8 * self.point_number * (2 + nth)))))
+
+    def neg_log_likelihood_and_gradient_batch(self, thetas):
+        """(f (B,), G (B, H)) at the B rows of `thetas`, each row equal bit for bit to neg_log_likelihood_and_gradient(thetas[b]); the
+        batch goes in chunks whose per-row outputs fit args["grad_batch_bytes"].  Where a conditional is not positive definite the value
+        is +inf and the gradient NaN."""
+        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+        assert thetas.ndim == 2 and thetas.shape[1] == len(self._hps), "thetas must be (B, number of hyperparameters)"
+        f, G = np.empty(len(thetas)), np.empty(thetas.shape)
+        step = self._grad_chunk(thetas.shape[1])
+        for a in range(0, len(thetas), step):
+            out, grad, _, _ = self._loglik_grad(thetas[a:a + step])
+            f[a:a + step], G[a:a + step] = -out[:, 0], -grad
+        bad = np.isnan(f)
+        G[bad] = np.nan
+        return np.where(bad, np.inf, f), G
+
+    def neg_log_likelihood_gradient_batch(self, thetas):
+        return self.neg_log_likelihood_and_gradient_batch(thetas)[1]
+
+    def conditional_scores(self, hyperparameters=None):
+        """(N, H), in the caller's order: row i is d log p(y_i | its neighbours) / d theta, the per-point terms that sum to the gradient
+        of log_likelihood (diagnostics, and the raw material of minibatch methods)"""
+        out, grad, info, score = self._loglik_grad(self._one(hyperparameters))
+        if info:
+            raise self._not_pd(info, self.point_number, "conditional_scores")
+        s = np.empty((self.point_number, score.shape[2]))
+        s[self.ordering] = score[0].cpu().numpy()
+        return s
+
     # ---- prediction ----------------------------------------------------------------------------------------------------------
     def _check_pred(self, x_pred, x_out=None):
         if x_out is not None:
@@ -302,17 +365,82 @@ class VecchiaGP:
 
     # ---- training ----------------------------------------------------------------------------------------------------------------
     def neg_log_likelihood_gradient(self, hyperparameters=None, component=0):
-        raise NotImplementedError("neg_log_likelihood_gradient: the exact gradient of the nearest-neighbour likelihood is not built yet; "
-                                  "train with method='mcmc' or 'global', or take gradients from the dense fvgp_amd.GP on a subset")
+        """with args={"likelihood_gradient": True}: the exact gradient (H,) of neg_log_likelihood"""
+        if not self.likelihood_gradient:
+            raise NotImplementedError("neg_log_likelihood_gradient: under this fvgp.GP name the exact gradient of the nearest-neighbour "
+                                      "likelihood is not built yet -- the name answers only with args={'likelihood_gradient': True}; "
+                                      "neg_log_likelihood_and_gradient, conditional_scores and train_gradient are always there")
+        return self.neg_log_likelihood_and_gradient(hyperparameters)[1]
+
+    def train_gradient(self, hyperparameter_bounds, init_hyperparameters=None, method="local", local_optimizer="L-BFGS-B", max_iter=200,
+                       tolerance=1e-4, lr=1e-2, info=False, seed=None):
+        """Training on the exact gradient, the neighbour lists fixed throughout.  "local": gp_training.train's scipy route with this
+        object's value and gradient as the objective (one device call serves both).  "adam": gp_training.adam_optimize with every iterate
+        clipped into the bounds; with args["adam_starts"] = S >= 2, S trajectories in lockstep (adam_optimize_batch) on the batched value
+        and gradient, the first from init_hyperparameters, the others uniform in the bounds from `seed`, the best end point kept
+        (adam_multistart_info).  adam_history keeps the iterates.  Ends with set_hyperparameters(theta) and returns theta."""
+        if method not in ("local", "adam"):
+            raise ValueError(f"train_gradient: method must be 'local' or 'adam', got {method!r}")
+        bounds = np.asarray(hyperparameter_bounds, dtype=np.float64)
+        assert bounds.ndim == 2 and bounds.shape == (len(self._hps), 2), "wrong bounds format"
+        theta0 = np.array(self._hps if init_hyperparameters is None else init_hyperparameters, dtype=np.float64)
+        if np.any(theta0 < bounds[:, 0]) or np.any(theta0 > bounds[:, 1]):
+            raise Exception("Starting positions outside of optimization bounds.", theta0, bounds)
+        last = {}
+
+        def evaluate(theta):
+            key = np.asarray(theta, dtype=np.float64).tobytes()
+            if last.get("key") != key:
+                last["key"], last["value"] = key, self.neg_log_likelihood_and_gradient(np.asarray(theta, dtype=np.float64))
+            return last["value"]
+
+        clip = lambda t: np.clip(t, bounds[:, 0], bounds[:, 1])      # noqa: E731
+        starts = int(self.args.get("adam_starts", 0) or 0)
+        if method == "local":
+            hps = _training.train(self, bounds, theta0, method="local", tolerance=tolerance, max_iter=max_iter,
+                                  local_optimizer=local_optimizer, info=info, objective_function=lambda t: evaluate(t)[0],
+                                  objective_function_gradient=lambda t: evaluate(t)[1])
+        elif starts >= 2:
+            x0 = _training.adam_start_points(theta0, bounds, starts, seed)
+
+            def project(thetas, idx, fvals, grads, iteration):                # (the callback sees the optimiser's own array, after the step)
+                thetas[idx] = clip(thetas[idx])
+
+            xs, histories = _training.adam_optimize_batch(self.neg_log_likelihood_and_gradient_batch, x0, lr=lr, max_iter=max_iter,
+                                                          tol=tolerance, callback=project)
+            fx = self.neg_log_likelihood_batch(xs)
+            best = int(np.argmin(fx))
+            self.adam_history = histories[best]
+            self.adam_multistart_info = {"x0": x0, "x": xs, "f(x)": fx, "best": best}
+            hps = xs[best].copy()
+        else:
+            progress = None
+            if info:
+                def progress(theta, fval, grad, iteration):
+                    if iteration % 10 == 0 or iteration == 1:
+                        print(f"fvGP adam iteration {iteration} out of {max_iter}: f(x)= {float(fval)}, |grad|= {float(np.linalg.norm(grad))}")
+            hps, self.adam_history = _training.adam_optimize(lambda t: evaluate(t)[0], lambda t: evaluate(t)[1], theta0, lr=lr,
+                                                             max_iter=max_iter, tol=tolerance, callback=progress, project=clip)
+        self.set_hyperparameters(hps)
+        return hps
 
     def train(self, hyperparameter_bounds, init_hyperparameters=None, method="mcmc", pop_size=20, tolerance=1e-4, max_iter=1000,
               info=False, seed=None, constraints=(), mcmc_prior=None, mcmc_args=None, mcmc_prop_distrs="normal"):
         """gp_training.train on the deterministic likelihood with the value-only methods: "mcmc" (default), "global" (a generation of
-        the population in one device call unless args["batch_population"] is False) or a callable.  The neighbour lists stay fixed
+        the population in one device call unless args["batch_population"] is False) or a callable; with
+        args={"likelihood_gradient": True} also "local" and "adam", which run train_gradient.  The neighbour lists stay fixed
         throughout.  Ends with set_hyperparameters(theta) and returns theta."""
-        if method in ("local", "adam", "hgdl", "bo"):
-            raise NotImplementedError(f"train(method={method!r}) needs a gradient, and the exact gradient of the nearest-neighbour "
-                                      "likelihood is not built yet: 'mcmc', 'global' or a callable run here")
+        if method in ("local", "adam") and self.likelihood_gradient:
+            return self.train_gradient(hyperparameter_bounds, init_hyperparameters, method=method, tolerance=tolerance, max_iter=max_iter,
+                                       info=info, seed=seed)
+        if method in ("hgdl", "bo"):
+            raise NotImplementedError(f"train(method={method!r}) needs HGDL / the BO surrogate loop; under this name the exact gradient of "
+                                      "the nearest-neighbour likelihood is not built yet for them: 'mcmc', 'global', a callable, and with "
+                                      "args={'likelihood_gradient': True} 'local' and 'adam' run here")
+        if method in ("local", "adam"):
+            raise NotImplementedError(f"train(method={method!r}) needs a gradient, and under this fvgp.GP name the exact gradient of the "
+                                      "nearest-neighbour likelihood is not built yet -- it answers only with "
+                                      "args={'likelihood_gradient': True}; train_gradient(bounds, method='local' | 'adam') is always there")
         bounds = np.asarray(hyperparameter_bounds, dtype=np.float64)
         assert bounds.ndim == 2 and bounds.shape == (len(self._hps), 2), "wrong bounds format"
         theta0 = np.array(self._hps if init_hyperparameters is None else init_hyperparameters, dtype=np.float64)

@@ -79,6 +79,34 @@ int fvgp_hip_nn_loglik(fvgp_handle *h, int kernel_id, const double *x, int64_t n
  * rows) and the three results per b.  -1 for an unknown `what`, nq < 1 or B < 1. */
 int64_t fvgp_hip_nn_workspace_bytes(int what, int64_t nq, int B);
 
+/* The likelihood and its exact gradient in the hyperparameters: fvgp_hip_nn_loglik, and per (b, row i) the score
+ *     score[b][i][h] = d/d theta_h log p(y_i | y_c(i)),      grad_host[b][h] = sum_i score[b][i][h] = d log p / d theta_h.
+ * No second factorisation: with the row's L still in place, a = L^-T w = A^-1 k and beta = L^-T z = A^-1 r_c (one backward pass for
+ * both, step j = M - 1 .. 0 taking a_j from lane j and the lanes l < j subtracting L[j][l] a_j), e = r_i - mu, d = var, the
+ * (m + 1)-vectors b = (-a, 1), g = (beta, 0),
+ *     q = (e / d) g + 1/2 (e^2 / d^2 - 1 / d) b,        score_h = b^T (dSigma / d theta_h) q,
+ * Sigma the kernel part of the joint covariance of (c, i) (the noise is no hyperparameter); as dSigma is symmetric the form is
+ * sum_{p > q'} (b_p q_q' + b_q' q_p) dSigma[p][q'] + sum_p b_p q_p dSigma[p][p], one more sweep over the (m + 1)(m + 2) / 2 entries, each
+ * evaluated with its derivative: dK / d sigma^2 = phi, dK / d l_k = cf e2[k] invl[k]; a kernel with one length scale for every dimension
+ * adds the d terms into it.  A row without neighbours has the sigma^2 term of d = k(x, x) + v alone.  score (B, n, ntheta) device:
+ * columns past the kernel's own hyperparameters receive 0.
+ * BIT CONTRACT: out_host, mu and var are bit for bit those of fvgp_hip_nn_loglik on the same inputs.  score[b][i][:] is a function of
+ * (x_i, v_i, the listed rows in their listed order, theta_b, m) alone: not of n, B, or the position in either.  The rows' scores are added
+ * as the likelihood's terms are (slices of 256 rows by a halving tree, the slices to 0 in ascending order, one thread per (b, h)): the
+ * same call gives the same bits, and row b of grad_host does not depend on B.
+ * A failed pivot gives NaN scores next to the NaN mu and var, and the same info; grad_host is then NaN.
+ * work: device, 8-byte aligned, fvgp_hip_nn_grad_workspace_bytes(n, B, ntheta) bytes.
+ * Errors: -1 h, -2 unknown kernel_id, -3 x, -4 n < 1 or past 2^31 - 1, -5 d outside 1 .. FVGP_MAX_DIM, -6 thetas_host, -7 too few
+ * hyperparameters, -8 B outside 1 .. 65535, -9 idx, -10 ld < m, -11 m outside 1 .. FVGP_NN_MAX_NEIGHBORS, -12 r, -13 v, -14 mu, -15 var,
+ * -16 score, -17 work NULL or misaligned, -18 work_bytes too small, -19 out_host, -20 grad_host, -21 info_host. */
+int fvgp_hip_nn_loglik_grad(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *thetas_host, int ntheta, int B,
+                            const int *idx, int64_t ld, int m, const double *r, const double *v, double *mu, double *var, double *score,
+                            double *work, int64_t work_bytes, double *out_host, double *grad_host, int64_t *info_host);
+
+/* bytes of the caller-owned `work` of fvgp_hip_nn_loglik_grad: the likelihood's, then the gradient per b and one sum per (b, slice of 256
+ * rows, hyperparameter).  -1 for n < 1, B < 1 or ntheta < 1. */
+int64_t fvgp_hip_nn_grad_workspace_bytes(int64_t n, int B, int ntheta);
+
 #ifdef __cplusplus
 }
 #endif
