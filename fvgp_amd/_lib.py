@@ -195,6 +195,9 @@ _ABI_NN = {
     "fvgp_hip_nn_loglik_grad": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_l, P_d, P_d,
                                       P_l]),
     "fvgp_hip_nn_grad_workspace_bytes": (c_l, [c_l, c_i, c_i]),
+    "fvgp_hip_nn_loglik_fisher": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, P_d,
+                                        P_d, P_d, P_l]),
+    "fvgp_hip_nn_fisher_workspace_bytes": (c_l, [c_l, c_i, c_i]),
 }
 SYMBOLS_NN = list(_ABI_NN)
 NN_MAX_NEIGHBORS = 64     # FVGP_NN_MAX_NEIGHBORS
@@ -361,6 +364,12 @@ def nn_grad_workspace_bytes(n, B=1, ntheta=2):
     """bytes of the caller-owned workspace of Handle.nn_loglik_grad for n rows, B hyperparameter vectors of ntheta numbers
     (fvgp_hip_nn_grad_workspace_bytes); -1 for bad arguments"""
     return _workspace_bytes("fvgp_hip_nn_grad_workspace_bytes", n, B, ntheta)
+
+
+def nn_fisher_workspace_bytes(n, B=1, ntheta=2):
+    """bytes of the caller-owned workspace of Handle.nn_loglik_fisher for n rows, B hyperparameter vectors of ntheta numbers
+    (fvgp_hip_nn_fisher_workspace_bytes); -1 for bad arguments"""
+    return _workspace_bytes("fvgp_hip_nn_fisher_workspace_bytes", n, B, ntheta)
 
 
 def loglik_hess_workspace_bytes(n, d):
@@ -1049,6 +1058,29 @@ class Handle(DistCalls):
                    _ptr(idx), idx.stride(0), int(m), _ptr(r), _ptr(v), _ptr(mu), _ptr(var), _ptr(score), _ptr(work), work.numel() * 8,
                    out.ctypes.data_as(P_d), grad.ctypes.data_as(P_d), ctypes.byref(info))
         return out, grad, int(info.value)
+
+    def nn_loglik_fisher(self, kernel_id, x, thetas, idx, m, r, v, mu, var, score, fisher_rows, work=None):
+        """fvgp_hip_nn_loglik_fisher: nn_loglik_grad and the Fisher information of the product of conditionals.  fisher_rows
+        (B, n, ntheta (ntheta + 1) / 2) device tensor <- every row's term, the packed lower triangle ((h, k <= h) at h (h + 1) / 2 + k).
+        Returns (out (B, 3) and grad (B, ntheta) as nn_loglik_grad, fisher (B, ntheta, ntheta) ndarray = the rows' sum, symmetric, info).
+        Synchronous."""
+        n = x.shape[0]
+        t, B = self._nn_operands("nn_loglik_fisher", thetas, idx, n, m, mu, var)
+        nth = t.shape[1]
+        if not score.is_contiguous() or score.numel() < B * n * nth:
+            raise ValueError(f"nn_loglik_fisher: score must be a contiguous (B, n, ntheta) tensor, got {tuple(score.shape)}")
+        if not fisher_rows.is_contiguous() or fisher_rows.numel() < B * n * (nth * (nth + 1) // 2):
+            raise ValueError("nn_loglik_fisher: fisher_rows must be a contiguous (B, n, ntheta (ntheta + 1) / 2) tensor, got "
+                             f"{tuple(fisher_rows.shape)}")
+        if work is None:
+            work = self.empty(max(1, nn_fisher_workspace_bytes(n, B, nth)) // 8)
+        out, grad = np.empty((B, 3), dtype=np.float64), np.empty((B, nth), dtype=np.float64)
+        fisher = np.empty((B, nth, nth), dtype=np.float64)
+        info = ctypes.c_int64(0)
+        self._call("fvgp_hip_nn_loglik_fisher", int(kernel_id), _ptr(x), n, x.shape[1], t.ctypes.data_as(P_d), nth, B,
+                   _ptr(idx), idx.stride(0), int(m), _ptr(r), _ptr(v), _ptr(mu), _ptr(var), _ptr(score), _ptr(fisher_rows), _ptr(work),
+                   work.numel() * 8, out.ctypes.data_as(P_d), grad.ctypes.data_as(P_d), fisher.ctypes.data_as(P_d), ctypes.byref(info))
+        return out, grad, fisher, int(info.value)
 
     def posterior_prepare(self, L, n):
         """enqueue the inverted diagonal blocks the posterior's sweep substitutes with (fvgp_hip_posterior_prepare)"""

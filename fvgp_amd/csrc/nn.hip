@@ -14,6 +14,9 @@
 // fvgp_hip_nn_loglik_grad   the same and the exact gradient in theta: the GRAD variant of the conditionals kernel goes on from
 //     the factor in LDS (a backward pass for A^-1 k and A^-1 r_c, one more sweep over the block's entries with their derivatives) and
 //     writes every row's score; the scores are summed per hyperparameter like the likelihood's terms.
+// fvgp_hip_nn_loglik_fisher the same and the Fisher information of the product of conditionals: the NN_FISHER mode of the kernel goes
+//     on after the score (a full-row sweep of derivatives, a forward pass with every right-hand side, the pairwise products) and writes
+//     every row's packed term; the terms are summed like the scores and the triangle is mirrored on the host.
 #include "radial.h"
 #include "kernel_family.h"
 #include "../../include/fvgp_hip_nn.h"
@@ -143,14 +146,24 @@ struct NcArgs {
     int d, m;
     double *score;                                 // GRAD: (B, nq, nth), the row's d log p(y_i | y_c) / d theta
     int nth, iso;                                  // GRAD: columns of score; one length scale for every dimension
+    double *fisher;                                // NN_FISHER: (B, nq, nth (nth + 1) / 2), the row's term of the Fisher information, packed lower
 };
+
+// what nn_cond_kernel computes beside mu and var: nothing, every row's score, or the score and the row's Fisher information
+constexpr int NN_VALUE = 0, NN_GRAD = 1, NN_FISHER = 2;
 
 // GRAD: the likelihood's conditionals (xq == xr, s == v) and each row's score.  Everything up to mu and var is the value kernel's code,
 // the same operations in the same order; the factor is still in LDS when they are done, and the score needs no second factorisation:
 // a = L^-T w = A^-1 k and beta = L^-T z = A^-1 r_c by one backward pass, then one more sweep over the kernel entries of the block of
 // (c, i) with their derivatives, each weighted by b_p q_q' + b_q' q_p (include/fvgp_hip_nn.h has the formula).
-template <int KIND, int D, int M, bool GRAD>   // D == 0: runtime dimension; M: the padded block, m <= M
+//
+// NN_FISHER: the row's term F_i of the Fisher information of the product of conditionals, E[-d^2 log p(y_i | y_c)], after the
+// score and from the same factor.  With dS = dSigma / d theta_h:  t_h = (dS b) on the neighbours (one full-row sweep over the block's
+// entries: the lanes the score's sweep masks take part), delta_h = b^T dS b = d var / d theta_h, u_h = L^-1 t_h (every right-hand side in
+// one forward pass), F_i[h][k] = u_h^T u_k / var + 1/2 delta_h delta_k / var^2.  It reads x, v, theta and the lists, never r.
+template <int KIND, int D, int M, int MODE>    // D == 0: runtime dimension; M: the padded block, m <= M
 __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
+    constexpr bool GRAD = MODE >= NN_GRAD;
     constexpr int DD = D ? D : FVGP_MAX_DIM;
     constexpr int TRI = M * (M + 1) / 2;
     __shared__ double sm_all[NN_WAVES * TRI];
@@ -283,6 +296,83 @@ __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
             }
         if (lane == 0)
             for (int h = np; h < a.nth; ++h) out[h] = 0.0;
+
+        if constexpr (MODE == NN_FISHER) {
+            double t[1 + DD], dlt[1 + DD];         // t_h: this lane's entry of dS_h b, then of L^-1 of it; delta_h (lane 0's is the sum)
+#pragma unroll
+            for (int h = 0; h <= DD; ++h) { t[h] = 0.0; dlt[h] = 0.0; }
+            // the neighbours' block, every entry (l, j), l != j, times b_j: the row of a symmetric matrix needs both triangles
+            for (int j = 0; j < M; ++j) {
+                if (!((vmask >> j) & 1ull)) continue;
+                const double bj = lane_value(bl, j);
+                double ek[DD], r2 = 0.0;
+#pragma unroll
+                for (int k = 0; k < DD; ++k) {
+                    ek[k] = 0.0;
+                    if (k < d) { ek[k] = (u[k] - lane_value(u[k], j)) * il[k]; r2 = fma(ek[k], ek[k], r2); }
+                }
+                double phi, cf;
+                radial_grad<KIND>(r2, sig, phi, cf);
+                if (valid && lane != j) {
+                    t[0] = fma(bj, phi, t[0]);
+                    const double wc = bj * cf;
+                    if (iso) t[1] = fma(wc, r2 * il[0], t[1]);
+                    else {
+#pragma unroll
+                        for (int k = 0; k < DD; ++k)
+                            if (k < d) t[1 + k] = fma(wc, ek[k] * ek[k] * il[k], t[1 + k]);
+                    }
+                }
+            }
+            if (valid) t[0] += bl;                 // the diagonal of the block: d Sigma[p][p] = 1 for sigma^2, 0 for the length scales
+            // the column of x_i (b = 1 there) closes t, and delta_h = sum_l b_l (t_h[l] + dk_h[l]) + d Sigma[i][i]
+            {
+                double ek[DD], r2 = 0.0;
+#pragma unroll
+                for (int k = 0; k < DD; ++k) {
+                    ek[k] = 0.0;
+                    if (k < d) { ek[k] = (u[k] - xi[k]) * il[k]; r2 = fma(ek[k], ek[k], r2); }
+                }
+                double phi, cf;
+                radial_grad<KIND>(r2, sig, phi, cf);
+#pragma unroll
+                for (int h = 0; h <= DD; ++h)
+                    if (h < np) {
+                        double dk = phi;           // d k(x_l, x_i) / d theta_h
+                        if (h > 0) dk = iso ? cf * (r2 * il[0]) : cf * (ek[h ? h - 1 : 0] * ek[h ? h - 1 : 0] * il[h ? h - 1 : 0]);
+                        double s = 0.0;
+                        if (valid) { t[h] += dk; s = bl * (t[h] + dk); }
+                        s = wave_tree_sum(s);
+                        dlt[h] = h == 0 ? s + 1.0 : s;
+                    }
+            }
+            // L u_h = t_h for every h at once: step j takes u_h[j] from lane j, the lanes l > j subtract L[l][j] times it (the column the
+            // factorisation wrote); lanes without a neighbour carry 0 and are identity rows
+            for (int j = 0, col = 0; j < M; col += M - j - 1, ++j) {
+                double l = 0.0;
+                if (lane > j && lane < M) l = sm[col + lane];
+#pragma unroll
+                for (int h = 0; h <= DD; ++h)
+                    if (h < np) {
+                        const double uj = lane_value(t[h] * linv, j);
+                        if (lane == j) t[h] = uj;
+                        else if (lane > j && lane < M) t[h] = fma(-l, uj, t[h]);
+                    }
+            }
+            // F_i[h][k] = u_h^T u_k / var + 1/2 delta_h delta_k / var^2, (h, k <= h) at h (h + 1) / 2 + k
+            double *fo = a.fisher + (b * a.nq + row) * ((long)a.nth * (a.nth + 1) / 2);
+#pragma unroll
+            for (int h = 0; h <= DD; ++h)
+                if (h < np) {
+#pragma unroll
+                    for (int k = 0; k <= h; ++k) {
+                        const double s = wave_tree_sum(t[h] * t[k]);
+                        if (lane == 0) fo[h * (h + 1) / 2 + k] = fail ? NAN : s / dv + 0.5 * (dlt[h] / dv) * (dlt[k] / dv);
+                    }
+                }
+            if (lane == 0)
+                for (int e = np * (np + 1) / 2; e < a.nth * (a.nth + 1) / 2; ++e) fo[e] = 0.0;
+        }
     }
 }
 
@@ -381,12 +471,19 @@ inline int64_t nn_work_doubles(int what, int64_t nq, int B) {
 inline int64_t nn_grad_off(int64_t n, int B) { return even_up(nn_work_doubles(FVGP_NN_LOGLIK, n, B)); }
 inline int64_t nn_gpart_off(int64_t n, int B, int ntheta) { return nn_grad_off(n, B) + even_up((int64_t)B * ntheta); }
 inline int64_t nn_grad_work_doubles(int64_t n, int B, int ntheta) { return nn_gpart_off(n, B, ntheta) + (int64_t)B * nn_slices(n) * ntheta; }
+// the Fisher call: the gradient call's work, then the B x P packed sums (P = ntheta (ntheta + 1) / 2) and the rows' sums per (b, slice, entry)
+inline int64_t nn_packed(int ntheta) { return (int64_t)ntheta * (ntheta + 1) / 2; }
+inline int64_t nn_fis_off(int64_t n, int B, int ntheta) { return even_up(nn_grad_work_doubles(n, B, ntheta)); }
+inline int64_t nn_fpart_off(int64_t n, int B, int ntheta) { return nn_fis_off(n, B, ntheta) + even_up((int64_t)B * nn_packed(ntheta)); }
+inline int64_t nn_fisher_work_doubles(int64_t n, int B, int ntheta) {
+    return nn_fpart_off(n, B, ntheta) + (int64_t)B * nn_slices(n) * nn_packed(ntheta);
+}
 
 // the theta table of B hyperparameter vectors into work, the conditionals over it and the info word; nothing is read back.
 // score: NULL, or (B, nq, ntheta) for the gradient variant of the kernel (the likelihood's structure only: xq == xr, s == v)
 int nn_run_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t nq, const double *xr, int64_t nr, int d,
                         const double *thetas, int ntheta, int B, const int *idx, int64_t ld, int m, const double *r, const double *v,
-                        const double *s, double *mu, double *var, double *work, double *score = nullptr) {
+                        const double *s, double *mu, double *var, double *work, double *score = nullptr, double *fisher = nullptr) {
     std::vector<double> tab((size_t)B * NN_TAB);
     KmatDesc k{};
     for (int b = 0; b < B; ++b) {
@@ -402,13 +499,16 @@ int nn_run_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t
     a.xq = xq; a.xr = xr; a.r = r; a.v = v; a.s = s; a.tab = tab_dev; a.idx = idx; a.mu = mu; a.var = var;
     a.nq = nq; a.nr = nr; a.ld = ld; a.d = d; a.m = m;
     a.score = score; a.nth = ntheta; a.iso = KERNEL_FAMILY[kernel_id].iso ? 1 : 0;
+    a.fisher = fisher;
     const dim3 grid((unsigned)((nq + NN_WAVES - 1) / NN_WAVES), (unsigned)B), block(64 * NN_WAVES);
     dispatch_kind_dim(k.kind, d, [&](auto KIND, auto D) {
         dispatch_pad(m, [&](auto M) {
-            if (score)
-                hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value, true>), grid, block, 0, h->stream, a);
+            if (score && fisher)
+                hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value, NN_FISHER>), grid, block, 0, h->stream, a);
+            else if (score)
+                hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value, NN_GRAD>), grid, block, 0, h->stream, a);
             else
-                hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value, false>), grid, block, 0, h->stream, a);
+                hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value, NN_VALUE>), grid, block, 0, h->stream, a);
         });
     });
     HIPCHK(hipGetLastError());
@@ -578,6 +678,72 @@ int fvgp_hip_nn_loglik_grad(fvgp_handle *h, int kernel_id, const double *x, int6
     HIPCHK(hipMemcpyAsync(grad_host, grad, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *info_host = info;
+    return 0;
+}
+
+int64_t fvgp_hip_nn_fisher_workspace_bytes(int64_t n, int B, int ntheta) {
+    if (n < 1 || B < 1 || ntheta < 1) return -1;
+    return nn_fisher_work_doubles(n, B, ntheta) * (int64_t)sizeof(double);
+}
+
+int fvgp_hip_nn_loglik_fisher(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *thetas_host, int ntheta, int B,
+                              const int *idx, int64_t ld, int m, const double *r, const double *v, double *mu, double *var, double *score,
+                              double *fisher_rows, double *work, int64_t work_bytes, double *out_host, double *grad_host,
+                              double *fisher_host, int64_t *info_host) {
+    if (!h) return -1;
+    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
+    if (!x) return -3;
+    if (n < 1 || n > 0x7fffffffLL) return -4;
+    int rc = check_kernel_args(kernel_id, d, thetas_host, ntheta, 5, 6, 7); if (rc) return rc;
+    if (B < 1 || B > 65535) { fvgp_set_error("nn_loglik_fisher: 1 .. 65535 hyperparameter vectors per call"); return -8; }
+    if (!idx) return -9;
+    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error("nn_loglik_fisher: 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -11; }
+    if (ld < m) return -10;
+    if (!r) return -12;
+    if (!v) return -13;
+    if (!mu) return -14;
+    if (!var) return -15;
+    if (!score) return -16;
+    if (!fisher_rows) return -17;
+    if (!work || ((uintptr_t)work & 7)) return -18;
+    if (work_bytes < nn_fisher_work_doubles(n, B, ntheta) * (int64_t)sizeof(double)) {
+        fvgp_set_error("nn_loglik_fisher: work smaller than fvgp_hip_nn_fisher_workspace_bytes(n, B, ntheta)"); return -19;
+    }
+    if (!out_host) return -20;
+    if (!grad_host) return -21;
+    if (!fisher_host) return -22;
+    if (!info_host) return -23;
+    HIPCHK(hipSetDevice(h->device));
+    rc = nn_run_conditionals(h, kernel_id, x, n, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, v, mu, var, work, score, fisher_rows);
+    if (rc) return rc;
+    const int64_t ns = nn_slices(n);
+    const int P = (int)nn_packed(ntheta);
+    double *out = work + nn_out_off(B), *part = work + nn_part_off(B);
+    double *grad = work + nn_grad_off(n, B), *gpart = work + nn_gpart_off(n, B, ntheta);
+    double *fis = work + nn_fis_off(n, B, ntheta), *fpart = work + nn_fpart_off(n, B, ntheta);
+    HIPLAUNCH(nn_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, r, (const double *)mu, (const double *)var, (long)n, part);
+    HIPLAUNCH(nn_total_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), h->stream, (const double *)part, (long)ns, (long)n, B, out);
+    HIPLAUNCH(nn_col_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, (const double *)score, (long)n, ntheta, gpart);
+    const long count = (long)B * ntheta, fcount = (long)B * P;
+    HIPLAUNCH(nn_col_total_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), h->stream, (const double *)gpart, (long)ns, ntheta, count, grad);
+    HIPLAUNCH(nn_col_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, (const double *)fisher_rows, (long)n, P, fpart);
+    HIPLAUNCH(nn_col_total_kernel, dim3((unsigned)((fcount + 63) / 64)), dim3(64), h->stream, (const double *)fpart, (long)ns, P, fcount, fis);
+    long long info = 0;
+    std::vector<double> packed((size_t)fcount);
+    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(out_host, out, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(grad_host, grad, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(packed.data(), fis, (size_t)fcount * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *info_host = info;
+    // the packed lower triangles into full symmetric matrices
+    for (int b = 0; b < B; ++b)
+        for (int hh = 0; hh < ntheta; ++hh)
+            for (int kk = 0; kk <= hh; ++kk) {
+                const double f = packed[(size_t)b * P + (size_t)hh * (hh + 1) / 2 + kk];
+                fisher_host[((size_t)b * ntheta + hh) * ntheta + kk] = f;
+                fisher_host[((size_t)b * ntheta + kk) * ntheta + hh] = f;
+            }
     return 0;
 }
 

@@ -13,6 +13,7 @@ values as m grows.  Prediction at x* conditions on the m nearest data points: th
     big = VecchiaGP(x_all, y_all, hps, noise_all, n_neighbors=32)         # or gp.vecchia(x_all, y_all, noise_all)
     big.log_likelihood(); big.train(bounds, method="mcmc")
     f, g = big.neg_log_likelihood_and_gradient(); big.train_gradient(bounds, method="local")
+    big.train_gradient(bounds, method="fisher"); big.hyperparameter_laplace()["std_error"]
     big.posterior_mean(x_pred); big.posterior_covariance(x_pred, variance_only=True)
 
 "Nearest" is measured after dividing every coordinate by a scale (args["neighbor_scales"]: the length scales at construction, 1, or a
@@ -24,12 +25,19 @@ the m x m factor that is already there, and one more sweep over each block's ker
 neg_log_likelihood_and_gradient, its _batch forms, conditional_scores (the per-point terms that sum to it) and train_gradient ("local":
 scipy's bounded optimisers, "adam": projected Adam, multi-start with args["adam_starts"]) are always there.  The fvgp.GP names
 neg_log_likelihood_gradient and train(method="local" | "adam") take this route with args={"likelihood_gradient": True}.  A tree search, a
-maxmin ordering and joint covariances are not built."""
+maxmin ordering and joint covariances are not built.
+
+The Fisher information of this likelihood -- the expected Hessian of neg_log_likelihood under the exact GP, positive semidefinite, in
+closed form from the same factors (fvgp_hip_nn_loglik_fisher) -- comes from one more device call of about the gradient's cost
+again: fisher_information, neg_log_likelihood_gradient_and_fisher and its _batch form, conditional_fisher (the per-point terms),
+train_gradient(method="fisher") (projected Fisher scoring; train(method="fisher") with args={"likelihood_gradient": True}) and
+hyperparameter_laplace (standard errors and hyperparameter samples from F^-1: the expected curvature, not the observed one)."""
 import warnings
 
 import numpy as np
 
 from . import _lib
+from . import fisher_scoring as _fisher
 from . import gp_training as _training
 from . import kernels as _kernels
 from .device import default_handle
@@ -47,9 +55,9 @@ class VecchiaGP:
     array; the data are held in that order and everything returned per data point is in the CALLER's order.  args:
     "neighbor_scales" = "lengthscales" (default: the kernel's length scales at construction), "unit" or a D-vector;
     "batch_population" (True: train(method="global") scores a generation in one device call); "likelihood_gradient" (True: the fvgp.GP
-    names neg_log_likelihood_gradient and train(method="local" | "adam") run the exact gradient); "adam_starts" (S >= 2:
+    names neg_log_likelihood_gradient and train(method="local" | "adam" | "fisher") run the exact gradient); "adam_starts" (S >= 2:
     train_gradient(method="adam") runs S trajectories in lockstep on the batched gradient); "grad_batch_bytes" (default 1 GiB: the most
-    device memory one batched gradient call may take for its per-row outputs)."""
+    device memory one batched gradient or Fisher call may take for its per-row outputs)."""
 
     def __init__(self, x_data, y_data, hyperparameters, noise_variances=None, kernel_function="matern32_ard", n_neighbors=32,
                  ordering="random", seed=0, args=None):
@@ -296,6 +304,83 @@ class VecchiaGP:
         s[self.ordering] = score[0].cpu().numpy()
         return s
 
+    # ---- the Fisher information ------------------------------------------------------------------------------------------------
+    def _loglik_fisher(self, thetas):
+        """(out (B, 3), grad (B, H), fisher (B, H, H), info, fisher_rows (B, n, H (H + 1) / 2) device) of one device call at the rows of
+        thetas"""
+        H, n = self._H, self.point_number
+        B, nth = thetas.shape
+        mu, var = H.empty(B, n), H.empty(B, n)
+        score = H.torch.empty((B, n, nth), dtype=H.torch.float64, device=mu.device)
+        rows = H.torch.empty((B, n, nth * (nth + 1) // 2), dtype=H.torch.float64, device=mu.device)
+        out, grad, fisher, info = H.nn_loglik_fisher(self._native.kernel_id, self._x_dev, thetas, self._idx, self.n_neighbors, self._r_dev,
+                                                     self._V_dev, mu, var, score, rows)
+        return out, grad, fisher, info, rows
+
+    def neg_log_likelihood_gradient_and_fisher(self, hyperparameters=None):
+        """(f, g (H,), F (H, H)) from one device call: the negative nearest-neighbour log-likelihood, its exact gradient and the Fisher
+        information of the approximation -- the EXPECTED Hessian of f under the exact GP at these hyperparameters, positive semidefinite
+        by construction, for about the cost of a second gradient"""
+        out, grad, fisher, info, _ = self._loglik_fisher(self._one(hyperparameters))
+        if info:
+            raise self._not_pd(info, self.point_number, "neg_log_likelihood_gradient_and_fisher")
+        return -float(out[0, 0]), -grad[0], fisher[0]
+
+    def fisher_information(self, hyperparameters=None):
+        """(H, H): the Fisher information of the nearest-neighbour likelihood; its inverse is the asymptotic covariance of the
+        maximum-likelihood hyperparameters"""
+        return self.neg_log_likelihood_gradient_and_fisher(hyperparameters)[2]
+
+    def _fisher_chunk(self, nth):
+        """hyperparameter vectors per device call: mu, var, score and fisher_rows of a call stay under args["grad_batch_bytes"]"""
+        cap = int(self.args.get("grad_batch_bytes", 1 << 30))
+        return int(max(1, min(65535, cap // (8 * self.point_number * (2 + nth + nth * (nth + 1) // 2)))))
+
+    def neg_log_likelihood_gradient_and_fisher_batch(self, thetas):
+        """(f (B,), G (B, H), F (B, H, H)) at the B rows of `thetas`, each row equal bit for bit to
+        neg_log_likelihood_gradient_and_fisher(thetas[b]); the batch goes in chunks whose per-row outputs fit args["grad_batch_bytes"].
+        Where a conditional is not positive definite the value is +inf, the gradient and the Fisher matrix NaN."""
+        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+        assert thetas.ndim == 2 and thetas.shape[1] == len(self._hps), "thetas must be (B, number of hyperparameters)"
+        nth = thetas.shape[1]
+        f, G, F = np.empty(len(thetas)), np.empty(thetas.shape), np.empty((len(thetas), nth, nth))
+        step = self._fisher_chunk(nth)
+        for a in range(0, len(thetas), step):
+            out, grad, fisher, _, _ = self._loglik_fisher(thetas[a:a + step])
+            f[a:a + step], G[a:a + step], F[a:a + step] = -out[:, 0], -grad, fisher
+        bad = np.isnan(f)
+        G[bad], F[bad] = np.nan, np.nan
+        return np.where(bad, np.inf, f), G, F
+
+    def conditional_fisher(self, hyperparameters=None):
+        """(N, H, H), in the caller's order: entry i is data point i's term of the Fisher information, E[-d^2 log p(y_i | its
+        neighbours)]; positive semidefinite each, they sum to fisher_information"""
+        out, grad, fisher, info, rows = self._loglik_fisher(self._one(hyperparameters))
+        if info:
+            raise self._not_pd(info, self.point_number, "conditional_fisher")
+        nth = fisher.shape[1]
+        packed = rows[0].cpu().numpy()
+        full = np.empty((self.point_number, nth, nth))
+        for h in range(nth):
+            for k in range(h + 1):
+                full[self.ordering, h, k] = full[self.ordering, k, h] = packed[:, h * (h + 1) // 2 + k]
+        return full
+
+    def hyperparameter_laplace(self, hyperparameters=None, n_samples=0, seed=0, bounds=None):
+        """gp_hessian.laplace_from_hessian at `hyperparameters` (None: the current, trained ones) with the Fisher information in the
+        Hessian's place: N(theta, F^-1), the asymptotic distribution of the maximum-likelihood estimate.  The curvature is the EXPECTED
+        one (the Fisher information of the nearest-neighbour likelihood), not the observed Hessian the dense GP's method of this name
+        uses: the two agree as N grows, and "log_evidence" is the Laplace formula with F for H.  Returns that function's dictionary
+        ("mean", "hessian" = F, "covariance", "log_evidence", "samples" (n_samples, H) inside `bounds`) plus "fisher" and "std_error" =
+        sqrt(diag F^-1).  Raises ValueError where F is not positive definite (a hyperparameter the data do not determine)."""
+        from .gp_hessian import laplace_from_hessian
+        hps = self._hps if hyperparameters is None else self._check_hps(hyperparameters)
+        f, _, fisher = self.neg_log_likelihood_gradient_and_fisher(hps)
+        out = laplace_from_hessian(hps, f, fisher, n_samples=n_samples, seed=seed, bounds=bounds)
+        out["fisher"] = fisher
+        out["std_error"] = np.sqrt(np.diag(out["covariance"]))
+        return out
+
     # ---- prediction ----------------------------------------------------------------------------------------------------------
     def _check_pred(self, x_pred, x_out=None):
         if x_out is not None:
@@ -378,9 +463,13 @@ class VecchiaGP:
         object's value and gradient as the objective (one device call serves both).  "adam": gp_training.adam_optimize with every iterate
         clipped into the bounds; with args["adam_starts"] = S >= 2, S trajectories in lockstep (adam_optimize_batch) on the batched value
         and gradient, the first from init_hyperparameters, the others uniform in the bounds from `seed`, the best end point kept
-        (adam_multistart_info).  adam_history keeps the iterates.  Ends with set_hyperparameters(theta) and returns theta."""
-        if method not in ("local", "adam"):
-            raise ValueError(f"train_gradient: method must be 'local' or 'adam', got {method!r}")
+        (adam_multistart_info).  adam_history keeps the iterates.  "fisher": projected Fisher scoring (fisher_scoring.fisher_scoring) on
+        neg_log_likelihood_gradient_and_fisher: Newton-type steps with the Fisher information as the curvature, a backtracking line
+        search inside the bounds, every trial point one device call; a trial at which a conditional is not positive definite counts as
+        +inf.  It stops when the decrement -g^T step falls below `tolerance`; fisher_history keeps the iterates as (theta, f, decrement,
+        step length) and fisher_evaluations the number of device calls.  Ends with set_hyperparameters(theta) and returns theta."""
+        if method not in ("local", "adam", "fisher"):
+            raise ValueError(f"train_gradient: method must be 'local' or 'adam', or 'fisher' for Fisher scoring, got {method!r}")
         bounds = np.asarray(hyperparameter_bounds, dtype=np.float64)
         assert bounds.ndim == 2 and bounds.shape == (len(self._hps), 2), "wrong bounds format"
         theta0 = np.array(self._hps if init_hyperparameters is None else init_hyperparameters, dtype=np.float64)
@@ -396,7 +485,18 @@ class VecchiaGP:
 
         clip = lambda t: np.clip(t, bounds[:, 0], bounds[:, 1])      # noqa: E731
         starts = int(self.args.get("adam_starts", 0) or 0)
-        if method == "local":
+        if method == "fisher":
+            def evaluate3(theta):
+                f, G, F = self.neg_log_likelihood_gradient_and_fisher_batch(theta.reshape(1, -1))
+                return float(f[0]), G[0], F[0]
+
+            progress = None
+            if info:
+                def progress(theta, fval, decrement, iteration):
+                    print(f"fvGP fisher scoring iteration {iteration} out of {max_iter}: f(x)= {float(fval)}, decrement= {float(decrement)}")
+            hps, self.fisher_history, self.fisher_evaluations = _fisher.fisher_scoring(evaluate3, theta0, bounds, max_iter=max_iter,
+                                                                                      tolerance=tolerance, callback=progress)
+        elif method == "local":
             hps = _training.train(self, bounds, theta0, method="local", tolerance=tolerance, max_iter=max_iter,
                                   local_optimizer=local_optimizer, info=info, objective_function=lambda t: evaluate(t)[0],
                                   objective_function_gradient=lambda t: evaluate(t)[1])
@@ -428,19 +528,19 @@ class VecchiaGP:
               info=False, seed=None, constraints=(), mcmc_prior=None, mcmc_args=None, mcmc_prop_distrs="normal"):
         """gp_training.train on the deterministic likelihood with the value-only methods: "mcmc" (default), "global" (a generation of
         the population in one device call unless args["batch_population"] is False) or a callable; with
-        args={"likelihood_gradient": True} also "local" and "adam", which run train_gradient.  The neighbour lists stay fixed
+        args={"likelihood_gradient": True} also "local", "adam" and "fisher", which run train_gradient.  The neighbour lists stay fixed
         throughout.  Ends with set_hyperparameters(theta) and returns theta."""
-        if method in ("local", "adam") and self.likelihood_gradient:
+        if method in ("local", "adam", "fisher") and self.likelihood_gradient:
             return self.train_gradient(hyperparameter_bounds, init_hyperparameters, method=method, tolerance=tolerance, max_iter=max_iter,
                                        info=info, seed=seed)
         if method in ("hgdl", "bo"):
             raise NotImplementedError(f"train(method={method!r}) needs HGDL / the BO surrogate loop; under this name the exact gradient of "
                                       "the nearest-neighbour likelihood is not built yet for them: 'mcmc', 'global', a callable, and with "
                                       "args={'likelihood_gradient': True} 'local' and 'adam' run here")
-        if method in ("local", "adam"):
+        if method in ("local", "adam", "fisher"):
             raise NotImplementedError(f"train(method={method!r}) needs a gradient, and under this fvgp.GP name the exact gradient of the "
                                       "nearest-neighbour likelihood is not built yet -- it answers only with "
-                                      "args={'likelihood_gradient': True}; train_gradient(bounds, method='local' | 'adam') is always there")
+                                      "args={'likelihood_gradient': True}; train_gradient(bounds, method='local' | 'adam' | 'fisher') is always there")
         bounds = np.asarray(hyperparameter_bounds, dtype=np.float64)
         assert bounds.ndim == 2 and bounds.shape == (len(self._hps), 2), "wrong bounds format"
         theta0 = np.array(self._hps if init_hyperparameters is None else init_hyperparameters, dtype=np.float64)

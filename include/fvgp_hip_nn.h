@@ -107,6 +107,38 @@ int fvgp_hip_nn_loglik_grad(fvgp_handle *h, int kernel_id, const double *x, int6
  * rows, hyperparameter).  -1 for n < 1, B < 1 or ntheta < 1. */
 int64_t fvgp_hip_nn_grad_workspace_bytes(int64_t n, int B, int ntheta);
 
+/* The likelihood, its gradient and the Fisher information of the product of conditionals: everything
+ * fvgp_hip_nn_loglik_grad does, and per (b, row i) the row's expected negative Hessian under the exact GP,
+ *     F_i = F(Sigma_ci + noise) - F(A),   F(S)[h][k] = 1/2 tr(S^-1 d_h S S^-1 d_k S),     fisher_host[b] = sum_i F_i.
+ * The Cholesky factor of the joint block extends L by the row (w^T, sqrt(d)), and the difference collapses to that row: with b = (-a, 1),
+ *     t_h = (d_h Sigma b) on the neighbours,   delta_h = b^T d_h Sigma b = d_h var,   u_h = L^-1 t_h,
+ *     F_i[h][k] = u_h^T u_k / var + 1/2 delta_h delta_k / var^2        (= E[d_h mu d_k mu] / var + 1/2 d_h var d_k var / var^2),
+ * each F_i positive semidefinite.  No second factorisation: one more sweep over the block's entries with their derivatives (both
+ * triangles, as t is a matrix-vector product), one forward pass with every right-hand side, the np (np + 1) / 2 products by the halving
+ * tree.  A row without neighbours has 1/2 delta delta^T / var^2 alone, delta = (1, 0, ..).  With every earlier point a neighbour the sum
+ * is the dense 1/2 tr((K + V)^-1 d_h K (K + V)^-1 d_k K).
+ * fisher_rows (B, n, P) device, P = ntheta (ntheta + 1) / 2: the packed lower triangle of F_i, (h, k <= h) at h (h + 1) / 2 + k; entries
+ * that involve a column past the kernel's own hyperparameters receive 0.  fisher_host (B, ntheta, ntheta) host: the sums, full symmetric.
+ * BIT CONTRACT: out_host, mu, var, score and grad_host are bit for bit those of fvgp_hip_nn_loglik_grad on the same inputs.
+ * fisher_rows[b][i][:] is a function of (x_i, v_i, the listed rows in their listed order, theta_b, m) alone: not of n, B, or the position in
+ * either, and -- unlike the score -- not of r.  The rows' terms are added as the scores are (slices of 256 rows by a halving tree, the
+ * slices to 0 in ascending order, one thread per (b, entry), no atomics): the same call gives the same bits, and row b of fisher_host
+ * does not depend on B.
+ * A failed pivot gives a NaN row of fisher_rows next to the NaN mu, var and scores, and the same info; fisher_host[b] is then NaN.
+ * work: device, 8-byte aligned, fvgp_hip_nn_fisher_workspace_bytes(n, B, ntheta) bytes.
+ * Errors: -1 h, -2 unknown kernel_id, -3 x, -4 n < 1 or past 2^31 - 1, -5 d outside 1 .. FVGP_MAX_DIM, -6 thetas_host, -7 too few
+ * hyperparameters, -8 B outside 1 .. 65535, -9 idx, -10 ld < m, -11 m outside 1 .. FVGP_NN_MAX_NEIGHBORS, -12 r, -13 v, -14 mu, -15 var,
+ * -16 score, -17 fisher_rows, -18 work NULL or misaligned, -19 work_bytes too small, -20 out_host, -21 grad_host, -22 fisher_host,
+ * -23 info_host. */
+int fvgp_hip_nn_loglik_fisher(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *thetas_host, int ntheta, int B,
+                              const int *idx, int64_t ld, int m, const double *r, const double *v, double *mu, double *var, double *score,
+                              double *fisher_rows, double *work, int64_t work_bytes, double *out_host, double *grad_host,
+                              double *fisher_host, int64_t *info_host);
+
+/* bytes of the caller-owned `work` of fvgp_hip_nn_loglik_fisher: the gradient call's, then the packed sums per b and one sum per (b, slice
+ * of 256 rows, packed entry).  -1 for n < 1, B < 1 or ntheta < 1. */
+int64_t fvgp_hip_nn_fisher_workspace_bytes(int64_t n, int B, int ntheta);
+
 #ifdef __cplusplus
 }
 #endif
