@@ -202,6 +202,7 @@ _ABI_NN = {
 SYMBOLS_NN = list(_ABI_NN)
 NN_MAX_NEIGHBORS = 64     # FVGP_NN_MAX_NEIGHBORS
 NN_SEARCH, NN_CONDITIONALS, NN_LOGLIK = 0, 1, 2   # FVGP_NN_*: the call fvgp_hip_nn_workspace_bytes sizes
+NN_VALUE, NN_GRAD, NN_FISHER = 0, 1, 2            # how far a likelihood call goes: fvgp_hip_nn_loglik, _loglik_grad, _loglik_fisher
 
 
 def bind(L):
@@ -1027,60 +1028,53 @@ class Handle(DistCalls):
                    _ptr(work), work.numel() * 8, ctypes.byref(info))
         return int(info.value)
 
+    def _nn_likelihood(self, level, kernel_id, x, thetas, idx, m, r, v, mu, var, score, fisher_rows, work):
+        """the three likelihood entries (level NN_VALUE, NN_GRAD, NN_FISHER): operand checks, workspace, host outputs and the call.
+        Returns (out, grad, fisher, info), None where the level has none."""
+        who = ("nn_loglik", "nn_loglik_grad", "nn_loglik_fisher")[level]
+        n = x.shape[0]
+        t, B = self._nn_operands(who, thetas, idx, n, m, mu, var)
+        nth = t.shape[1]
+        if level >= NN_GRAD and (not score.is_contiguous() or score.numel() < B * n * nth):
+            raise ValueError(f"{who}: score must be a contiguous (B, n, ntheta) tensor, got {tuple(score.shape)}")
+        if level == NN_FISHER and (not fisher_rows.is_contiguous() or fisher_rows.numel() < B * n * (nth * (nth + 1) // 2)):
+            raise ValueError(f"{who}: fisher_rows must be a contiguous (B, n, ntheta (ntheta + 1) / 2) tensor, got "
+                             f"{tuple(fisher_rows.shape)}")
+        if work is None:
+            size = nn_workspace_bytes(NN_LOGLIK, n, B) if level == NN_VALUE else \
+                nn_grad_workspace_bytes(n, B, nth) if level == NN_GRAD else nn_fisher_workspace_bytes(n, B, nth)
+            work = self.empty(max(1, size) // 8)
+        out = np.empty((B, 3), dtype=np.float64)
+        grad = np.empty((B, nth), dtype=np.float64) if level >= NN_GRAD else None
+        fisher = np.empty((B, nth, nth), dtype=np.float64) if level == NN_FISHER else None
+        info = ctypes.c_int64(0)
+        # the entries' argument lists differ by the arrays of their level alone: score, fisher_rows before work; grad, fisher behind out
+        rows = [_ptr(a) for a in (score, fisher_rows)[:level]]
+        sums = [a.ctypes.data_as(P_d) for a in (grad, fisher)[:level]]
+        self._call("fvgp_hip_" + who, int(kernel_id), _ptr(x), n, x.shape[1], t.ctypes.data_as(P_d), nth, B, _ptr(idx), idx.stride(0), int(m),
+                   _ptr(r), _ptr(v), _ptr(mu), _ptr(var), *rows, _ptr(work), work.numel() * 8, out.ctypes.data_as(P_d), *sums, ctypes.byref(info))
+        return out, grad, fisher, int(info.value)
+
     def nn_loglik(self, kernel_id, x, thetas, idx, m, r, v, mu, var, work=None):
         """fvgp_hip_nn_loglik: the nearest-neighbour log-likelihood of the rows of x in their order (idx: nn_search of x on itself with
         c0 = 0) at the B rows of `thetas`.  Returns (out (B, 3) ndarray of {log p, sum (r - mu)^2 / var, sum log var}, info as
         nn_conditionals); mu, var (B, n) keep the per-row conditionals.  Synchronous."""
-        n = x.shape[0]
-        t, B = self._nn_operands("nn_loglik", thetas, idx, n, m, mu, var)
-        if work is None:
-            work = self.empty(max(1, nn_workspace_bytes(NN_LOGLIK, n, B)) // 8)
-        out = np.empty((B, 3), dtype=np.float64)
-        info = ctypes.c_int64(0)
-        self._call("fvgp_hip_nn_loglik", int(kernel_id), _ptr(x), n, x.shape[1], t.ctypes.data_as(P_d), t.shape[1], B,
-                   _ptr(idx), idx.stride(0), int(m), _ptr(r), _ptr(v), _ptr(mu), _ptr(var), _ptr(work), work.numel() * 8,
-                   out.ctypes.data_as(P_d), ctypes.byref(info))
-        return out, int(info.value)
+        out, _, _, info = self._nn_likelihood(NN_VALUE, kernel_id, x, thetas, idx, m, r, v, mu, var, None, None, work)
+        return out, info
 
     def nn_loglik_grad(self, kernel_id, x, thetas, idx, m, r, v, mu, var, score, work=None):
         """fvgp_hip_nn_loglik_grad: nn_loglik and the exact gradient.  score (B, n, ntheta) device tensor <- every row's
         d log p(y_i | y_c(i)) / d theta.  Returns (out (B, 3) as nn_loglik, grad (B, ntheta) ndarray = d log p / d theta, info).
         Synchronous."""
-        n = x.shape[0]
-        t, B = self._nn_operands("nn_loglik_grad", thetas, idx, n, m, mu, var)
-        if not score.is_contiguous() or score.numel() < B * n * t.shape[1]:
-            raise ValueError(f"nn_loglik_grad: score must be a contiguous (B, n, ntheta) tensor, got {tuple(score.shape)}")
-        if work is None:
-            work = self.empty(max(1, nn_grad_workspace_bytes(n, B, t.shape[1])) // 8)
-        out, grad = np.empty((B, 3), dtype=np.float64), np.empty((B, t.shape[1]), dtype=np.float64)
-        info = ctypes.c_int64(0)
-        self._call("fvgp_hip_nn_loglik_grad", int(kernel_id), _ptr(x), n, x.shape[1], t.ctypes.data_as(P_d), t.shape[1], B,
-                   _ptr(idx), idx.stride(0), int(m), _ptr(r), _ptr(v), _ptr(mu), _ptr(var), _ptr(score), _ptr(work), work.numel() * 8,
-                   out.ctypes.data_as(P_d), grad.ctypes.data_as(P_d), ctypes.byref(info))
-        return out, grad, int(info.value)
+        out, grad, _, info = self._nn_likelihood(NN_GRAD, kernel_id, x, thetas, idx, m, r, v, mu, var, score, None, work)
+        return out, grad, info
 
     def nn_loglik_fisher(self, kernel_id, x, thetas, idx, m, r, v, mu, var, score, fisher_rows, work=None):
         """fvgp_hip_nn_loglik_fisher: nn_loglik_grad and the Fisher information of the product of conditionals.  fisher_rows
         (B, n, ntheta (ntheta + 1) / 2) device tensor <- every row's term, the packed lower triangle ((h, k <= h) at h (h + 1) / 2 + k).
         Returns (out (B, 3) and grad (B, ntheta) as nn_loglik_grad, fisher (B, ntheta, ntheta) ndarray = the rows' sum, symmetric, info).
         Synchronous."""
-        n = x.shape[0]
-        t, B = self._nn_operands("nn_loglik_fisher", thetas, idx, n, m, mu, var)
-        nth = t.shape[1]
-        if not score.is_contiguous() or score.numel() < B * n * nth:
-            raise ValueError(f"nn_loglik_fisher: score must be a contiguous (B, n, ntheta) tensor, got {tuple(score.shape)}")
-        if not fisher_rows.is_contiguous() or fisher_rows.numel() < B * n * (nth * (nth + 1) // 2):
-            raise ValueError("nn_loglik_fisher: fisher_rows must be a contiguous (B, n, ntheta (ntheta + 1) / 2) tensor, got "
-                             f"{tuple(fisher_rows.shape)}")
-        if work is None:
-            work = self.empty(max(1, nn_fisher_workspace_bytes(n, B, nth)) // 8)
-        out, grad = np.empty((B, 3), dtype=np.float64), np.empty((B, nth), dtype=np.float64)
-        fisher = np.empty((B, nth, nth), dtype=np.float64)
-        info = ctypes.c_int64(0)
-        self._call("fvgp_hip_nn_loglik_fisher", int(kernel_id), _ptr(x), n, x.shape[1], t.ctypes.data_as(P_d), nth, B,
-                   _ptr(idx), idx.stride(0), int(m), _ptr(r), _ptr(v), _ptr(mu), _ptr(var), _ptr(score), _ptr(fisher_rows), _ptr(work),
-                   work.numel() * 8, out.ctypes.data_as(P_d), grad.ctypes.data_as(P_d), fisher.ctypes.data_as(P_d), ctypes.byref(info))
-        return out, grad, fisher, int(info.value)
+        return self._nn_likelihood(NN_FISHER, kernel_id, x, thetas, idx, m, r, v, mu, var, score, fisher_rows, work)
 
     def posterior_prepare(self, L, n):
         """enqueue the inverted diagonal blocks the posterior's sweep substitutes with (fvgp_hip_posterior_prepare)"""

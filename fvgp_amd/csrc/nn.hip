@@ -9,14 +9,13 @@
 //     addresses).  Factorisation: left-looking, column by column, lane l accumulating its entry of the column over the earlier columns
 //     (own entries conflict-free, row j's entries broadcast); the pivot leaves lane j by v_readlane, and both right-hand sides (k and
 //     r_c, a register each) are substituted in the same step.  Padded lanes are identity rows.
-// fvgp_hip_nn_loglik        the conditionals on the data itself, then the two sums: slices of 256 rows by a halving tree in LDS, the
-//     slices to 0 in ascending order by one thread per b.  No atomics anywhere.
-// fvgp_hip_nn_loglik_grad   the same and the exact gradient in theta: the GRAD variant of the conditionals kernel goes on from
-//     the factor in LDS (a backward pass for A^-1 k and A^-1 r_c, one more sweep over the block's entries with their derivatives) and
-//     writes every row's score; the scores are summed per hyperparameter like the likelihood's terms.
-// fvgp_hip_nn_loglik_fisher the same and the Fisher information of the product of conditionals: the NN_FISHER mode of the kernel goes
-//     on after the score (a full-row sweep of derivatives, a forward pass with every right-hand side, the pairwise products) and writes
-//     every row's packed term; the terms are summed like the scores and the triangle is mirrored on the host.
+// fvgp_hip_nn_loglik, _loglik_grad, _loglik_fisher   one host path (nn_loglik, one workspace layout: nn_layout) at the levels NN_VALUE,
+//     NN_GRAD, NN_FISHER: the conditionals on the data itself in the level's mode of the kernel, then the sums.
+//     NN_GRAD: the kernel goes on from the factor in LDS (a backward pass for A^-1 k and A^-1 r_c, one more sweep over the
+//     block's entries with their derivatives) and writes every row's score.  NN_FISHER: it goes on after the score (a full-row
+//     sweep of derivatives, a forward pass with every right-hand side, the pairwise products) and writes every row's packed term.
+//     The sums (nn_sum_columns: the likelihood's two terms, the scores' columns, the packed entries): slices of 256 rows by a halving tree in
+//     LDS, the slices to 0 in ascending order by one thread per (b, column).  No atomics anywhere.  The triangle is mirrored on the host.
 #include "radial.h"
 #include "kernel_family.h"
 #include "../../include/fvgp_hip_nn.h"
@@ -137,6 +136,18 @@ inline void dispatch_pad(int m, F &&f) {
     else f(std::integral_constant<int, 64>{});
 }
 
+// the level of a likelihood call, and what nn_cond_kernel computes beside mu and var: nothing, every row's score, or the score and the
+// row's Fisher information
+constexpr int NN_VALUE = 0, NN_GRAD = 1, NN_FISHER = 2;
+
+// f(std::integral_constant<int, MODE>) for the level
+template <class F>
+inline void dispatch_mode(int level, F &&f) {
+    if (level == NN_FISHER) f(std::integral_constant<int, NN_FISHER>{});
+    else if (level == NN_GRAD) f(std::integral_constant<int, NN_GRAD>{});
+    else f(std::integral_constant<int, NN_VALUE>{});
+}
+
 // ------------------------------------------------------------------------------------------------------------ conditionals
 struct NcArgs {
     const double *xq, *xr, *r, *v, *s, *tab;       // tab (B, NN_TAB)
@@ -148,9 +159,6 @@ struct NcArgs {
     int nth, iso;                                  // GRAD: columns of score; one length scale for every dimension
     double *fisher;                                // NN_FISHER: (B, nq, nth (nth + 1) / 2), the row's term of the Fisher information, packed lower
 };
-
-// what nn_cond_kernel computes beside mu and var: nothing, every row's score, or the score and the row's Fisher information
-constexpr int NN_VALUE = 0, NN_GRAD = 1, NN_FISHER = 2;
 
 // GRAD: the likelihood's conditionals (xq == xr, s == v) and each row's score.  Everything up to mu and var is the value kernel's code,
 // the same operations in the same order; the factor is still in LDS when they are done, and the score needs no second factorisation:
@@ -393,97 +401,104 @@ __global__ __launch_bounds__(256) void nn_info_kernel(const double *var, long to
     if (tid == 0) *info = sm[0] == 0x7fffffffffffffffLL ? 0 : sm[0] + 1;
 }
 
-// ------------------------------------------------------------------------------------------------------ the likelihood's sums
-// part[(b * nslices + slice) * 2 + {0, 1}] = the slice's sums of (r - mu)^2 / var and log var: a halving tree over 256 rows
-__global__ __launch_bounds__(NN_SUM_ROWS) void nn_terms_kernel(const double *r, const double *mu, const double *var, long n, double *part) {
-    __shared__ double sf[NN_SUM_ROWS], sl[NN_SUM_ROWS];
-    const int tid = threadIdx.x;
-    const long i = (long)blockIdx.x * NN_SUM_ROWS + tid, b = blockIdx.y;
-    double f = 0.0, l = 0.0;
-    if (i < n) {
+// --------------------------------------------------------------------------------------------------- the sums over the rows
+// where the W columns c .. c + W - 1 of row (b, i) come from: a (B, n, ncol) array (the scores, the Fisher rows), a column at a time ...
+struct NnColumns {
+    static constexpr int W = 1;
+    const double *src;
+    __device__ void operator()(long b, long i, int c, long n, int ncol, double *t) const { t[0] = src[(b * n + i) * ncol + c]; }
+};
+// ... or the likelihood's pair, formed here and summed together: column 0 (r - mu)^2 / var, column 1 log var
+struct NnLikTerms {
+    static constexpr int W = 2;
+    const double *r, *mu, *var;
+    __device__ void operator()(long b, long i, int, long n, int, double *t) const {
         const double dv = var[b * n + i], e = r[i] - mu[b * n + i];
-        f = e * e / dv;
-        l = log(dv);
+        t[0] = e * e / dv;
+        t[1] = log(dv);
     }
-    sf[tid] = f; sl[tid] = l;
-    __syncthreads();
-    for (int off = NN_SUM_ROWS / 2; off > 0; off >>= 1) {
-        if (tid < off) { sf[tid] += sf[tid + off]; sl[tid] += sl[tid + off]; }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        double *o = part + (b * gridDim.x + blockIdx.x) * 2;
-        o[0] = sf[0]; o[1] = sl[0];
-    }
-}
+};
 
-// out[b] = {log p, fit, logdet}: the slices added to 0 in ascending order, one thread per b
-__global__ __launch_bounds__(64) void nn_total_kernel(const double *part, long nslices, long n, int B, double *out) {
-    const long b = (long)blockIdx.x * 64 + threadIdx.x;
-    if (b >= B) return;
-    double f = 0.0, l = 0.0;
-    for (long s = 0; s < nslices; ++s) { f += part[(b * nslices + s) * 2]; l += part[(b * nslices + s) * 2 + 1]; }
-    out[b * 3] = -0.5 * (f + l + (double)n * 1.8378770664093454836);       // log 2 pi
-    out[b * 3 + 1] = f;
-    out[b * 3 + 2] = l;
-}
-
-// the same pair for ncol columns per row (the scores): part[(b * nslices + slice) * ncol + c] = the slice's sum of src[b][i][c] by the
-// same halving tree over 256 rows ...
-__global__ __launch_bounds__(NN_SUM_ROWS) void nn_col_terms_kernel(const double *src, long n, int ncol, double *part) {
-    __shared__ double sf[NN_SUM_ROWS];
+// part[(b * nslices + slice) * ncol + c] = the slice's sum of column c: a halving tree over 256 rows, W columns at a time (W divides ncol) ...
+template <class S>
+__global__ __launch_bounds__(NN_SUM_ROWS) void nn_slice_sum_kernel(S src, long n, int ncol, double *part) {
+    constexpr int W = S::W;
+    __shared__ double sf[W][NN_SUM_ROWS];
     const int tid = threadIdx.x;
     const long i = (long)blockIdx.x * NN_SUM_ROWS + tid, b = blockIdx.y;
-    for (int c = 0; c < ncol; ++c) {
-        sf[tid] = i < n ? src[(b * n + i) * ncol + c] : 0.0;
+    for (int c = 0; c < ncol; c += W) {
+        double t[W] = {};
+        if (i < n) src(b, i, c, n, ncol, t);
+#pragma unroll
+        for (int w = 0; w < W; ++w) sf[w][tid] = t[w];
         __syncthreads();
         for (int off = NN_SUM_ROWS / 2; off > 0; off >>= 1) {
-            if (tid < off) sf[tid] += sf[tid + off];
+            if (tid < off) {
+#pragma unroll
+                for (int w = 0; w < W; ++w) sf[w][tid] += sf[w][tid + off];
+            }
             __syncthreads();
         }
-        if (tid == 0) part[(b * gridDim.x + blockIdx.x) * ncol + c] = sf[0];
-        __syncthreads();                           // (sf[0] has been read before the next column overwrites it)
+        if (tid == 0) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) part[(b * gridDim.x + blockIdx.x) * ncol + c + w] = sf[w][0];
+        }
+        __syncthreads();                           // (sf[.][0] has been read before the next columns overwrite it)
     }
 }
 
-// ... and out[b][c] = the slices added to 0 in ascending order, one thread per (b, c)
-__global__ __launch_bounds__(64) void nn_col_total_kernel(const double *part, long nslices, int ncol, long count, double *out) {
+// ... and out[b][c] = the slices added to 0 in ascending order, one thread per (b, c).  LIK (ncol == 2, the likelihood's pair):
+// out[b] = {log p, fit, logdet} instead, log p by the thread of fit, which takes logdet from the lane beside it
+template <bool LIK>
+__global__ __launch_bounds__(64) void nn_total_kernel(const double *part, long nslices, int ncol, long count, long n, double *out) {
     const long e = (long)blockIdx.x * 64 + threadIdx.x;
-    if (e >= count) return;
     const long b = e / ncol, c = e - b * ncol;
     double s = 0.0;
-    for (long sl = 0; sl < nslices; ++sl) s += part[(b * nslices + sl) * ncol + c];
-    out[e] = s;
+    if (e < count)
+        for (long sl = 0; sl < nslices; ++sl) s += part[(b * nslices + sl) * ncol + c];
+    if (!LIK) {
+        if (e < count) out[e] = s;
+        return;
+    }
+    const double f = s, l = __shfl_down(s, 1, 64);
+    if (e < count) out[b * 3 + 1 + c] = s;
+    if (e < count && c == 0) out[b * 3] = -0.5 * (f + l + (double)n * 1.8378770664093454836);      // log 2 pi
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
 inline int64_t nn_slices(int64_t n) { return (n + NN_SUM_ROWS - 1) / NN_SUM_ROWS; }
-// work, in doubles: [0] the info word, [2 ..) the theta table, then (likelihood) the results and the slices' sums
-inline int64_t nn_tab_off() { return 2; }
-inline int64_t nn_out_off(int B) { return nn_tab_off() + even_up((int64_t)B * NN_TAB); }
-inline int64_t nn_part_off(int B) { return nn_out_off(B) + even_up((int64_t)B * 3); }
-inline int64_t nn_work_doubles(int what, int64_t nq, int B) {
-    if (what == FVGP_NN_SEARCH) return 0;
-    if (what == FVGP_NN_CONDITIONALS) return nn_out_off(B);
-    return nn_part_off(B) + 2 * (int64_t)B * nn_slices(nq);
-}
-// the gradient call: the likelihood's work, then the B x ntheta gradient and the scores' sums per (b, slice, column)
-inline int64_t nn_grad_off(int64_t n, int B) { return even_up(nn_work_doubles(FVGP_NN_LOGLIK, n, B)); }
-inline int64_t nn_gpart_off(int64_t n, int B, int ntheta) { return nn_grad_off(n, B) + even_up((int64_t)B * ntheta); }
-inline int64_t nn_grad_work_doubles(int64_t n, int B, int ntheta) { return nn_gpart_off(n, B, ntheta) + (int64_t)B * nn_slices(n) * ntheta; }
-// the Fisher call: the gradient call's work, then the B x P packed sums (P = ntheta (ntheta + 1) / 2) and the rows' sums per (b, slice, entry)
 inline int64_t nn_packed(int ntheta) { return (int64_t)ntheta * (ntheta + 1) / 2; }
-inline int64_t nn_fis_off(int64_t n, int B, int ntheta) { return even_up(nn_grad_work_doubles(n, B, ntheta)); }
-inline int64_t nn_fpart_off(int64_t n, int B, int ntheta) { return nn_fis_off(n, B, ntheta) + even_up((int64_t)B * nn_packed(ntheta)); }
-inline int64_t nn_fisher_work_doubles(int64_t n, int B, int ntheta) {
-    return nn_fpart_off(n, B, ntheta) + (int64_t)B * nn_slices(n) * nn_packed(ntheta);
+
+// work, in doubles, every piece on an even offset: [0] the info word, `tab` the theta table (all a conditionals call takes: it ends at
+// `out`); the likelihood: `out` the three results per b, `part` the pair's sums per (b, slice); from NN_GRAD: `grad` (B, ntheta), `gpart`
+// the scores' sums per (b, slice, column); at NN_FISHER: `fis` (B, P) packed, `fpart` the rows' sums per (b, slice, entry).  `end`: the
+// call's size.  A level's layout is the one below it and its own two pieces behind.
+struct NnLayout { int64_t tab, out, part, grad, gpart, fis, fpart, end; };
+
+NnLayout nn_layout(int level, int64_t n, int B, int ntheta) {
+    NnLayout l{};
+    l.tab = 2;
+    l.out = l.tab + even_up((int64_t)B * NN_TAB);
+    l.part = l.out + even_up((int64_t)B * 3);
+    l.end = l.part + 2 * (int64_t)B * nn_slices(n);
+    if (level >= NN_GRAD) {
+        l.grad = even_up(l.end);
+        l.gpart = l.grad + even_up((int64_t)B * ntheta);
+        l.end = l.gpart + (int64_t)B * nn_slices(n) * ntheta;
+    }
+    if (level >= NN_FISHER) {
+        l.fis = even_up(l.end);
+        l.fpart = l.fis + even_up((int64_t)B * nn_packed(ntheta));
+        l.end = l.fpart + (int64_t)B * nn_slices(n) * nn_packed(ntheta);
+    }
+    return l;
 }
 
-// the theta table of B hyperparameter vectors into work, the conditionals over it and the info word; nothing is read back.
-// score: NULL, or (B, nq, ntheta) for the gradient variant of the kernel (the likelihood's structure only: xq == xr, s == v)
-int nn_run_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t nq, const double *xr, int64_t nr, int d,
+// the theta table of B hyperparameter vectors into work, the conditionals over it at `level` and the info word; nothing is read back.
+// score (B, nq, ntheta) from NN_GRAD and fisher (B, nq, P) at NN_FISHER, else NULL (the likelihood's structure only: xq == xr, s == v)
+int nn_run_conditionals(fvgp_handle *h, int level, int kernel_id, const double *xq, int64_t nq, const double *xr, int64_t nr, int d,
                         const double *thetas, int ntheta, int B, const int *idx, int64_t ld, int m, const double *r, const double *v,
-                        const double *s, double *mu, double *var, double *work, double *score = nullptr, double *fisher = nullptr) {
+                        const double *s, double *mu, double *var, double *work, double *score, double *fisher) {
     std::vector<double> tab((size_t)B * NN_TAB);
     KmatDesc k{};
     for (int b = 0; b < B; ++b) {
@@ -492,7 +507,7 @@ int nn_run_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t
         tab[(size_t)b * NN_TAB] = k.sig;
         for (int i = 0; i < FVGP_MAX_DIM; ++i) tab[(size_t)b * NN_TAB + 1 + i] = k.invl[i];
     }
-    double *tab_dev = work + nn_tab_off();
+    double *tab_dev = work + nn_layout(NN_VALUE, nq, B, ntheta).tab;
     HIPCHK(hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));       // (the table leaves this frame)
     NcArgs a;
@@ -503,16 +518,84 @@ int nn_run_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t
     const dim3 grid((unsigned)((nq + NN_WAVES - 1) / NN_WAVES), (unsigned)B), block(64 * NN_WAVES);
     dispatch_kind_dim(k.kind, d, [&](auto KIND, auto D) {
         dispatch_pad(m, [&](auto M) {
-            if (score && fisher)
-                hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value, NN_FISHER>), grid, block, 0, h->stream, a);
-            else if (score)
-                hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value, NN_GRAD>), grid, block, 0, h->stream, a);
-            else
-                hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value, NN_VALUE>), grid, block, 0, h->stream, a);
+            dispatch_mode(level, [&](auto MODE) {
+                hipLaunchKernelGGL((nn_cond_kernel<decltype(KIND)::value, decltype(D)::value, decltype(M)::value, decltype(MODE)::value>), grid, block, 0,
+                                   h->stream, a);
+            });
         });
     });
     HIPCHK(hipGetLastError());
     HIPLAUNCH(nn_info_kernel, dim3(1), dim3(256), h->stream, (const double *)var, (long)(nq * B), (long long *)work);
+    return 0;
+}
+
+// the slices' sums of `source`'s ncol columns over n rows into part (B, slices, ncol), and their totals into `total`
+template <class S>
+int nn_sum_columns(hipStream_t stream, S source, int64_t n, int ncol, int B, double *part, double *total) {
+    const int64_t ns = nn_slices(n);
+    const long count = (long)B * ncol;
+    HIPLAUNCH(nn_slice_sum_kernel<S>, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), stream, source, (long)n, ncol, part);
+    constexpr bool LIK = std::is_same<S, NnLikTerms>::value;
+    HIPLAUNCH(nn_total_kernel<LIK>, dim3((unsigned)((count + 63) / 64)), dim3(64), stream, (const double *)part,
+              (long)ns, ncol, count, (long)n, total);
+    return 0;
+}
+
+// The three likelihood entries (include/fvgp_hip_nn.h): `level` says how far the call goes, `who` is the entry's name in its error texts.
+// An error is minus the argument's position in THAT entry: score and grad_host exist from NN_GRAD, fisher_rows and fisher_host at
+// NN_FISHER, and the positions behind them shift with the level.  Nothing is launched or written before the last check has passed.
+int nn_loglik(int level, const std::string &who, fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *thetas_host,
+              int ntheta, int B, const int *idx, int64_t ld, int m, const double *r, const double *v, double *mu, double *var, double *score,
+              double *fisher_rows, double *work, int64_t work_bytes, double *out_host, double *grad_host, double *fisher_host,
+              int64_t *info_host) {
+    static const char *const sizing[] = {"fvgp_hip_nn_workspace_bytes(FVGP_NN_LOGLIK, n, B)", "fvgp_hip_nn_grad_workspace_bytes(n, B, ntheta)",
+                                         "fvgp_hip_nn_fisher_workspace_bytes(n, B, ntheta)"};
+    if (!h) return -1;
+    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
+    if (!x) return -3;
+    if (n < 1 || n > 0x7fffffffLL) return -4;
+    int rc = check_kernel_args(kernel_id, d, thetas_host, ntheta, 5, 6, 7); if (rc) return rc;
+    if (B < 1 || B > 65535) { fvgp_set_error(who + ": 1 .. 65535 hyperparameter vectors per call"); return -8; }
+    if (!idx) return -9;
+    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error(who + ": 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -11; }
+    if (ld < m) return -10;
+    if (!r) return -12;
+    if (!v) return -13;
+    if (!mu) return -14;
+    if (!var) return -15;
+    if (level >= NN_GRAD && !score) return -16;
+    if (level == NN_FISHER && !fisher_rows) return -17;
+    const int at = 15 + level;                     // the last device array's position: var, score or fisher_rows
+    if (!work || ((uintptr_t)work & 7)) return -(at + 1);
+    const NnLayout l = nn_layout(level, n, B, ntheta);
+    if (work_bytes < l.end * (int64_t)sizeof(double)) { fvgp_set_error(who + ": work smaller than " + sizing[level]); return -(at + 2); }
+    if (!out_host) return -(at + 3);
+    if (level >= NN_GRAD && !grad_host) return -(at + 4);
+    if (level == NN_FISHER && !fisher_host) return -(at + 5);
+    if (!info_host) return -(at + 4 + level);
+    HIPCHK(hipSetDevice(h->device));
+    rc = nn_run_conditionals(h, level, kernel_id, x, n, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, v, mu, var, work, score, fisher_rows);
+    if (rc) return rc;
+    const int P = (int)nn_packed(ntheta);
+    rc = nn_sum_columns(h->stream, NnLikTerms{r, mu, var}, n, 2, B, work + l.part, work + l.out); if (rc) return rc;
+    if (level >= NN_GRAD) { rc = nn_sum_columns(h->stream, NnColumns{score}, n, ntheta, B, work + l.gpart, work + l.grad); if (rc) return rc; }
+    if (level == NN_FISHER) { rc = nn_sum_columns(h->stream, NnColumns{fisher_rows}, n, P, B, work + l.fpart, work + l.fis); if (rc) return rc; }
+    long long info = 0;
+    std::vector<double> packed(level == NN_FISHER ? (size_t)B * P : 0);
+    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(out_host, work + l.out, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (level >= NN_GRAD) HIPCHK(hipMemcpyAsync(grad_host, work + l.grad, (size_t)B * ntheta * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (level == NN_FISHER) HIPCHK(hipMemcpyAsync(packed.data(), work + l.fis, packed.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *info_host = info;
+    // the packed lower triangles into full symmetric matrices
+    for (int b = 0; level == NN_FISHER && b < B; ++b)
+        for (int hh = 0; hh < ntheta; ++hh)
+            for (int kk = 0; kk <= hh; ++kk) {
+                const double f = packed[(size_t)b * P + (size_t)hh * (hh + 1) / 2 + kk];
+                fisher_host[((size_t)b * ntheta + hh) * ntheta + kk] = f;
+                fisher_host[((size_t)b * ntheta + kk) * ntheta + hh] = f;
+            }
     return 0;
 }
 
@@ -522,7 +605,18 @@ extern "C" {
 
 int64_t fvgp_hip_nn_workspace_bytes(int what, int64_t nq, int B) {
     if (what < FVGP_NN_SEARCH || what > FVGP_NN_LOGLIK || nq < 1 || B < 1) return -1;
-    return nn_work_doubles(what, nq, B) * (int64_t)sizeof(double);
+    const NnLayout l = nn_layout(NN_VALUE, nq, B, 0);
+    return (what == FVGP_NN_SEARCH ? 0 : what == FVGP_NN_CONDITIONALS ? l.out : l.end) * (int64_t)sizeof(double);
+}
+
+int64_t fvgp_hip_nn_grad_workspace_bytes(int64_t n, int B, int ntheta) {
+    if (n < 1 || B < 1 || ntheta < 1) return -1;
+    return nn_layout(NN_GRAD, n, B, ntheta).end * (int64_t)sizeof(double);
+}
+
+int64_t fvgp_hip_nn_fisher_workspace_bytes(int64_t n, int B, int ntheta) {
+    if (n < 1 || B < 1 || ntheta < 1) return -1;
+    return nn_layout(NN_FISHER, n, B, ntheta).end * (int64_t)sizeof(double);
 }
 
 int fvgp_hip_nn_search(fvgp_handle *h, const double *xq, int64_t nq, const double *xr, int64_t nr, int d, const double *scales_host,
@@ -581,12 +675,12 @@ int fvgp_hip_nn_conditionals(fvgp_handle *h, int kernel_id, const double *xq, in
     if (!mu) return -17;
     if (!var) return -18;
     if (!work || ((uintptr_t)work & 7)) return -19;
-    if (work_bytes < nn_work_doubles(FVGP_NN_CONDITIONALS, nq, B) * (int64_t)sizeof(double)) {
+    if (work_bytes < fvgp_hip_nn_workspace_bytes(FVGP_NN_CONDITIONALS, nq, B)) {
         fvgp_set_error("nn_conditionals: work smaller than fvgp_hip_nn_workspace_bytes(FVGP_NN_CONDITIONALS, nq, B)"); return -20;
     }
     if (!info_host) return -21;
     HIPCHK(hipSetDevice(h->device));
-    rc = nn_run_conditionals(h, kernel_id, xq, nq, xr, nr, d, thetas_host, ntheta, B, idx, ld, m, r, v, s_or_null, mu, var, work);
+    rc = nn_run_conditionals(h, NN_VALUE, kernel_id, xq, nq, xr, nr, d, thetas_host, ntheta, B, idx, ld, m, r, v, s_or_null, mu, var, work, nullptr, nullptr);
     if (rc) return rc;
     long long info = 0;
     HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
@@ -598,153 +692,23 @@ int fvgp_hip_nn_conditionals(fvgp_handle *h, int kernel_id, const double *xq, in
 int fvgp_hip_nn_loglik(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *thetas_host, int ntheta, int B,
                        const int *idx, int64_t ld, int m, const double *r, const double *v, double *mu, double *var,
                        double *work, int64_t work_bytes, double *out_host, int64_t *info_host) {
-    if (!h) return -1;
-    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
-    if (!x) return -3;
-    if (n < 1 || n > 0x7fffffffLL) return -4;
-    int rc = check_kernel_args(kernel_id, d, thetas_host, ntheta, 5, 6, 7); if (rc) return rc;
-    if (B < 1 || B > 65535) { fvgp_set_error("nn_loglik: 1 .. 65535 hyperparameter vectors per call"); return -8; }
-    if (!idx) return -9;
-    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error("nn_loglik: 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -11; }
-    if (ld < m) return -10;
-    if (!r) return -12;
-    if (!v) return -13;
-    if (!mu) return -14;
-    if (!var) return -15;
-    if (!work || ((uintptr_t)work & 7)) return -16;
-    if (work_bytes < nn_work_doubles(FVGP_NN_LOGLIK, n, B) * (int64_t)sizeof(double)) {
-        fvgp_set_error("nn_loglik: work smaller than fvgp_hip_nn_workspace_bytes(FVGP_NN_LOGLIK, n, B)"); return -17;
-    }
-    if (!out_host) return -18;
-    if (!info_host) return -19;
-    HIPCHK(hipSetDevice(h->device));
-    rc = nn_run_conditionals(h, kernel_id, x, n, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, v, mu, var, work);
-    if (rc) return rc;
-    const int64_t ns = nn_slices(n);
-    double *out = work + nn_out_off(B), *part = work + nn_part_off(B);
-    HIPLAUNCH(nn_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, r, (const double *)mu, (const double *)var, (long)n, part);
-    HIPLAUNCH(nn_total_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), h->stream, (const double *)part, (long)ns, (long)n, B, out);
-    long long info = 0;
-    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(out_host, out, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    *info_host = info;
-    return 0;
-}
-
-int64_t fvgp_hip_nn_grad_workspace_bytes(int64_t n, int B, int ntheta) {
-    if (n < 1 || B < 1 || ntheta < 1) return -1;
-    return nn_grad_work_doubles(n, B, ntheta) * (int64_t)sizeof(double);
+    return nn_loglik(NN_VALUE, "nn_loglik", h, kernel_id, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, mu, var, nullptr, nullptr, work,
+                     work_bytes, out_host, nullptr, nullptr, info_host);
 }
 
 int fvgp_hip_nn_loglik_grad(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *thetas_host, int ntheta, int B,
                             const int *idx, int64_t ld, int m, const double *r, const double *v, double *mu, double *var, double *score,
                             double *work, int64_t work_bytes, double *out_host, double *grad_host, int64_t *info_host) {
-    if (!h) return -1;
-    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
-    if (!x) return -3;
-    if (n < 1 || n > 0x7fffffffLL) return -4;
-    int rc = check_kernel_args(kernel_id, d, thetas_host, ntheta, 5, 6, 7); if (rc) return rc;
-    if (B < 1 || B > 65535) { fvgp_set_error("nn_loglik_grad: 1 .. 65535 hyperparameter vectors per call"); return -8; }
-    if (!idx) return -9;
-    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error("nn_loglik_grad: 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -11; }
-    if (ld < m) return -10;
-    if (!r) return -12;
-    if (!v) return -13;
-    if (!mu) return -14;
-    if (!var) return -15;
-    if (!score) return -16;
-    if (!work || ((uintptr_t)work & 7)) return -17;
-    if (work_bytes < nn_grad_work_doubles(n, B, ntheta) * (int64_t)sizeof(double)) {
-        fvgp_set_error("nn_loglik_grad: work smaller than fvgp_hip_nn_grad_workspace_bytes(n, B, ntheta)"); return -18;
-    }
-    if (!out_host) return -19;
-    if (!grad_host) return -20;
-    if (!info_host) return -21;
-    HIPCHK(hipSetDevice(h->device));
-    rc = nn_run_conditionals(h, kernel_id, x, n, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, v, mu, var, work, score);
-    if (rc) return rc;
-    const int64_t ns = nn_slices(n);
-    double *out = work + nn_out_off(B), *part = work + nn_part_off(B);
-    double *grad = work + nn_grad_off(n, B), *gpart = work + nn_gpart_off(n, B, ntheta);
-    HIPLAUNCH(nn_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, r, (const double *)mu, (const double *)var, (long)n, part);
-    HIPLAUNCH(nn_total_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), h->stream, (const double *)part, (long)ns, (long)n, B, out);
-    HIPLAUNCH(nn_col_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, (const double *)score, (long)n, ntheta, gpart);
-    const long count = (long)B * ntheta;
-    HIPLAUNCH(nn_col_total_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), h->stream, (const double *)gpart, (long)ns, ntheta, count, grad);
-    long long info = 0;
-    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(out_host, out, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(grad_host, grad, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    *info_host = info;
-    return 0;
-}
-
-int64_t fvgp_hip_nn_fisher_workspace_bytes(int64_t n, int B, int ntheta) {
-    if (n < 1 || B < 1 || ntheta < 1) return -1;
-    return nn_fisher_work_doubles(n, B, ntheta) * (int64_t)sizeof(double);
+    return nn_loglik(NN_GRAD, "nn_loglik_grad", h, kernel_id, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, mu, var, score, nullptr, work,
+                     work_bytes, out_host, grad_host, nullptr, info_host);
 }
 
 int fvgp_hip_nn_loglik_fisher(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *thetas_host, int ntheta, int B,
                               const int *idx, int64_t ld, int m, const double *r, const double *v, double *mu, double *var, double *score,
                               double *fisher_rows, double *work, int64_t work_bytes, double *out_host, double *grad_host,
                               double *fisher_host, int64_t *info_host) {
-    if (!h) return -1;
-    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
-    if (!x) return -3;
-    if (n < 1 || n > 0x7fffffffLL) return -4;
-    int rc = check_kernel_args(kernel_id, d, thetas_host, ntheta, 5, 6, 7); if (rc) return rc;
-    if (B < 1 || B > 65535) { fvgp_set_error("nn_loglik_fisher: 1 .. 65535 hyperparameter vectors per call"); return -8; }
-    if (!idx) return -9;
-    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error("nn_loglik_fisher: 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -11; }
-    if (ld < m) return -10;
-    if (!r) return -12;
-    if (!v) return -13;
-    if (!mu) return -14;
-    if (!var) return -15;
-    if (!score) return -16;
-    if (!fisher_rows) return -17;
-    if (!work || ((uintptr_t)work & 7)) return -18;
-    if (work_bytes < nn_fisher_work_doubles(n, B, ntheta) * (int64_t)sizeof(double)) {
-        fvgp_set_error("nn_loglik_fisher: work smaller than fvgp_hip_nn_fisher_workspace_bytes(n, B, ntheta)"); return -19;
-    }
-    if (!out_host) return -20;
-    if (!grad_host) return -21;
-    if (!fisher_host) return -22;
-    if (!info_host) return -23;
-    HIPCHK(hipSetDevice(h->device));
-    rc = nn_run_conditionals(h, kernel_id, x, n, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, v, mu, var, work, score, fisher_rows);
-    if (rc) return rc;
-    const int64_t ns = nn_slices(n);
-    const int P = (int)nn_packed(ntheta);
-    double *out = work + nn_out_off(B), *part = work + nn_part_off(B);
-    double *grad = work + nn_grad_off(n, B), *gpart = work + nn_gpart_off(n, B, ntheta);
-    double *fis = work + nn_fis_off(n, B, ntheta), *fpart = work + nn_fpart_off(n, B, ntheta);
-    HIPLAUNCH(nn_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, r, (const double *)mu, (const double *)var, (long)n, part);
-    HIPLAUNCH(nn_total_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), h->stream, (const double *)part, (long)ns, (long)n, B, out);
-    HIPLAUNCH(nn_col_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, (const double *)score, (long)n, ntheta, gpart);
-    const long count = (long)B * ntheta, fcount = (long)B * P;
-    HIPLAUNCH(nn_col_total_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), h->stream, (const double *)gpart, (long)ns, ntheta, count, grad);
-    HIPLAUNCH(nn_col_terms_kernel, dim3((unsigned)ns, (unsigned)B), dim3(NN_SUM_ROWS), h->stream, (const double *)fisher_rows, (long)n, P, fpart);
-    HIPLAUNCH(nn_col_total_kernel, dim3((unsigned)((fcount + 63) / 64)), dim3(64), h->stream, (const double *)fpart, (long)ns, P, fcount, fis);
-    long long info = 0;
-    std::vector<double> packed((size_t)fcount);
-    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(out_host, out, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(grad_host, grad, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(packed.data(), fis, (size_t)fcount * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    *info_host = info;
-    // the packed lower triangles into full symmetric matrices
-    for (int b = 0; b < B; ++b)
-        for (int hh = 0; hh < ntheta; ++hh)
-            for (int kk = 0; kk <= hh; ++kk) {
-                const double f = packed[(size_t)b * P + (size_t)hh * (hh + 1) / 2 + kk];
-                fisher_host[((size_t)b * ntheta + hh) * ntheta + kk] = f;
-                fisher_host[((size_t)b * ntheta + kk) * ntheta + hh] = f;
-            }
-    return 0;
+    return nn_loglik(NN_FISHER, "nn_loglik_fisher", h, kernel_id, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, mu, var, score, fisher_rows,
+                     work, work_bytes, out_host, grad_host, fisher_host, info_host);
 }
 
 }  // extern "C"

@@ -32,6 +32,7 @@ closed form from the same factors (fvgp_hip_nn_loglik_fisher) -- come
 again: fisher_information, neg_log_likelihood_gradient_and_fisher and its _batch form, conditional_fisher (the per-point terms),
 train_gradient(method="fisher") (projected Fisher scoring; train(method="fisher") with args={"likelihood_gradient": True}) and
 hyperparameter_laplace (standard errors and hyperparameter samples from F^-1: the expected curvature, not the observed one)."""
+import collections
 import warnings
 
 import numpy as np
@@ -45,6 +46,7 @@ from .gp_lin_alg import NonPositiveDefiniteError
 
 _DENSE = "the dense fvgp_amd.GP has it"
 _LOG_2PI = float(np.log(2.0 * np.pi))
+_Evaluation = collections.namedtuple("_Evaluation", "out grad fisher info mu var score rows")      # what VecchiaGP._evaluate returns
 
 
 class VecchiaGP:
@@ -189,9 +191,9 @@ class VecchiaGP:
         return out
 
     def _unorder(self, a):
-        """per-point values in the ordering (last axis) -> the caller's order"""
+        """per-point values in the ordering (first axis) -> the caller's order"""
         out = np.empty_like(a)
-        out[..., self.ordering] = a
+        out[self.ordering] = a
         return out
 
     def _not_pd(self, info, nq, what, points=None):
@@ -202,26 +204,72 @@ class VecchiaGP:
             f"{self.n_neighbors} x {self.n_neighbors} neighbour block K + V or its conditional variance has a pivot that is not positive; "
             "duplicated points need positive noise, or rethink the hyperparameters")
 
-    # ---- the likelihood ----------------------------------------------------------------------------------------------------
-    def _loglik(self, thetas):
-        """(out (B, 3), info, mu (B, n), var (B, n)) of one device call at the rows of thetas"""
+    # ---- the likelihood, its gradient and its Fisher information: one evaluation at three levels -----------------------------------
+    def _evaluate(self, thetas, level):
+        """one device call at the rows of thetas (B, H), as far as `level` (_lib.NN_VALUE, NN_GRAD, NN_FISHER): out (B, 3), grad (B, H) =
+        d log p / d theta, fisher (B, H, H), info, and on the device mu, var (B, n), score (B, n, H), rows (B, n, H (H + 1) / 2); None
+        where the level has none"""
         H, n = self._H, self.point_number
-        B = thetas.shape[0]
+        B, nth = thetas.shape
         mu, var = H.empty(B, n), H.empty(B, n)
-        out, info = H.nn_loglik(self._native.kernel_id, self._x_dev, thetas, self._idx, self.n_neighbors, self._r_dev, self._V_dev, mu, var)
-        return out, info, mu, var
+        score = H.torch.empty((B, n, nth), dtype=H.torch.float64, device=mu.device) if level >= _lib.NN_GRAD else None
+        rows = H.torch.empty((B, n, nth * (nth + 1) // 2), dtype=H.torch.float64, device=mu.device) if level == _lib.NN_FISHER else None
+        out, grad, fisher, info = H._nn_likelihood(level, self._native.kernel_id, self._x_dev, thetas, self._idx, self.n_neighbors,
+                                                   self._r_dev, self._V_dev, mu, var, score, rows, None)
+        return _Evaluation(out, grad, fisher, info, mu, var, score, rows)
 
     def _one(self, hyperparameters):
         hps = self._hps if hyperparameters is None else self._check_hps(hyperparameters)
         return hps.reshape(1, -1)
 
+    def _at(self, hyperparameters, level, what):
+        """_evaluate at the object's hyperparameters or at `hyperparameters`; `what` names the caller where a conditional fails"""
+        ev = self._evaluate(self._one(hyperparameters), level)
+        if ev.info:
+            raise self._not_pd(ev.info, self.point_number, what)
+        return ev
+
+    def _chunk(self, level, nth):
+        """hyperparameter vectors per device call: 4096 for the value; with the gradient or the Fisher information, as many as keep the
+        call's per-row outputs (mu, var, score, fisher_rows) under args["grad_batch_bytes"]"""
+        if level == _lib.NN_VALUE:
+            return 4096
+        per_row = 2 + nth + (nth * (nth + 1) // 2 if level == _lib.NN_FISHER else 0)
+        cap = int(self.args.get("grad_batch_bytes", 1 << 30))
+        return int(max(1, min(65535, cap // (8 * self.point_number * per_row))))
+
+    def _grad_chunk(self, nth):
+        return self._chunk(_lib.NN_GRAD, nth)
+
+    def _fisher_chunk(self, nth):
+        return self._chunk(_lib.NN_FISHER, nth)
+
+    def _batch(self, thetas, level):
+        """(log p (B,), G (B, H) = -d log p / d theta, F (B, H, H)) at the B rows of `thetas`, in chunks of _chunk; None where the level
+        has none, NaN all three where a conditional is not positive definite"""
+        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+        assert thetas.ndim == 2 and thetas.shape[1] == len(self._hps), "thetas must be (B, number of hyperparameters)"
+        B, nth = thetas.shape
+        lp = np.empty(B)
+        G = np.empty((B, nth)) if level >= _lib.NN_GRAD else None
+        F = np.empty((B, nth, nth)) if level == _lib.NN_FISHER else None
+        step = self._chunk(level, nth)
+        for a in range(0, B, step):
+            ev = self._evaluate(thetas[a:a + step], level)
+            lp[a:a + step] = ev.out[:, 0]
+            if G is not None:
+                G[a:a + step] = -ev.grad
+            if F is not None:
+                F[a:a + step] = ev.fisher
+        for A in (G, F):
+            if A is not None:
+                A[np.isnan(lp)] = np.nan
+        return lp, G, F
+
     def log_likelihood(self, hyperparameters=None):
         """the nearest-neighbour log marginal likelihood at the object's hyperparameters or at `hyperparameters`: deterministic, the
         same bits on every call"""
-        out, info, _, _ = self._loglik(self._one(hyperparameters))
-        if info:
-            raise self._not_pd(info, self.point_number, "log_likelihood")
-        return float(out[0, 0])
+        return float(self._at(hyperparameters, _lib.NN_VALUE, "log_likelihood").out[0, 0])
 
     def neg_log_likelihood(self, hyperparameters=None):
         return -self.log_likelihood(hyperparameters)
@@ -229,12 +277,7 @@ class VecchiaGP:
     def log_likelihood_batch(self, thetas):
         """(B,): the log-likelihood at the B rows of `thetas` in one device call, each equal bit for bit to log_likelihood(thetas[b]);
         NaN where a conditional is not positive definite"""
-        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
-        assert thetas.ndim == 2 and thetas.shape[1] == len(self._hps), "thetas must be (B, number of hyperparameters)"
-        out = np.empty(len(thetas))
-        for a in range(0, len(thetas), 4096):
-            out[a:a + 4096] = self._loglik(thetas[a:a + 4096])[0][:, 0]
-        return out
+        return self._batch(thetas, _lib.NN_VALUE)[0]
 
     def neg_log_likelihood_batch(self, thetas):
         """-log_likelihood_batch with +inf where it is NaN (what a population optimiser wants to see)"""
@@ -244,52 +287,24 @@ class VecchiaGP:
     def conditionals(self, hyperparameters=None):
         """{"mean", "variance", "log_predictive"} (N,) each, in the caller's order: every data point's conditional given its neighbours,
         the factors of the likelihood (their log_predictive sum to it up to rounding) and the approximation's residual diagnostics"""
-        out, info, mu, var = self._loglik(self._one(hyperparameters))
-        if info:
-            raise self._not_pd(info, self.point_number, "conditionals")
-        mu, var = self._H.to_host(mu)[0], self._H.to_host(var)[0]
+        ev = self._at(hyperparameters, _lib.NN_VALUE, "conditionals")
+        mu, var = self._H.to_host(ev.mu)[0], self._H.to_host(ev.var)[0]
         r = (self.y_data - self._m)[self.ordering]
         lp = -0.5 * ((r - mu) ** 2 / var + np.log(var) + _LOG_2PI)
         return {"mean": self._unorder(self._m + mu), "variance": self._unorder(var), "log_predictive": self._unorder(lp)}
 
-    # ---- the gradient --------------------------------------------------------------------------------------------------------
-    def _loglik_grad(self, thetas):
-        """(out (B, 3), grad (B, H) = d log p / d theta, info, score (B, n, H) device) of one device call at the rows of thetas"""
-        H, n = self._H, self.point_number
-        B, nth = thetas.shape
-        mu, var = H.empty(B, n), H.empty(B, n)
-        score = H.torch.empty((B, n, nth), dtype=H.torch.float64, device=mu.device)
-        out, grad, info = H.nn_loglik_grad(self._native.kernel_id, self._x_dev, thetas, self._idx, self.n_neighbors, self._r_dev,
-                                           self._V_dev, mu, var, score)
-        return out, grad, info, score
-
     def neg_log_likelihood_and_gradient(self, hyperparameters=None):
         """(f, g (H,)): the negative nearest-neighbour log-likelihood and its exact gradient from one device call; deterministic, the
         same bits on every call"""
-        out, grad, info, _ = self._loglik_grad(self._one(hyperparameters))
-        if info:
-            raise self._not_pd(info, self.point_number, "neg_log_likelihood_and_gradient")
-        return -float(out[0, 0]), -grad[0]
-
-    def _grad_chunk(self, nth):
-        """hyperparameter vectors per device call: mu, var and score of a call stay under args["grad_batch_bytes"]"""
-        cap = int(self.args.get("grad_batch_bytes", 1 << 30))
-        return int(max(1, min(65535, cap // (8 * self.point_number * (2 + nth)))))
+        ev = self._at(hyperparameters, _lib.NN_GRAD, "neg_log_likelihood_and_gradient")
+        return -float(ev.out[0, 0]), -ev.grad[0]
 
     def neg_log_likelihood_and_gradient_batch(self, thetas):
         """(f (B,), G (B, H)) at the B rows of `thetas`, each row equal bit for bit to neg_log_likelihood_and_gradient(thetas[b]); the
         batch goes in chunks whose per-row outputs fit args["grad_batch_bytes"].  Where a conditional is not positive definite the value
         is +inf and the gradient NaN."""
-        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
-        assert thetas.ndim == 2 and thetas.shape[1] == len(self._hps), "thetas must be (B, number of hyperparameters)"
-        f, G = np.empty(len(thetas)), np.empty(thetas.shape)
-        step = self._grad_chunk(thetas.shape[1])
-        for a in range(0, len(thetas), step):
-            out, grad, _, _ = self._loglik_grad(thetas[a:a + step])
-            f[a:a + step], G[a:a + step] = -out[:, 0], -grad
-        bad = np.isnan(f)
-        G[bad] = np.nan
-        return np.where(bad, np.inf, f), G
+        lp, G, _ = self._batch(thetas, _lib.NN_GRAD)
+        return np.where(np.isnan(lp), np.inf, -lp), G
 
     def neg_log_likelihood_gradient_batch(self, thetas):
         return self.neg_log_likelihood_and_gradient_batch(thetas)[1]
@@ -297,74 +312,35 @@ class VecchiaGP:
     def conditional_scores(self, hyperparameters=None):
         """(N, H), in the caller's order: row i is d log p(y_i | its neighbours) / d theta, the per-point terms that sum to the gradient
         of log_likelihood (diagnostics, and the raw material of minibatch methods)"""
-        out, grad, info, score = self._loglik_grad(self._one(hyperparameters))
-        if info:
-            raise self._not_pd(info, self.point_number, "conditional_scores")
-        s = np.empty((self.point_number, score.shape[2]))
-        s[self.ordering] = score[0].cpu().numpy()
-        return s
-
-    # ---- the Fisher information ------------------------------------------------------------------------------------------------
-    def _loglik_fisher(self, thetas):
-        """(out (B, 3), grad (B, H), fisher (B, H, H), info, fisher_rows (B, n, H (H + 1) / 2) device) of one device call at the rows of
-        thetas"""
-        H, n = self._H, self.point_number
-        B, nth = thetas.shape
-        mu, var = H.empty(B, n), H.empty(B, n)
-        score = H.torch.empty((B, n, nth), dtype=H.torch.float64, device=mu.device)
-        rows = H.torch.empty((B, n, nth * (nth + 1) // 2), dtype=H.torch.float64, device=mu.device)
-        out, grad, fisher, info = H.nn_loglik_fisher(self._native.kernel_id, self._x_dev, thetas, self._idx, self.n_neighbors, self._r_dev,
-                                                     self._V_dev, mu, var, score, rows)
-        return out, grad, fisher, info, rows
+        return self._unorder(self._at(hyperparameters, _lib.NN_GRAD, "conditional_scores").score[0].cpu().numpy())
 
     def neg_log_likelihood_gradient_and_fisher(self, hyperparameters=None):
         """(f, g (H,), F (H, H)) from one device call: the negative nearest-neighbour log-likelihood, its exact gradient and the Fisher
         information of the approximation -- the EXPECTED Hessian of f under the exact GP at these hyperparameters, positive semidefinite
         by construction, for about the cost of a second gradient"""
-        out, grad, fisher, info, _ = self._loglik_fisher(self._one(hyperparameters))
-        if info:
-            raise self._not_pd(info, self.point_number, "neg_log_likelihood_gradient_and_fisher")
-        return -float(out[0, 0]), -grad[0], fisher[0]
+        ev = self._at(hyperparameters, _lib.NN_FISHER, "neg_log_likelihood_gradient_and_fisher")
+        return -float(ev.out[0, 0]), -ev.grad[0], ev.fisher[0]
 
     def fisher_information(self, hyperparameters=None):
         """(H, H): the Fisher information of the nearest-neighbour likelihood; its inverse is the asymptotic covariance of the
         maximum-likelihood hyperparameters"""
         return self.neg_log_likelihood_gradient_and_fisher(hyperparameters)[2]
 
-    def _fisher_chunk(self, nth):
-        """hyperparameter vectors per device call: mu, var, score and fisher_rows of a call stay under args["grad_batch_bytes"]"""
-        cap = int(self.args.get("grad_batch_bytes", 1 << 30))
-        return int(max(1, min(65535, cap // (8 * self.point_number * (2 + nth + nth * (nth + 1) // 2)))))
-
     def neg_log_likelihood_gradient_and_fisher_batch(self, thetas):
         """(f (B,), G (B, H), F (B, H, H)) at the B rows of `thetas`, each row equal bit for bit to
         neg_log_likelihood_gradient_and_fisher(thetas[b]); the batch goes in chunks whose per-row outputs fit args["grad_batch_bytes"].
         Where a conditional is not positive definite the value is +inf, the gradient and the Fisher matrix NaN."""
-        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
-        assert thetas.ndim == 2 and thetas.shape[1] == len(self._hps), "thetas must be (B, number of hyperparameters)"
-        nth = thetas.shape[1]
-        f, G, F = np.empty(len(thetas)), np.empty(thetas.shape), np.empty((len(thetas), nth, nth))
-        step = self._fisher_chunk(nth)
-        for a in range(0, len(thetas), step):
-            out, grad, fisher, _, _ = self._loglik_fisher(thetas[a:a + step])
-            f[a:a + step], G[a:a + step], F[a:a + step] = -out[:, 0], -grad, fisher
-        bad = np.isnan(f)
-        G[bad], F[bad] = np.nan, np.nan
-        return np.where(bad, np.inf, f), G, F
+        lp, G, F = self._batch(thetas, _lib.NN_FISHER)
+        return np.where(np.isnan(lp), np.inf, -lp), G, F
 
     def conditional_fisher(self, hyperparameters=None):
         """(N, H, H), in the caller's order: entry i is data point i's term of the Fisher information, E[-d^2 log p(y_i | its
         neighbours)]; positive semidefinite each, they sum to fisher_information"""
-        out, grad, fisher, info, rows = self._loglik_fisher(self._one(hyperparameters))
-        if info:
-            raise self._not_pd(info, self.point_number, "conditional_fisher")
-        nth = fisher.shape[1]
-        packed = rows[0].cpu().numpy()
-        full = np.empty((self.point_number, nth, nth))
-        for h in range(nth):
-            for k in range(h + 1):
-                full[self.ordering, h, k] = full[self.ordering, k, h] = packed[:, h * (h + 1) // 2 + k]
-        return full
+        packed = self._at(hyperparameters, _lib.NN_FISHER, "conditional_fisher").rows[0].cpu().numpy()
+        h, k = np.tril_indices(len(self._hps))            # the packed lower triangle: (h, k <= h) at h (h + 1) / 2 + k
+        full = np.empty((self.point_number, len(self._hps), len(self._hps)))
+        full[:, h, k] = full[:, k, h] = packed
+        return self._unorder(full)
 
     def hyperparameter_laplace(self, hyperparameters=None, n_samples=0, seed=0, bounds=None):
         """gp_hessian.laplace_from_hessian at `hyperparameters` (None: the current, trained ones) with the Fisher information in the

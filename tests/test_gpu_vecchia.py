@@ -9,10 +9,10 @@ import numpy as np
 import pytest
 
 import vecchia_ref as vr
+from vecchia_device import CANARY, _device_loglik, _frame_untouched, _framed, _kid
 
 pytestmark = pytest.mark.gpu
 
-CANARY = -7.25e300
 ICANARY = -7777
 LD = vr.LD
 
@@ -23,11 +23,6 @@ def H():
     h = _lib.Handle(0)
     yield h
     h.close()
-
-
-def _kid(kernel):
-    from fvgp_amd import _lib
-    return _lib.KERNEL_IDS[kernel]
 
 
 def _framed_idx(H, nq, m):
@@ -42,17 +37,6 @@ def _framed_idx(H, nq, m):
 def _idx_frame_untouched(big, nq, m):
     a = big.cpu().numpy()
     return np.all(a[0] == ICANARY) and np.all(a[1 + nq:] == ICANARY) and np.all(a[:, m:] == ICANARY)
-
-
-def _framed_rows(H, B, n):
-    """a contiguous (B, n) view inside a canary-filled flat buffer: (buffer, view)"""
-    big = H.torch.full((B * n + 16,), CANARY, dtype=H.torch.float64, device=f"cuda:{H.device}")
-    return big, big[8:8 + B * n].view(B, n)
-
-
-def _rows_frame_untouched(big, B, n):
-    a = big.cpu().numpy()
-    return np.all(a[:8] == CANARY) and np.all(a[8 + B * n:] == CANARY)
 
 
 def _search(H, xq, xr, m, scales=None, c0=-1):
@@ -144,21 +128,6 @@ def test_search_argument_rules(H):
 
 
 # ---- 2. conditionals and likelihood against longdouble ---------------------------------------------------------------------------------------
-def _device_loglik(H, case, thetas=None):
-    """Handle.nn_loglik on a case's inputs (the twin's neighbour lists) into framed mu / var: (out (B, 3), info, mu (B, n), var (B, n))"""
-    name, d, n, m, B = case
-    x, th, r, v, idx = vr.case_inputs(case)
-    th = th if thetas is None else thetas
-    B = len(th)
-    t = H.torch
-    mbig, mu = _framed_rows(H, B, n)
-    vbig, var = _framed_rows(H, B, n)
-    idx_d = t.as_tensor(np.ascontiguousarray(idx), device=mu.device)
-    out, info = H.nn_loglik(_kid(name), H.to_device(x), th, idx_d, m, H.to_device(r), H.to_device(v), mu, var)
-    assert _rows_frame_untouched(mbig, B, n) and _rows_frame_untouched(vbig, B, n)
-    return out, info, mu.cpu().numpy(), var.cpu().numpy()
-
-
 @pytest.mark.parametrize("case", vr.ACC_CASES, ids=vr.case_id)
 def test_conditionals_and_likelihood_against_longdouble(H, case):
     """Bars from the float64 twin, never from the device: every figure <= MARGIN * max(base, FLOOR) (vecchia_ref)."""
@@ -222,8 +191,8 @@ def test_conditionals_argument_rules(H):
     x = H.to_device(np.random.default_rng(1).random((n, 3)))
     r, v = H.to_device(np.ones(n)), H.to_device(np.ones(n))
     idx = t.full((n, m), -1, dtype=t.int32, device=x.device)
-    mbig, mu = _framed_rows(H, B, n)
-    vbig, var = _framed_rows(H, B, n)
+    mbig, mu = _framed(H, B, n)
+    vbig, var = _framed(H, B, n)
     wb = _lib.nn_workspace_bytes(_lib.NN_LOGLIK, n, B)
     work = t.full((wb // 8,), CANARY, dtype=t.float64, device=x.device)
     th = np.ones((B, 4))
@@ -304,11 +273,11 @@ def test_failure_is_reported_not_trapped(H):
     thetas = np.array([np.concatenate([[4.0], theta[1:]]), np.concatenate([[1.0], 1.5 * theta[1:]])])
     t = H.torch
     xd, rd, vd = H.to_device(x), H.to_device(r), H.to_device(v0)
-    mbig, mu = _framed_rows(H, 2, n)
-    vbig, var = _framed_rows(H, 2, n)
+    mbig, mu = _framed(H, 2, n)
+    vbig, var = _framed(H, 2, n)
     out, info = H.nn_loglik(_kid(name), xd, thetas, t.as_tensor(idx, device=xd.device), m, rd, vd, mu, var)
     mu, var = mu.cpu().numpy(), var.cpu().numpy()
-    assert _rows_frame_untouched(mbig, 2, n) and _rows_frame_untouched(vbig, 2, n)
+    assert _frame_untouched(mbig) and _frame_untouched(vbig)
     bad = ~(var > 0.0)
     assert bad[0, 20] and bad[1, 20] and bad.sum() == 2, "the singular row fails at both thetas, no other row does"
     assert info == 1 + 0 * n + 20

@@ -9,10 +9,10 @@ import pytest
 
 import vecchia_fisher_ref as vf
 import vecchia_ref as vr
+from vecchia_device import CANARY, _device_fisher, _device_grad, _frame_untouched, _framed, _same
 
 pytestmark = pytest.mark.gpu
 
-CANARY = -7.25e300
 LD = vr.LD
 
 
@@ -22,57 +22,6 @@ def H():
     h = _lib.Handle(0)
     yield h
     h.close()
-
-
-def _kid(kernel):
-    from fvgp_amd import _lib
-    return _lib.KERNEL_IDS[kernel]
-
-
-def _framed(H, *shape):
-    """a contiguous view of `shape` inside a canary-filled flat buffer: (buffer, view)"""
-    size = int(np.prod(shape))
-    big = H.torch.full((size + 16,), CANARY, dtype=H.torch.float64, device=f"cuda:{H.device}")
-    return big, big[8:8 + size].view(*shape)
-
-
-def _frame_untouched(big):
-    a = big.cpu().numpy()
-    return np.all(a[:8] == CANARY) and np.all(a[-8:] == CANARY)
-
-
-def _device_fisher(H, name, x, thetas, idx, m, r, v):
-    """Handle.nn_loglik_fisher into framed outputs: (out (B, 3), grad (B, H), fisher (B, H, H), info, mu, var, score (B, n, H),
-    rows (B, n, P)) on the host"""
-    thetas = np.atleast_2d(thetas)
-    B, nth = thetas.shape
-    n = len(x)
-    mbig, mu = _framed(H, B, n)
-    vbig, var = _framed(H, B, n)
-    sbig, score = _framed(H, B, n, nth)
-    fbig, rows = _framed(H, B, n, nth * (nth + 1) // 2)
-    idx_d = H.torch.as_tensor(np.ascontiguousarray(idx), device=mu.device)
-    out, grad, fisher, info = H.nn_loglik_fisher(_kid(name), H.to_device(x), thetas, idx_d, m, H.to_device(r), H.to_device(v), mu, var,
-                                                 score, rows)
-    assert all(_frame_untouched(b) for b in (mbig, vbig, sbig, fbig))
-    assert not np.any(rows.cpu().numpy() == CANARY), "every entry of fisher_rows is written"
-    return out, grad, fisher, info, mu.cpu().numpy(), var.cpu().numpy(), score.cpu().numpy(), rows.cpu().numpy()
-
-
-def _device_grad(H, name, x, thetas, idx, m, r, v):
-    thetas = np.atleast_2d(thetas)
-    B, nth = thetas.shape
-    n = len(x)
-    mu, var = H.empty(B, n), H.empty(B, n)
-    score = H.torch.empty((B, n, nth), dtype=H.torch.float64, device=mu.device)
-    idx_d = H.torch.as_tensor(np.ascontiguousarray(idx), device=mu.device)
-    out, grad, info = H.nn_loglik_grad(_kid(name), H.to_device(x), thetas, idx_d, m, H.to_device(r), H.to_device(v), mu, var, score)
-    return out, grad, info, mu.cpu().numpy(), var.cpu().numpy(), score.cpu().numpy()
-
-
-def _same(a, b):
-    """bit for bit, NaN in the same places"""
-    return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
 
 
 # ---- 1. accuracy against longdouble ------------------------------------------------------------------------------------------------------
@@ -128,6 +77,40 @@ def test_bit_contracts(H):
     other = np.cos(17.0 * np.arange(n)) * 3.0
     o = _device_fisher(H, name, x, thetas, idx, m, other, v)
     assert _same(o[7], rows) and _same(o[2], fisher) and _same(o[5], var) and not _same(o[6], score)
+
+
+def _documented_sum(col):
+    """the header's order in float64: slices of 256 rows (the last one padded with 0.0) by the halving tree, the slices to 0 ascending"""
+    a = np.zeros((len(col) + 255) // 256 * 256)
+    a[:len(col)] = col
+    s = np.float64(0.0)
+    for t in a.reshape(-1, 256):
+        for off in (128, 64, 32, 16, 8, 4, 2, 1):
+            t[:off] += t[off:2 * off]
+        s += t[0]
+    return s
+
+
+@pytest.mark.parametrize("n", [1, 256, 257])
+def test_summation_order(H, n):
+    """grad and fisher are the documented sums of score and fisher_rows, bit for bit: a lone row, a full slice, a second slice of one row;
+    with B = 2 and 3 / 6 columns, every stride of the partial sums.  (fit and logdet: the device's division and log are not numpy's.)"""
+    name, d, m, B = "matern32_ard", 2, 2, 2
+    rng = np.random.default_rng(2600 + n)
+    x, r, v = rng.random((n, d)), rng.standard_normal(n), 0.01 + 0.05 * rng.random(n)
+    thetas = np.array([[1.0, 0.3, 0.4], [1.7, 0.5, 0.2]])
+    xd = H.to_device(x)
+    idx = H.torch.empty((n, m), dtype=H.torch.int32, device=xd.device)
+    H.nn_search(xd, xd, m, idx, c0=0)
+    out, grad, fisher, info, mu, var, score, rows = _device_fisher(H, name, x, thetas, idx.cpu().numpy(), m, r, v)
+    nth = thetas.shape[1]
+    assert info == 0 and score.shape == (B, n, nth) and rows.shape == (B, n, nth * (nth + 1) // 2)
+    for b in range(B):
+        for h in range(nth):
+            assert grad[b, h] == _documented_sum(score[b, :, h]), (b, h)
+            for k in range(h + 1):
+                assert fisher[b, h, k] == _documented_sum(rows[b, :, h * (h + 1) // 2 + k]), (b, h, k)
+        assert np.array_equal(fisher[b], fisher[b].T), b
 
 
 # ---- 3. exactness ------------------------------------------------------------------------------------------------------------------------------

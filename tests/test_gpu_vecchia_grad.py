@@ -10,10 +10,10 @@ import pytest
 
 import vecchia_grad_ref as vg
 import vecchia_ref as vr
+from vecchia_device import CANARY, _device_grad, _device_value, _frame_untouched, _framed, _same
 
 pytestmark = pytest.mark.gpu
 
-CANARY = -7.25e300
 LD = vr.LD
 
 
@@ -23,51 +23,6 @@ def H():
     h = _lib.Handle(0)
     yield h
     h.close()
-
-
-def _kid(kernel):
-    from fvgp_amd import _lib
-    return _lib.KERNEL_IDS[kernel]
-
-
-def _framed(H, *shape):
-    """a contiguous view of `shape` inside a canary-filled flat buffer: (buffer, view)"""
-    size = int(np.prod(shape))
-    big = H.torch.full((size + 16,), CANARY, dtype=H.torch.float64, device=f"cuda:{H.device}")
-    return big, big[8:8 + size].view(*shape)
-
-
-def _frame_untouched(big):
-    a = big.cpu().numpy()
-    return np.all(a[:8] == CANARY) and np.all(a[-8:] == CANARY)
-
-
-def _device_grad(H, name, x, thetas, idx, m, r, v):
-    """Handle.nn_loglik_grad into framed mu / var / score: (out (B, 3), grad (B, H), info, mu, var, score (B, n, H)) on the host"""
-    thetas = np.atleast_2d(thetas)
-    B, nth = thetas.shape
-    n = len(x)
-    mbig, mu = _framed(H, B, n)
-    vbig, var = _framed(H, B, n)
-    sbig, score = _framed(H, B, n, nth)
-    idx_d = H.torch.as_tensor(np.ascontiguousarray(idx), device=mu.device)
-    out, grad, info = H.nn_loglik_grad(_kid(name), H.to_device(x), thetas, idx_d, m, H.to_device(r), H.to_device(v), mu, var, score)
-    assert _frame_untouched(mbig) and _frame_untouched(vbig) and _frame_untouched(sbig)
-    return out, grad, info, mu.cpu().numpy(), var.cpu().numpy(), score.cpu().numpy()
-
-
-def _device_value(H, name, x, thetas, idx, m, r, v):
-    thetas = np.atleast_2d(thetas)
-    B, n = len(thetas), len(x)
-    mu, var = H.empty(B, n), H.empty(B, n)
-    idx_d = H.torch.as_tensor(np.ascontiguousarray(idx), device=mu.device)
-    out, info = H.nn_loglik(_kid(name), H.to_device(x), thetas, idx_d, m, H.to_device(r), H.to_device(v), mu, var)
-    return out, info, mu.cpu().numpy(), var.cpu().numpy()
-
-
-def _same(a, b):
-    """bit for bit, NaN in the same places"""
-    return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
 
 
 # ---- 1. accuracy against longdouble ------------------------------------------------------------------------------------------------------
