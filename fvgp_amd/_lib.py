@@ -198,6 +198,8 @@ _ABI_NN = {
     "fvgp_hip_nn_loglik_fisher": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, P_d,
                                         P_d, P_d, P_l]),
     "fvgp_hip_nn_fisher_workspace_bytes": (c_l, [c_l, c_i, c_i]),
+    "fvgp_hip_nn_maxmin_workspace_bytes": (c_l, [c_l]),
+    "fvgp_hip_nn_maxmin_order": (c_i, [c_p, c_p, c_l, c_i, P_d, c_l, c_l, c_p, c_p, c_p, c_l]),
 }
 SYMBOLS_NN = list(_ABI_NN)
 NN_MAX_NEIGHBORS = 64     # FVGP_NN_MAX_NEIGHBORS
@@ -371,6 +373,11 @@ def nn_fisher_workspace_bytes(n, B=1, ntheta=2):
     """bytes of the caller-owned workspace of Handle.nn_loglik_fisher for n rows, B hyperparameter vectors of ntheta numbers
     (fvgp_hip_nn_fisher_workspace_bytes); -1 for bad arguments"""
     return _workspace_bytes("fvgp_hip_nn_fisher_workspace_bytes", n, B, ntheta)
+
+
+def nn_maxmin_workspace_bytes(n):
+    """bytes of the caller-owned workspace of Handle.nn_maxmin_order for n points (fvgp_hip_nn_maxmin_workspace_bytes); -1 for n < 1"""
+    return _workspace_bytes("fvgp_hip_nn_maxmin_workspace_bytes", n)
 
 
 def loglik_hess_workspace_bytes(n, d):
@@ -999,6 +1006,28 @@ class Handle(DistCalls):
             sp = sc.ctypes.data_as(P_d)
         self._call("fvgp_hip_nn_search", _ptr(xq), xq.shape[0], _ptr(xr), xr.shape[0], xq.shape[1], sp, int(m), int(c0),
                    _ptr(idx_out), idx_out.stride(0))
+
+    def nn_maxmin_order(self, x, first, q=None, scales=None, want_distances=True):
+        """fvgp_hip_nn_maxmin_order: the exact maxmin ordering of the rows of the device tensor x (n, d) from the point `first`, its
+        first q positions (default: all n), distances as in nn_search (scales None or d positive numbers, host).  Returns (perm (q,)
+        int64 ndarray, dist (q,) float64 ndarray or None): dist[t] is the squared scaled distance of perm[t] to the nearest earlier pick,
+        dist[0] = inf.  q launches in stream order, then one synchronisation for the results."""
+        n, d = x.shape
+        q = n if q is None else int(q)
+        if not x.is_contiguous() or x.dtype != self.torch.float64:
+            raise ValueError(f"nn_maxmin_order: x must be a contiguous float64 (n, d) tensor, got {tuple(x.shape)} {x.dtype}")
+        sp = None
+        if scales is not None:
+            sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
+            if sc.shape != (d,):
+                raise ValueError(f"nn_maxmin_order: scales must be {d} numbers")
+            sp = sc.ctypes.data_as(P_d)
+        perm = self.torch.empty((max(q, 1),), dtype=self.torch.int64, device=x.device)
+        dist = self.empty(max(q, 1)) if want_distances else None
+        work = self.empty(max(1, nn_maxmin_workspace_bytes(n)) // 8)
+        self._call("fvgp_hip_nn_maxmin_order", _ptr(x), n, d, sp, int(first), q, _ptr(perm), _ptr(dist), _ptr(work), work.numel() * 8)
+        self.sync()
+        return perm.cpu().numpy(), None if dist is None else dist.cpu().numpy()
 
     def _nn_operands(self, who, thetas, idx, nq, m, mu, var):
         t = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))

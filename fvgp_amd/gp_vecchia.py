@@ -16,16 +16,21 @@ values as m grows.  Prediction at x* conditions on the m nearest data points: th
     big.train_gradient(bounds, method="fisher"); big.hyperparameter_laplace()["std_error"]
     big.posterior_mean(x_pred); big.posterior_covariance(x_pred, variance_only=True)
 
+The ordering decides how good the approximation is at a given m.  ordering="maxmin" is the literature's default (GpGp, GPvecchia): the
+exact farthest-point ordering, computed on the device (fvgp_hip_nn_maxmin_order, DESIGN 27: N steps of O(N) work, one launch each), so
+that the early conditioning sets span the domain and the late ones are local; args["maxmin_points"] = q orders only the first q
+positions that way and bounds the construction to q launches.  ordering_distances keeps the distance at which each point entered.
+
 "Nearest" is measured after dividing every coordinate by a scale (args["neighbor_scales"]: the length scales at construction, 1, or a
 vector), and the neighbour lists stay FIXED while the hyperparameters move (set_hyperparameters, training): the likelihood is then a
-smooth function of theta.  refresh_neighbors() rebuilds them.
+smooth function of theta.  refresh_neighbors() rebuilds them, with reorder=True the maxmin ordering under the new scales as well.
 
 The exact gradient of this likelihood comes from the same device call as its value (fvgp_hip_nn_loglik_grad: two back-substitutions with
 the m x m factor that is already there, and one more sweep over each block's kernel entries with their derivatives):
 neg_log_likelihood_and_gradient, its _batch forms, conditional_scores (the per-point terms that sum to it) and train_gradient ("local":
 scipy's bounded optimisers, "adam": projected Adam, multi-start with args["adam_starts"]) are always there.  The fvgp.GP names
-neg_log_likelihood_gradient and train(method="local" | "adam") take this route with args={"likelihood_gradient": True}.  A tree search, a
-maxmin ordering and joint covariances are not built.
+neg_log_likelihood_gradient and train(method="local" | "adam") take this route with args={"likelihood_gradient": True}.  A tree search
+and joint covariances are not built.
 
 The Fisher information of this likelihood -- the expected Hessian of neg_log_likelihood under the exact GP, positive semidefinite, in
 closed form from the same factors (fvgp_hip_nn_loglik_fisher) -- comes from one more device call of about the gradient's cost
@@ -49,12 +54,23 @@ _LOG_2PI = float(np.log(2.0 * np.pi))
 _Evaluation = collections.namedtuple("_Evaluation", "out grad fisher info mu var score rows")      # what VecchiaGP._evaluate returns
 
 
+def first_point(x, scales=None):
+    """where a maxmin ordering of the rows of x (n, d) starts: the point nearest, in the scaled coordinates x / scales, to their mean
+    (ties to the lowest index) -- GpGp's convention"""
+    z = x if scales is None else x * (1.0 / np.asarray(scales, dtype=np.float64))
+    return int(np.argmin(np.sum((z - np.mean(z, axis=0)) ** 2, axis=1)))
+
+
 class VecchiaGP:
     """The nearest-neighbour GP over x_data (N, D), y_data (N,): hyperparameters in the named kernel's layout, noise_variances (N,) or
     None (the rule and the warning of GP: (0.01 mean|y|)^2), prior mean = mean(y).
 
-    n_neighbors: m in 1 .. 64.  ordering: "random" (a permutation drawn from `seed`), "given" (the caller's order) or a permutation
-    array; the data are held in that order and everything returned per data point is in the CALLER's order.  args:
+    n_neighbors: m in 1 .. 64.  ordering: "random" (a permutation drawn from `seed`), "given" (the caller's order), "maxmin" (the exact
+    farthest-point ordering under the neighbour scales, from the point nearest the centre of the scaled data) or a permutation array;
+    the data are held in that order and everything returned per data point is in the CALLER's order.  ordering_distances (N,), in
+    ordering position: under "maxmin" the scaled distance to the nearest earlier point at which each point entered (inf at position 0,
+    nan past args["maxmin_points"] and for appended points), else None.  args: "maxmin_points" (None: all N; q in 1 .. N: only the
+    first q positions are ordered by maxmin, the other points follow in a random order drawn from `seed`);
     "neighbor_scales" = "lengthscales" (default: the kernel's length scales at construction), "unit" or a D-vector;
     "batch_population" (True: train(method="global") scores a generation in one device call); "likelihood_gradient" (True: the fvgp.GP
     names neg_log_likelihood_gradient and train(method="local" | "adam" | "fisher") run the exact gradient); "adam_starts" (S >= 2:
@@ -92,7 +108,7 @@ class VecchiaGP:
         self._scale_mode = self.args.get("neighbor_scales", "lengthscales")
         self._scales = self._scales_at(self._hps, x_data.shape[1])
         self._ordering_rule = (ordering if isinstance(ordering, str) else "given", seed)
-        self._set_data(x_data, y_data, noise_variances, self._make_ordering(ordering, len(x_data), seed))
+        self._set_data(x_data, y_data, noise_variances, *self._ordering_of(ordering, x_data))
         self._search_all()
 
     # ---- state -----------------------------------------------------------------------------------------------------------
@@ -127,14 +143,38 @@ class VecchiaGP:
                 return np.random.default_rng(seed).permutation(n).astype(np.int64)
             if ordering == "given":
                 return np.arange(n, dtype=np.int64)
-            raise ValueError(f"ordering must be 'random', 'given' or a permutation of range({n}), got {ordering!r}")
+            raise ValueError(f"ordering must be 'random', 'given', 'maxmin' or a permutation of range({n}), got {ordering!r}")
         perm = np.array(ordering, dtype=np.int64)
         if perm.shape != (n,) or not np.array_equal(np.sort(perm), np.arange(n)):
-            raise ValueError(f"ordering must be 'random', 'given' or a permutation of range({n})")
+            raise ValueError(f"ordering must be 'random', 'given', 'maxmin' or a permutation of range({n})")
         return perm
 
-    def _set_data(self, x_data, y_data, noise_variances, perm):
-        """the caller's arrays as they came, and on the device in the ordering `perm` (position p holds the caller's row perm[p])"""
+    def _maxmin(self, x_data):
+        """(perm, entry distances): the maxmin ordering of x_data under the object's scales from first_point's point, its first
+        args["maxmin_points"] positions by the device (fvgp_hip_nn_maxmin_order), the points left over behind them in a random order"""
+        x = np.ascontiguousarray(x_data, dtype=np.float64)
+        n = len(x)
+        if not np.all(np.isfinite(x)):
+            raise ValueError("ordering='maxmin' needs finite coordinates in x_data")
+        q = self.args.get("maxmin_points")
+        q = n if q is None else q
+        if isinstance(q, bool) or int(q) != q or not 1 <= int(q) <= n:
+            raise ValueError(f"args['maxmin_points'] must be None or an integer in 1 .. {n} (the number of data points), got {q!r}")
+        q = int(q)
+        head, dist2 = self._H.nn_maxmin_order(self._H.to_device(x), first_point(x, self._scales), q, scales=self._scales)
+        rest = np.setdiff1d(np.arange(n, dtype=np.int64), head)
+        rest = rest[np.random.default_rng(self._ordering_rule[1]).permutation(len(rest))]
+        return np.concatenate([head, rest]), np.concatenate([np.sqrt(dist2), np.full(n - q, np.nan)])
+
+    def _ordering_of(self, ordering, x_data):
+        """(perm, entry distances or None) of x_data by `ordering`: a rule's name or a permutation"""
+        if isinstance(ordering, str) and ordering == "maxmin":
+            return self._maxmin(x_data)
+        return self._make_ordering(ordering, len(x_data), self._ordering_rule[1]), None
+
+    def _set_data(self, x_data, y_data, noise_variances, perm, distances=None):
+        """the caller's arrays as they came, and on the device in the ordering `perm` (position p holds the caller's row perm[p]);
+        `distances`: what ordering_distances becomes"""
         H = self._H
         self._check_dim(x_data)
         self.x_data = np.ascontiguousarray(x_data, dtype=np.float64)
@@ -150,6 +190,7 @@ class VecchiaGP:
         self._V = np.ascontiguousarray(V)
         self._m = float(np.mean(self.y_data))
         self.ordering = perm
+        self.ordering_distances = distances
         self._x_dev = H.to_device(self.x_data[perm])
         self._V_dev = H.to_device(self._V[perm])
         self._r_dev = H.to_device((self.y_data - self._m)[perm])
@@ -175,11 +216,17 @@ class VecchiaGP:
         """new hyperparameters; the neighbour lists stay as they are (refresh_neighbors rebuilds them)"""
         self._hps = self._check_hps(hps)
 
-    def refresh_neighbors(self, hyperparameters=None):
+    def refresh_neighbors(self, hyperparameters=None, reorder=False):
         """rebuild the neighbour lists: under the length scales of `hyperparameters` (default: the current ones) where
-        args["neighbor_scales"] is "lengthscales", else under the same scales as before"""
+        args["neighbor_scales"] is "lengthscales", else under the same scales as before.  reorder=True (ordering="maxmin" only): the
+        ordering is made again under those scales first and the data are uploaded in it"""
+        if reorder and self._ordering_rule[0] != "maxmin":
+            raise ValueError(f"refresh_neighbors(reorder=True) recomputes a maxmin ordering: this object's ordering rule is "
+                             f"{self._ordering_rule[0]!r}, which does not depend on the scales")
         hps = self._hps if hyperparameters is None else self._check_hps(hyperparameters)
         self._scales = self._scales_at(hps, self.index_set_dim)
+        if reorder:
+            self._set_data(self.x_data, self.y_data, self.noise_variances, *self._maxmin(self.x_data))
         self._search_all()
 
     def neighbors(self):
@@ -405,12 +452,13 @@ class VecchiaGP:
     # ---- data ------------------------------------------------------------------------------------------------------------------
     def update_gp_data(self, x_new, y_new, noise_variances_new=None, append=True):
         """append=True: the new points go to the END of the ordering and only their neighbours are searched (the old rows' lists stay:
-        the state equals a fresh object with the same ordering and the new rows last); the prior mean is recomputed.  append=False
-        replaces everything (the ordering is made again by the constructor's rule; a permutation array there: the caller's order)."""
+        the state equals a fresh object with the same ordering and the new rows last; their ordering_distances are nan); the prior mean
+        is recomputed.  append=False replaces everything (the ordering is made again by the constructor's rule, "maxmin" runs on the
+        new data; a permutation array there: the caller's order)."""
         assert isinstance(x_new, np.ndarray) and np.ndim(x_new) == 2 and isinstance(y_new, np.ndarray) and np.ndim(y_new) == 1
         assert x_new.shape[1] == self.index_set_dim and len(x_new) == len(y_new), "x_new / y_new do not fit the data"
         if not append:
-            self._set_data(x_new, y_new, noise_variances_new, self._make_ordering(self._ordering_rule[0], len(x_new), self._ordering_rule[1]))
+            self._set_data(x_new, y_new, noise_variances_new, *self._ordering_of(self._ordering_rule[0], x_new))
             self._search_all()
             return
         if (self.noise_variances is None) != (noise_variances_new is None):
@@ -421,7 +469,8 @@ class VecchiaGP:
         old_idx = self._idx
         x_all, y_all = np.vstack([self.x_data, x_new]), np.concatenate([self.y_data, y_new])
         v_all = None if noise_variances_new is None else np.concatenate([self.noise_variances, noise_variances_new])
-        self._set_data(x_all, y_all, v_all, np.concatenate([self.ordering, n_old + np.arange(k, dtype=np.int64)]))
+        dist = None if self.ordering_distances is None else np.concatenate([self.ordering_distances, np.full(k, np.nan)])
+        self._set_data(x_all, y_all, v_all, np.concatenate([self.ordering, n_old + np.arange(k, dtype=np.int64)]), dist)
         self._idx = self._H.torch.cat([old_idx, self._search(self._x_dev[n_old:], n_old)], dim=0)
 
     # ---- training ----------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@
  * iteration count and no standard error; with m >= n - 1 it is the exact likelihood.
  *
  * The conventions of fvgp_hip.h hold: fp64, row-major, device pointers unless the parameter says "host", 0 / -k / >= 1000 as return
- * value.  Every call here synchronises the stream except fvgp_hip_nn_search.  No call allocates device memory.
+ * value.  Every call here synchronises the stream except fvgp_hip_nn_search and fvgp_hip_nn_maxmin_order.  No call allocates device memory.
  */
 #ifndef FVGP_HIP_NN_H
 #define FVGP_HIP_NN_H
@@ -138,6 +138,31 @@ int fvgp_hip_nn_loglik_fisher(fvgp_handle *h, int kernel_id, const double *x, in
 /* bytes of the caller-owned `work` of fvgp_hip_nn_loglik_fisher: the gradient call's, then the packed sums per b and one sum per (b, slice
  * of 256 rows, packed entry).  -1 for n < 1, B < 1 or ntheta < 1. */
 int64_t fvgp_hip_nn_fisher_workspace_bytes(int64_t n, int B, int ntheta);
+
+/* bytes of the caller-owned `work` of the maxmin ordering below: the n distances to the nearest pick and two rows of per-workgroup
+ * partials.  -1 for n < 1. */
+int64_t fvgp_hip_nn_maxmin_workspace_bytes(int64_t n);
+
+/* The exact maxmin (farthest-point, coarse-to-fine) ordering of the rows of x (n, d) (csrc/nn_order.hip).  With the search's
+ * distance  dist(i, j) = sum_k ((x[i][k] - x[j][k]) * (1 / scales[k]))^2  (scales_host NULL: 1; fused multiply-adds in ascending k):
+ *     perm_out[0] = first,      perm_out[t] = the i not picked yet with the largest  mindist_t(i) = min_{s < t} dist(i, perm_out[s]),
+ * ties to the lowest index, for t < q.  dist_out (q) or NULL: dist_out[t] = mindist_t(perm_out[t]), the SQUARED scaled distance at which
+ * the point entered; dist_out[0] = +inf, dist_out[1 ..] never increases.  Duplicated points have mindist 0 and come last, in index order:
+ * with q = n every point is ordered.  perm_out (q) int64, device.
+ * One launch per step, q launches in stream order: every workgroup reduces the previous step's per-workgroup partials to the same pick,
+ * lowers the mindist of its own strip of points against it and leaves its best point as its partial.  No atomics, no host
+ * synchronisation: asynchronous.  O(q n d) flops.
+ * BIT CONTRACT: perm_out and dist_out are functions of (x, scales, first, q) alone -- the same bits on every call, whatever the grid --
+ * and the first q' entries of a call with q are those of the call with q' < q.  mindist_t(i) depends on x[i] and the t earlier picks
+ * alone: rows appended to x change nothing before the first step at which one of them is picked.
+ * Coordinates that are not finite are the caller's error: a distance that comes out as no number counts as 0 (such a point is ordered
+ * with the duplicates), an infinite one as the largest.  Every entry of perm_out is one of 0 .. n - 1 and none repeats, whatever x holds.
+ * work: device, 8-byte aligned, the bytes the sizing entry above gives for n.
+ * Errors: -1 h, -2 x, -3 n < 1 or past 2^31 - 1, -4 d outside 1 .. FVGP_MAX_DIM, -5 a scale that is not positive and finite, -6 first
+ * outside 0 .. n - 1, -7 q outside 1 .. n, -8 perm_out, -10 work NULL or misaligned, -11 work_bytes too small. */
+int fvgp_hip_nn_maxmin_order(fvgp_handle *h, const double *x, int64_t n, int d, const double *scales_host_or_null,
+                             int64_t first, int64_t q, int64_t *perm_out, double *dist_out_or_null,
+                             double *work, int64_t work_bytes);
 
 #ifdef __cplusplus
 }
