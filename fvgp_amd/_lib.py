@@ -198,11 +198,17 @@ _ABI_NN = {
     "fvgp_hip_nn_loglik_fisher": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, P_d,
                                         P_d, P_d, P_l]),
     "fvgp_hip_nn_fisher_workspace_bytes": (c_l, [c_l, c_i, c_i]),
+    "fvgp_hip_nn_grid_bytes": (c_l, [c_l, c_i]),
+    "fvgp_hip_nn_grid_workspace_bytes": (c_l, [c_l, c_i]),
+    "fvgp_hip_nn_grid_build": (c_i, [c_p, c_p, c_l, c_i, P_d, c_p, c_l, c_p, c_l, P_d]),
+    "fvgp_hip_nn_grid_search": (c_i, [c_p, c_p, c_l, c_p, c_l, c_i, c_i, c_l, P_d, c_p, c_p, c_l]),
     "fvgp_hip_nn_maxmin_workspace_bytes": (c_l, [c_l]),
     "fvgp_hip_nn_maxmin_order": (c_i, [c_p, c_p, c_l, c_i, P_d, c_l, c_l, c_p, c_p, c_p, c_l]),
 }
 SYMBOLS_NN = list(_ABI_NN)
 NN_MAX_NEIGHBORS = 64     # FVGP_NN_MAX_NEIGHBORS
+NN_GRID_MAX_DIM = 3       # FVGP_NN_GRID_MAX_DIM: most dimensions of the cell-grid search
+NN_GRID_INFO = 20         # FVGP_NN_GRID_INFO: doubles of the host record a grid build leaves for the grid search
 NN_SEARCH, NN_CONDITIONALS, NN_LOGLIK = 0, 1, 2   # FVGP_NN_*: the call fvgp_hip_nn_workspace_bytes sizes
 NN_VALUE, NN_GRAD, NN_FISHER = 0, 1, 2            # how far a likelihood call goes: fvgp_hip_nn_loglik, _loglik_grad, _loglik_fisher
 
@@ -378,6 +384,33 @@ def nn_fisher_workspace_bytes(n, B=1, ntheta=2):
 def nn_maxmin_workspace_bytes(n):
     """bytes of the caller-owned workspace of Handle.nn_maxmin_order for n points (fvgp_hip_nn_maxmin_workspace_bytes); -1 for n < 1"""
     return _workspace_bytes("fvgp_hip_nn_maxmin_workspace_bytes", n)
+
+
+def nn_grid_bytes(nr, d):
+    """bytes of the device buffer that holds the cell grid of nr reference rows in d dimensions (fvgp_hip_nn_grid_bytes); -1 for
+    nr < 1 or d outside 1 .. NN_GRID_MAX_DIM"""
+    return _workspace_bytes("fvgp_hip_nn_grid_bytes", nr, d)
+
+
+def nn_grid_workspace_bytes(nr, d):
+    """bytes of the caller-owned workspace of Handle.nn_grid_build (fvgp_hip_nn_grid_workspace_bytes); -1 as nn_grid_bytes"""
+    return _workspace_bytes("fvgp_hip_nn_grid_workspace_bytes", nr, d)
+
+
+class NNGrid:
+    """What Handle.nn_grid_build leaves for Handle.nn_grid_search: `buffer` (the device buffer with the bucketed rows), `info` (the host
+    record, NN_GRID_INFO doubles) and the (nr, d) it was built over.  cells: the cells per dimension, edge: their scaled edge."""
+
+    def __init__(self, buffer, info, nr, d):
+        self.buffer, self.info, self.nr, self.d = buffer, info, int(nr), int(d)
+
+    @property
+    def cells(self):
+        return tuple(int(c) for c in self.info[14:14 + self.d])
+
+    @property
+    def edge(self):
+        return float(self.info[12])
 
 
 def loglik_hess_workspace_bytes(n, d):
@@ -1006,6 +1039,39 @@ class Handle(DistCalls):
             sp = sc.ctypes.data_as(P_d)
         self._call("fvgp_hip_nn_search", _ptr(xq), xq.shape[0], _ptr(xr), xr.shape[0], xq.shape[1], sp, int(m), int(c0),
                    _ptr(idx_out), idx_out.stride(0))
+
+    def nn_grid_build(self, xr, scales=None):
+        """fvgp_hip_nn_grid_build: the cell grid over the rows of the device tensor xr (nr, d), d <= NN_GRID_MAX_DIM, under `scales`
+        (None or d positive numbers, host) -> NNGrid.  Synchronises once (the bounding box is read back); the buffer is allocated
+        here, the build's workspace is released with the call."""
+        nr, d = xr.shape
+        if not xr.is_contiguous() or xr.dtype != self.torch.float64:
+            raise ValueError(f"nn_grid_build: xr must be a contiguous float64 (nr, d) tensor, got {tuple(xr.shape)} {xr.dtype}")
+        if not 1 <= d <= NN_GRID_MAX_DIM:
+            raise ValueError(f"nn_grid_build: the cell grid takes 1 .. {NN_GRID_MAX_DIM} dimensions, got {d}; nn_search has no such limit")
+        sp = None
+        if scales is not None:
+            sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
+            if sc.shape != (d,):
+                raise ValueError(f"nn_grid_build: scales must be {d} numbers")
+            sp = sc.ctypes.data_as(P_d)
+        buf = self.empty(max(1, nn_grid_bytes(nr, d)) // 8)
+        work = self.empty(max(1, nn_grid_workspace_bytes(nr, d)) // 8)
+        info = np.zeros(NN_GRID_INFO)
+        self._call("fvgp_hip_nn_grid_build", _ptr(xr), nr, d, sp, _ptr(buf), buf.numel() * 8, _ptr(work), work.numel() * 8,
+                   info.ctypes.data_as(P_d))
+        self.sync()                                # (the workspace goes back to the allocator with this frame)
+        return NNGrid(buf, info, nr, d)
+
+    def nn_grid_search(self, xq, xr, m, idx_out, grid, c0=-1):
+        """fvgp_hip_nn_grid_search: idx_out as nn_search leaves it for (xq, xr, m, c0) under the scales `grid` (the NNGrid of
+        nn_grid_build over this xr) was built with, element for element.  Asynchronous."""
+        if idx_out.dim() != 2 or idx_out.stride(1) != 1 or idx_out.dtype != self.torch.int32 or idx_out.shape[0] < xq.shape[0]:
+            raise ValueError(f"nn_grid_search: idx_out must be an int32 (nq, >= m) tensor with unit column stride, got {tuple(idx_out.shape)}")
+        if xq.shape[1] != xr.shape[1]:
+            raise ValueError(f"nn_grid_search: xq has {xq.shape[1]} columns, xr {xr.shape[1]}")
+        self._call("fvgp_hip_nn_grid_search", _ptr(xq), xq.shape[0], _ptr(xr), xr.shape[0], xr.shape[1], int(m), int(c0),
+                   grid.info.ctypes.data_as(P_d), _ptr(grid.buffer), _ptr(idx_out), idx_out.stride(0))
 
     def nn_maxmin_order(self, x, first, q=None, scales=None, want_distances=True):
         """fvgp_hip_nn_maxmin_order: the exact maxmin ordering of the rows of the device tensor x (n, d) from the point `first`, its

@@ -29,8 +29,13 @@ The exact gradient of this likelihood comes from the same device call as its val
 the m x m factor that is already there, and one more sweep over each block's kernel entries with their derivatives):
 neg_log_likelihood_and_gradient, its _batch forms, conditional_scores (the per-point terms that sum to it) and train_gradient ("local":
 scipy's bounded optimisers, "adam": projected Adam, multi-start with args["adam_starts"]) are always there.  The fvgp.GP names
-neg_log_likelihood_gradient and train(method="local" | "adam") take this route with args={"likelihood_gradient": True}.  A tree search
-and joint covariances are not built.
+neg_log_likelihood_gradient and train(method="local" | "adam") take this route with args={"likelihood_gradient": True}.  Joint
+covariances are not built.
+
+The neighbour search itself has two routes that return the same lists element for element (args["neighbor_search"]): the brute search
+(fvgp_hip_nn_search, O(N^2 d)) and, at input dimension <= 3, an exact search through a uniform cell grid over the ordered data
+(fvgp_hip_nn_grid_build / _search, DESIGN 28, near-linear in N for data spread evenly).  The grid is built with the lists and kept for
+prediction and appends; it is made again whenever the data, the ordering or the scales change.
 
 The Fisher information of this likelihood -- the expected Hessian of neg_log_likelihood under the exact GP, positive semidefinite, in
 closed form from the same factors (fvgp_hip_nn_loglik_fisher) -- comes from one more device call of about the gradient's cost
@@ -51,6 +56,11 @@ from .gp_lin_alg import NonPositiveDefiniteError
 
 _DENSE = "the dense fvgp_amd.GP has it"
 _LOG_2PI = float(np.log(2.0 * np.pi))
+# args["neighbor_search"]: "auto" takes the cell grid (the same lists) at input dimension <= 3 from this many data points on --
+# the smallest size measured (profiles/r21_vecchia_grid.txt: 10^4 .. 10^6) from which on grid build + search beat the brute search on
+# every measured configuration; below it nothing was measured and the brute search stays
+NEIGHBOR_SEARCH_DEFAULT = "auto"
+NEIGHBOR_SEARCH_AUTO_POINTS = 10000
 _Evaluation = collections.namedtuple("_Evaluation", "out grad fisher info mu var score rows")      # what VecchiaGP._evaluate returns
 
 
@@ -75,7 +85,10 @@ class VecchiaGP:
     "batch_population" (True: train(method="global") scores a generation in one device call); "likelihood_gradient" (True: the fvgp.GP
     names neg_log_likelihood_gradient and train(method="local" | "adam" | "fisher") run the exact gradient); "adam_starts" (S >= 2:
     train_gradient(method="adam") runs S trajectories in lockstep on the batched gradient); "grad_batch_bytes" (default 1 GiB: the most
-    device memory one batched gradient or Fisher call may take for its per-row outputs)."""
+    device memory one batched gradient or Fisher call may take for its per-row outputs); "neighbor_search" = "auto" (default: the cell
+    grid where the input dimension is <= 3 and there are at least NEIGHBOR_SEARCH_AUTO_POINTS = 10 000 data points, else the brute
+    search), "grid" (the cell grid; ValueError at input dimension > 3) or "brute" -- the same neighbour lists, likelihood bits and
+    predictions on either route."""
 
     def __init__(self, x_data, y_data, hyperparameters, noise_variances=None, kernel_function="matern32_ard", n_neighbors=32,
                  ordering="random", seed=0, args=None):
@@ -192,17 +205,41 @@ class VecchiaGP:
         self.ordering = perm
         self.ordering_distances = distances
         self._x_dev = H.to_device(self.x_data[perm])
+        self._grid = None                          # (of the rows that were: _build_grid makes the new one)
         self._V_dev = H.to_device(self._V[perm])
         self._r_dev = H.to_device((self.y_data - self._m)[perm])
 
+    def _search_route(self):
+        """"brute" or "grid": args["neighbor_search"] resolved for the data as they are"""
+        mode = self.args.get("neighbor_search", NEIGHBOR_SEARCH_DEFAULT)
+        if mode not in ("brute", "grid", "auto"):
+            raise ValueError(f"args['neighbor_search'] must be 'brute', 'grid' or 'auto', got {mode!r}")
+        fits = self.index_set_dim <= _lib.NN_GRID_MAX_DIM
+        if mode == "grid" and not fits:
+            raise ValueError(f"args['neighbor_search'] = 'grid' takes input dimension <= {_lib.NN_GRID_MAX_DIM}, got "
+                             f"{self.index_set_dim}: use 'brute', or 'auto', which takes the brute search there")
+        if mode == "auto":
+            return "grid" if fits and self.point_number >= NEIGHBOR_SEARCH_AUTO_POINTS else "brute"
+        return mode
+
+    def _build_grid(self):
+        """the cell grid over the ordered data under the object's scales (None on the brute route): made again whenever the data, the
+        ordering or the scales change, kept for prediction and appends"""
+        self._grid = self._H.nn_grid_build(self._x_dev, self._scales) if self._search_route() == "grid" else None
+
     def _search(self, xq_dev, c0):
-        """int32 (nq, m) device tensor: the neighbours of the rows of xq_dev among the ordered data under the object's scales"""
+        """int32 (nq, m) device tensor: the neighbours of the rows of xq_dev among the ordered data under the object's scales, by the
+        grid where there is one (the same lists element for element)"""
         H = self._H
         idx = H.torch.empty((xq_dev.shape[0], self.n_neighbors), dtype=H.torch.int32, device=xq_dev.device)
-        H.nn_search(xq_dev, self._x_dev, self.n_neighbors, idx, scales=self._scales, c0=c0)
+        if self._grid is not None:
+            H.nn_grid_search(xq_dev, self._x_dev, self.n_neighbors, idx, self._grid, c0=c0)
+        else:
+            H.nn_search(xq_dev, self._x_dev, self.n_neighbors, idx, scales=self._scales, c0=c0)
         return idx
 
     def _search_all(self):
+        self._build_grid()
         self._idx = self._search(self._x_dev, 0)
 
     @property
@@ -471,6 +508,7 @@ class VecchiaGP:
         v_all = None if noise_variances_new is None else np.concatenate([self.noise_variances, noise_variances_new])
         dist = None if self.ordering_distances is None else np.concatenate([self.ordering_distances, np.full(k, np.nan)])
         self._set_data(x_all, y_all, v_all, np.concatenate([self.ordering, n_old + np.arange(k, dtype=np.int64)]), dist)
+        self._build_grid()
         self._idx = self._H.torch.cat([old_idx, self._search(self._x_dev[n_old:], n_old)], dim=0)
 
     # ---- training ----------------------------------------------------------------------------------------------------------------

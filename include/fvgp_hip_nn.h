@@ -6,7 +6,8 @@
  * iteration count and no standard error; with m >= n - 1 it is the exact likelihood.
  *
  * The conventions of fvgp_hip.h hold: fp64, row-major, device pointers unless the parameter says "host", 0 / -k / >= 1000 as return
- * value.  Every call here synchronises the stream except fvgp_hip_nn_search and fvgp_hip_nn_maxmin_order.  No call allocates device memory.
+ * value.  Every call here synchronises the stream except fvgp_hip_nn_search, fvgp_hip_nn_maxmin_order and fvgp_hip_nn_grid_search
+ * (fvgp_hip_nn_grid_build synchronises once, in its middle).  No call allocates device memory.
  */
 #ifndef FVGP_HIP_NN_H
 #define FVGP_HIP_NN_H
@@ -138,6 +139,59 @@ int fvgp_hip_nn_loglik_fisher(fvgp_handle *h, int kernel_id, const double *x, in
 /* bytes of the caller-owned `work` of fvgp_hip_nn_loglik_fisher: the gradient call's, then the packed sums per b and one sum per (b, slice
  * of 256 rows, packed entry).  -1 for n < 1, B < 1 or ntheta < 1. */
 int64_t fvgp_hip_nn_fisher_workspace_bytes(int64_t n, int B, int ntheta);
+
+/* ---- the exact cell-grid search (csrc/nn_grid.hip): the lists of fvgp_hip_nn_search in near-linear time, d <= 3 ---- */
+#define FVGP_NN_GRID_MAX_DIM 3     /* most dimensions of the cell grid */
+#define FVGP_NN_GRID_INFO 20       /* doubles of the host record fvgp_hip_nn_grid_build leaves for fvgp_hip_nn_grid_search */
+
+/* bytes of the caller-owned device buffer that holds the grid of nr reference rows in d dimensions: the rows' coordinates bucketed by
+ * cell (nr d doubles), the cells' first positions (at most min(nr, 2^24) + 1 ints) and the bucketed row indices (nr ints).  A function
+ * of (nr, d) alone, not of the data.  -1 for nr < 1 or past 2^31 - 1, d outside 1 .. FVGP_NN_GRID_MAX_DIM. */
+int64_t fvgp_hip_nn_grid_bytes(int64_t nr, int d);
+
+/* bytes of the caller-owned `work` of fvgp_hip_nn_grid_build: the box partials, every row's cell and rank, the block sums of the scan.
+ * -1 as above. */
+int64_t fvgp_hip_nn_grid_workspace_bytes(int64_t nr, int d);
+
+/* Build the grid over the reference rows xr (nr, d), d <= 3, in the search's scaled coordinates (scales_host_or_null as in
+ * fvgp_hip_nn_search): cubic cells of one scaled edge h over the rows' bounding box, about two rows per cell on average and at most
+ * min(nr, 2^24) cells; a dimension of zero extent, or thinner than a cell, has one cell.  Row x lies in cell
+ * min(floor(((x[k] - lo[k]) * (1 / scales[k])) * (1 / h)), cells[k] - 1) of dimension k.  grid_dev receives the rows bucketed by cell;
+ * info_host (FVGP_NN_GRID_INFO doubles, host) what was chosen: { a magic word, nr, d, scales[3], 1 / scales[3], lo[3], h, 1 / h,
+ * cells[3], their product, the causal candidate count below which the search takes the brute entry, 0 }.
+ * Steps: the box by a reduction, read back (the call SYNCHRONISES the stream once, there); every row's cell and its rank inside the cell
+ * by an integer atomic on the cell's counter; an exclusive scan of the counts; the scatter.  Cost O(nr d + cells), independent of how
+ * many rows share a cell.  Returns with the last launches still in the stream: a search on the same handle may follow at once.
+ * BIT CONTRACT: info_host is a function of (xr, scales) alone.  The order of the rows inside a cell's bucket is not (it follows the
+ * atomics), and no result of fvgp_hip_nn_grid_search depends on it.
+ * grid_dev: device, 8-byte aligned, fvgp_hip_nn_grid_bytes(nr, d) bytes; work: device, 8-byte aligned,
+ * fvgp_hip_nn_grid_workspace_bytes(nr, d) bytes, free again when the stream has passed the call.
+ * Errors: -1 h, -2 xr, -3 nr < 1 or past 2^31 - 1, -4 d outside 1 .. FVGP_NN_GRID_MAX_DIM (fvgp_hip_nn_search remains the route there),
+ * -5 a scale that is not positive and finite, -6 grid_dev NULL or misaligned, -7 grid_bytes too small, -8 work NULL or misaligned,
+ * -9 work_bytes too small, -10 info_host, -11 a coordinate of xr, or the scaled extent of the box, is not finite (nothing was built). */
+int fvgp_hip_nn_grid_build(fvgp_handle *h, const double *xr, int64_t nr, int d, const double *scales_host_or_null, void *grid_dev,
+                           int64_t grid_bytes, void *work, int64_t work_bytes, double *info_host);
+
+/* fvgp_hip_nn_search through the grid: idx_out (nq, ld >= m) int32 receives, ELEMENT FOR ELEMENT, what fvgp_hip_nn_search writes for the
+ * same (xq, xr, m, c0) under the scales the grid was built with -- min(m, candidates) entries sorted by (distance, index) ascending, ties
+ * to the lower index, then -1 up to column m; columns m .. ld are not written; c0 as there.  xr, nr, d: the rows the grid was built over,
+ * unchanged since; info_host and grid_dev: what that build left.
+ * A lane per query.  Every candidate's distance is computed by the brute kernel's operations; cells are visited in growing shells around
+ * the query's cell (queries outside the box start from the nearest border cell) and the running list is ordered by the pair
+ * (distance, index) explicitly.  The walk of a query ends when every cell has been visited, or when the list is full and its worst
+ * distance is strictly below (1 - 2^-20) times the square of a lower bound, itself lowered by 2^-40 (|cell coordinate| + cells + 2)
+ * cells, on the computed distance to any row in a cell not visited yet.  In a causal call the queries with fewer than 1024 (nr < 65536) or 4096
+ * candidates are searched by fvgp_hip_nn_search itself.  Every loop is bounded by the cells per dimension or a cell's occupancy.
+ * BIT CONTRACT: that of fvgp_hip_nn_search -- a row is a function of its query, the reference rows, the scales, m and its candidate count
+ * alone: not of the other queries, the launch geometry, the cell sizes or the order of the rows inside a bucket.
+ * Query coordinates that are not finite are the caller's error: such a row receives legal candidates, not necessarily the brute entry's.
+ * Cost: for rows spread evenly, O(m) distances per query once the candidates outnumber m by far; a causal query i visits about N m / i
+ * rows' worth of cells; clustered rows cost what their fullest visited cells hold.  Asynchronous.
+ * Errors: -1 h, -2 xq, -3 nq < 1, -4 xr, -5 nr < 1 or past 2^31 - 1, -6 d outside 1 .. FVGP_NN_GRID_MAX_DIM, -8 m outside
+ * 1 .. FVGP_NN_MAX_NEIGHBORS, -9 info_host NULL or not the record of a grid over (nr, d), -10 idx_out, -11 ld < m, -12 grid_dev NULL or
+ * misaligned. */
+int fvgp_hip_nn_grid_search(fvgp_handle *h, const double *xq, int64_t nq, const double *xr, int64_t nr, int d, int m, int64_t c0,
+                            const double *info_host, const void *grid_dev, int *idx_out, int64_t ld);
 
 /* bytes of the caller-owned `work` of the maxmin ordering below: the n distances to the nearest pick and two rows of per-workgroup
  * partials.  -1 for n < 1. */
