@@ -460,6 +460,16 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _scales_ptr(who, scales, d):
+    """host pointer to the d scales of the nearest-neighbour binding `who`, or None (the pointer keeps its array alive)"""
+    if scales is None:
+        return None
+    sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
+    if sc.shape != (d,):
+        raise ValueError(f"{who}: scales must be {d} numbers")
+    return sc.ctypes.data_as(P_d)
+
+
 def _batch_operands(who, x, thetas, vdiag, ymean):
     """the operands the batched entries share, as Handle method `who` passes them on: thetas as a contiguous (B, ntheta) array, vdiag as
     (1 or B, n) and ymean as (1 or B, n, ncol) with their per-problem strides in doubles (0 = one shared by every problem)"""
@@ -1025,18 +1035,16 @@ class Handle(DistCalls):
                    _ptr(work), work.numel() * 8)
 
     # -- nearest-neighbour (Vecchia) path (include/fvgp_hip_nn.h) ---------------------------------------------------------------
+    def _nn_check_idx_out(self, who, idx_out, nq):
+        if idx_out.dim() != 2 or idx_out.stride(1) != 1 or idx_out.dtype != self.torch.int32 or idx_out.shape[0] < nq:
+            raise ValueError(f"{who}: idx_out must be an int32 (nq, >= m) tensor with unit column stride, got {tuple(idx_out.shape)}")
+
     def nn_search(self, xq, xr, m, idx_out, scales=None, c0=-1):
         """fvgp_hip_nn_search: idx_out (nq, >= m) int32 device tensor <- per row of xq the m nearest candidates among the rows of xr,
         sorted by (distance, index), -1 past the candidate count; scales None or d positive numbers (host); c0 < 0: every row of xr is
         a candidate, c0 >= 0: rows j < min(nr, c0 + i) for query i.  Asynchronous."""
-        if idx_out.dim() != 2 or idx_out.stride(1) != 1 or idx_out.dtype != self.torch.int32 or idx_out.shape[0] < xq.shape[0]:
-            raise ValueError(f"nn_search: idx_out must be an int32 (nq, >= m) tensor with unit column stride, got {tuple(idx_out.shape)}")
-        sp = None
-        if scales is not None:
-            sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
-            if sc.shape != (xq.shape[1],):
-                raise ValueError(f"nn_search: scales must be {xq.shape[1]} numbers")
-            sp = sc.ctypes.data_as(P_d)
+        self._nn_check_idx_out("nn_search", idx_out, xq.shape[0])
+        sp = _scales_ptr("nn_search", scales, xq.shape[1])
         self._call("fvgp_hip_nn_search", _ptr(xq), xq.shape[0], _ptr(xr), xr.shape[0], xq.shape[1], sp, int(m), int(c0),
                    _ptr(idx_out), idx_out.stride(0))
 
@@ -1049,12 +1057,7 @@ class Handle(DistCalls):
             raise ValueError(f"nn_grid_build: xr must be a contiguous float64 (nr, d) tensor, got {tuple(xr.shape)} {xr.dtype}")
         if not 1 <= d <= NN_GRID_MAX_DIM:
             raise ValueError(f"nn_grid_build: the cell grid takes 1 .. {NN_GRID_MAX_DIM} dimensions, got {d}; nn_search has no such limit")
-        sp = None
-        if scales is not None:
-            sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
-            if sc.shape != (d,):
-                raise ValueError(f"nn_grid_build: scales must be {d} numbers")
-            sp = sc.ctypes.data_as(P_d)
+        sp = _scales_ptr("nn_grid_build", scales, d)
         buf = self.empty(max(1, nn_grid_bytes(nr, d)) // 8)
         work = self.empty(max(1, nn_grid_workspace_bytes(nr, d)) // 8)
         info = np.zeros(NN_GRID_INFO)
@@ -1066,8 +1069,7 @@ class Handle(DistCalls):
     def nn_grid_search(self, xq, xr, m, idx_out, grid, c0=-1):
         """fvgp_hip_nn_grid_search: idx_out as nn_search leaves it for (xq, xr, m, c0) under the scales `grid` (the NNGrid of
         nn_grid_build over this xr) was built with, element for element.  Asynchronous."""
-        if idx_out.dim() != 2 or idx_out.stride(1) != 1 or idx_out.dtype != self.torch.int32 or idx_out.shape[0] < xq.shape[0]:
-            raise ValueError(f"nn_grid_search: idx_out must be an int32 (nq, >= m) tensor with unit column stride, got {tuple(idx_out.shape)}")
+        self._nn_check_idx_out("nn_grid_search", idx_out, xq.shape[0])
         if xq.shape[1] != xr.shape[1]:
             raise ValueError(f"nn_grid_search: xq has {xq.shape[1]} columns, xr {xr.shape[1]}")
         self._call("fvgp_hip_nn_grid_search", _ptr(xq), xq.shape[0], _ptr(xr), xr.shape[0], xr.shape[1], int(m), int(c0),
@@ -1082,12 +1084,7 @@ class Handle(DistCalls):
         q = n if q is None else int(q)
         if not x.is_contiguous() or x.dtype != self.torch.float64:
             raise ValueError(f"nn_maxmin_order: x must be a contiguous float64 (n, d) tensor, got {tuple(x.shape)} {x.dtype}")
-        sp = None
-        if scales is not None:
-            sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
-            if sc.shape != (d,):
-                raise ValueError(f"nn_maxmin_order: scales must be {d} numbers")
-            sp = sc.ctypes.data_as(P_d)
+        sp = _scales_ptr("nn_maxmin_order", scales, d)
         perm = self.torch.empty((max(q, 1),), dtype=self.torch.int64, device=x.device)
         dist = self.empty(max(q, 1)) if want_distances else None
         work = self.empty(max(1, nn_maxmin_workspace_bytes(n)) // 8)

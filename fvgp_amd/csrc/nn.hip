@@ -1,8 +1,5 @@
-// The nearest-neighbour (Vecchia) path (include/fvgp_hip_nn.h): n independent m x m problems, m <= 64, instead of one n x n.
-// fvgp_hip_nn_search        brute-force m nearest candidates of every query: a wavefront per 64 queries, a lane per query, the reference
-//     rows staged through LDS in slices (every lane reads the same row: broadcast reads), each lane's running top-m kept sorted in LDS
-//     (slot-major, so lanes touching the same slot never meet on a bank) by insertion from the end.  Rows are walked in ascending index
-//     and an entry moves only for a strictly smaller distance: ties stay with the lower index.
+// The m x m linear algebra of the nearest-neighbour (Vecchia) path (include/fvgp_hip_nn.h): n independent m x m problems,
+// m <= 64, instead of one n x n.  The neighbour lists come from nn_search.hip or nn_grid.hip; only dispatch_pad is shared with them.
 // fvgp_hip_nn_conditionals  one wavefront per (row, b), NN_WAVES of them per workgroup and nothing shared between them: lane l owns
 //     neighbour l.  Assembly: for column j the lanes read x_j from lane j's registers (v_readlane, j is uniform) and lanes l >= j store
 //     K(x_l, x_j) into the packed lower triangle held COLUMN-major in LDS (column j: rows j .. M - 1, consecutive lanes on consecutive
@@ -18,6 +15,7 @@
 //     LDS, the slices to 0 in ascending order by one thread per (b, column).  No atomics anywhere.  The triangle is mirrored on the host.
 #include "radial.h"
 #include "kernel_family.h"
+#include "nn_geometry.h"
 #include "../../include/fvgp_hip_nn.h"
 #include <math.h>
 #include <vector>
@@ -26,8 +24,6 @@ namespace {
 
 constexpr int NN_WAVES = 4;                       // conditionals: waves (problems) per workgroup
 constexpr int NN_TAB = 1 + FVGP_MAX_DIM;          // theta table row: sigma^2, then 1 / l per dimension
-constexpr int NN_SEARCH_ROWS = 128;               // reference rows per staged slice of the search
-constexpr int NN_SEARCH_QUERIES = 65536;          // queries per launch of the search
 constexpr int NN_SUM_ROWS = 256;                 // rows per slice of the likelihood's sums
 
 // LDS traffic between the lanes of ONE wave: the wave's DS operations execute in order, the fences keep the compiler from moving them
@@ -48,92 +44,6 @@ __device__ __forceinline__ double wave_tree_sum(double w) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
     return w;
-}
-
-// ------------------------------------------------------------------------------------------------------------------ search
-struct NsArgs {
-    const double *xq, *xr;
-    int *out;
-    long nq, nr, ld, c0;
-    int d, m;
-    double is[FVGP_MAX_DIM];                       // 1 / scale per dimension (1: unscaled)
-};
-
-template <int D, int M>      // D == 0: runtime dimension (<= FVGP_MAX_DIM); M: list capacity, m <= M
-__global__ __launch_bounds__(64) void nn_search_kernel(NsArgs a) {
-    constexpr int DD = D ? D : FVGP_MAX_DIM;
-    __shared__ double sx[NN_SEARCH_ROWS * DD];
-    __shared__ double sd[M * 64];                  // [slot][lane]
-    __shared__ int si[M * 64];
-    const int d = D ? D : a.d, m = a.m;
-    const int lane = threadIdx.x;
-    const long q0 = (long)blockIdx.x * 64, q = q0 + lane;
-    const long qi = q < a.nq ? q : a.nq - 1;
-    double u[DD], is[DD];
-#pragma unroll
-    for (int k = 0; k < DD; ++k) { u[k] = k < d ? a.xq[qi * d + k] : 0.0; is[k] = a.is[k]; }
-    // candidates of this lane [0, lim) and of the block [0, top)
-    long lim = a.nr, top = a.nr;
-    if (a.c0 >= 0) {
-        lim = a.c0 + q < a.nr ? a.c0 + q : a.nr;
-        const long ql = q0 + 63 < a.nq ? q0 + 63 : a.nq - 1;
-        top = a.c0 + ql < a.nr ? a.c0 + ql : a.nr;
-    }
-    if (q >= a.nq) lim = 0;
-    int cnt = 0;
-    double worst = INFINITY;                       // the list's last distance once it is full
-
-    for (long row0 = 0; row0 < top; row0 += NN_SEARCH_ROWS) {
-        __syncthreads();                           // the last slice has been read
-        const int rows = top - row0 < NN_SEARCH_ROWS ? (int)(top - row0) : NN_SEARCH_ROWS;
-        for (int e = lane; e < rows * d; e += 64) {
-            const int rr = e / d, kk = e - rr * d;
-            sx[rr * DD + kk] = a.xr[(row0 + rr) * d + kk];
-        }
-        __syncthreads();
-        for (int r = 0; r < rows; ++r) {
-            const double *xr = sx + r * DD;
-            double dist = 0.0;
-#pragma unroll
-            for (int k = 0; k < DD; ++k)
-                if (k < d) { const double e = (u[k] - xr[k]) * is[k]; dist = fma(e, e, dist); }
-            const long j = row0 + r;
-            if (j < lim && (cnt < m || dist < worst)) {
-                int p = cnt < m ? cnt : m - 1;     // the slot that opens: behind the list, or its last entry drops out
-                while (p > 0 && sd[(p - 1) * 64 + lane] > dist) {
-                    sd[p * 64 + lane] = sd[(p - 1) * 64 + lane];
-                    si[p * 64 + lane] = si[(p - 1) * 64 + lane];
-                    --p;
-                }
-                sd[p * 64 + lane] = dist;
-                si[p * 64 + lane] = (int)j;
-                if (cnt < m) ++cnt;
-                if (cnt == m) worst = sd[(m - 1) * 64 + lane];
-            }
-        }
-    }
-    if (q >= a.nq) return;
-    for (int p = 0; p < m; ++p) a.out[q * a.ld + p] = p < cnt ? si[p * 64 + lane] : -1;
-}
-
-// f(std::integral_constant<int, D>) with the dimensions that have an instantiation of their own (those of dispatch_kind_dim)
-template <class F>
-inline void dispatch_dim(int d, F &&f) {
-    switch (d) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        default: f(std::integral_constant<int, 0>{}); break;
-    }
-}
-
-// f(std::integral_constant<int, M>) for the padded size of m neighbours
-template <class F>
-inline void dispatch_pad(int m, F &&f) {
-    if (m <= 16) f(std::integral_constant<int, 16>{});
-    else if (m <= 32) f(std::integral_constant<int, 32>{});
-    else f(std::integral_constant<int, 64>{});
 }
 
 // the level of a likelihood call, and what nn_cond_kernel computes beside mu and var: nothing, every row's score, or the score and the
@@ -617,42 +527,6 @@ int64_t fvgp_hip_nn_grad_workspace_bytes(int64_t n, int B, int ntheta) {
 int64_t fvgp_hip_nn_fisher_workspace_bytes(int64_t n, int B, int ntheta) {
     if (n < 1 || B < 1 || ntheta < 1) return -1;
     return nn_layout(NN_FISHER, n, B, ntheta).end * (int64_t)sizeof(double);
-}
-
-int fvgp_hip_nn_search(fvgp_handle *h, const double *xq, int64_t nq, const double *xr, int64_t nr, int d, const double *scales_host,
-                       int m, int64_t c0, int *idx_out, int64_t ld) {
-    if (!h) return -1;
-    if (!xq) return -2;
-    if (nq < 1 || (nq + 63) / 64 > 0x7fffffffLL) return -3;
-    if (!xr) return -4;
-    if (nr < 1 || nr > 0x7fffffffLL) return -5;
-    if (d < 1 || d > FVGP_MAX_DIM) { fvgp_set_error("input dimension out of range"); return -6; }
-    NsArgs a;
-    for (int k = 0; k < FVGP_MAX_DIM; ++k) a.is[k] = 1.0;
-    if (scales_host)
-        for (int k = 0; k < d; ++k) {
-            if (!(scales_host[k] > 0.0) || !std::isfinite(scales_host[k])) { fvgp_set_error("nn_search: scales must be positive and finite"); return -7; }
-            a.is[k] = 1.0 / scales_host[k];
-        }
-    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error("nn_search: 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -8; }
-    if (!idx_out) return -10;
-    if (ld < m) return -11;
-    HIPCHK(hipSetDevice(h->device));
-    a.xr = xr; a.nr = nr; a.ld = ld; a.d = d; a.m = m;
-    // a launch per NN_SEARCH_QUERIES queries (a row's result does not depend on the cut): no single launch walks 10^6 x 10^6 pairs
-    for (int64_t q0 = 0; q0 < nq; q0 += NN_SEARCH_QUERIES) {
-        a.xq = xq + q0 * d; a.out = idx_out + q0 * ld;
-        a.nq = nq - q0 < NN_SEARCH_QUERIES ? nq - q0 : NN_SEARCH_QUERIES;
-        a.c0 = c0 < 0 ? -1 : c0 + q0;
-        const dim3 grid((unsigned)((a.nq + 63) / 64)), block(64);
-        dispatch_dim(d, [&](auto D) {
-            dispatch_pad(m, [&](auto M) {
-                hipLaunchKernelGGL((nn_search_kernel<decltype(D)::value, decltype(M)::value>), grid, block, 0, h->stream, a);
-            });
-        });
-        HIPCHK(hipGetLastError());
-    }
-    return 0;
 }
 
 int fvgp_hip_nn_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t nq, const double *xr, int64_t nr, int d,

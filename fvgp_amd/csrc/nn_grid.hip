@@ -6,20 +6,17 @@
 //     on the order, the ranks do: they only decide where inside its cell's bucket a row lands); an exclusive scan of the counts (three
 //     launches: blocks of NG_SCAN_BLOCK entries, their sums by one workgroup, the offsets added); the rows' indices and coordinates
 //     written to start[cell] + rank.  Linear in nr whatever the fullest cell holds.
-// fvgp_hip_nn_grid_search   a lane per query as in nn_search_kernel, the running top-m in LDS slot-major, but ordered by the pair
-//     (distance, index) explicitly, since rows no longer arrive in ascending index.  Cells are visited in growing Chebyshev shells around
+// fvgp_hip_nn_grid_search   a lane per query as in nn_search_kernel, its distance and its list (nn_geometry.h: nn_dist2, nn_top_insert),
+//     the list ordered by the pair (distance, index) explicitly, since rows no longer arrive in ascending index.  Cells are visited in growing Chebyshev shells around
 //     the query's cell; cells that follow each other along the last dimension are one contiguous range of the bucketed rows, so a run of
 //     them costs two reads of `start`.  The walk stops when the list is full and its worst distance lies STRICTLY below a lower bound on
 //     the computed distance of every row in a cell not visited yet (ng_stop_bound; the margin is derived in DESIGN 28).  Causal calls: the
 //     queries with fewer than ng_early(nr) candidates go to the brute entry (fvgp_hip_nn_search), whose cost there is small, while a grid
 //     walk would cover most of the grid to find them.  Every loop is bounded by the grid's shape or a cell's occupancy, never by a
 //     coordinate.
-#include "common.h"
+#include "nn_geometry.h"
 #include "../../include/fvgp_hip_nn.h"
-#include <math.h>
 #include <algorithm>
-#include <cmath>
-#include <type_traits>
 #include <vector>
 
 namespace {
@@ -252,31 +249,14 @@ __global__ __launch_bounds__(64) void nn_grid_search_kernel(NgArgs a) {
         ghi[s] = (double)(cq[s] + 1) - t;
         slack[s] = NG_SLACK * (fabs(t) + (double)(nc[s] + 2));
     }
-    int cnt = 0, worst_i = 0;
-    double worst = INFINITY;                       // the list's last (distance, index) once it is full
+    NnTop t;
 
-    // the bucketed rows p0 .. p1 - 1: every candidate's distance by the brute kernel's operations, the list kept sorted by (distance, index)
+    // the bucketed rows p0 .. p1 - 1 into the list, sorted by (distance, index)
     auto visit = [&](const int p0, const int p1) {
         for (int p = p0; p < p1; ++p) {
             const int j = a.bidx[p];
             if (j >= lim) continue;
-            const double *xr = a.bx + (long)p * D;
-            double dist = 0.0;
-#pragma unroll
-            for (int k = 0; k < D; ++k) { const double e = (u[k] - xr[k]) * is[k]; dist = fma(e, e, dist); }
-            if (cnt < m || dist < worst || (dist == worst && j < worst_i)) {
-                int s = cnt < m ? cnt : m - 1;     // the slot that opens: behind the list, or its last entry drops out
-                while (s > 0) {
-                    const double pd = sd[(s - 1) * 64 + lane];
-                    const int pi = si[(s - 1) * 64 + lane];
-                    if (!(pd > dist || (pd == dist && pi > j))) break;
-                    sd[s * 64 + lane] = pd; si[s * 64 + lane] = pi;
-                    --s;
-                }
-                sd[s * 64 + lane] = dist; si[s * 64 + lane] = j;
-                if (cnt < m) ++cnt;
-                if (cnt == m) { worst = sd[(m - 1) * 64 + lane]; worst_i = si[(m - 1) * 64 + lane]; }
-            }
+            nn_top_insert<true>(t, sd, si, lane, m, nn_dist2<D>(u, a.bx + (long)p * D, is, D), j);
         }
     };
     // the cells (c0, c1, l2 .. h2), contiguous in the buckets
@@ -305,7 +285,7 @@ __global__ __launch_bounds__(64) void nn_grid_search_kernel(NgArgs a) {
                 }
             }
         }
-        if (cnt < m) continue;
+        if (t.cnt < m) continue;
         // ng_stop_bound: a row in a cell outside shells 0 .. R lies, in some slot s, at least R + 1 cells above or below cq[s]; its
         // computed cell coordinate then differs from the query's by at least the gap to that face plus R
         double bound = INFINITY;
@@ -315,25 +295,9 @@ __global__ __launch_bounds__(64) void nn_grid_search_kernel(NgArgs a) {
             if (cq[s] - R - 1 >= 0) { const double g = fmax(glo[s] + (double)R - slack[s], 0.0) * a.g.h; bound = fmin(bound, g * g); }
         }
         bound *= NG_SHRINK;
-        if (bound >= NG_BOUND_FLOOR && worst < bound) break;
+        if (bound >= NG_BOUND_FLOOR && t.worst < bound) break;
     }
-    for (int p = 0; p < m; ++p) a.out[q * a.ld + p] = p < cnt ? si[p * 64 + lane] : -1;
-}
-
-template <class F>
-inline void dispatch_dim3(int d, F &&f) {
-    switch (d) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        default: f(std::integral_constant<int, 3>{}); break;
-    }
-}
-
-template <class F>
-inline void dispatch_pad(int m, F &&f) {
-    if (m <= 16) f(std::integral_constant<int, 16>{});
-    else if (m <= 32) f(std::integral_constant<int, 32>{});
-    else f(std::integral_constant<int, 64>{});
+    for (int p = 0; p < m; ++p) a.out[q * a.ld + p] = p < t.cnt ? si[p * 64 + lane] : -1;
 }
 
 inline bool pos_finite(double v) { return v > 0.0 && std::isfinite(v); }
@@ -419,12 +383,8 @@ int fvgp_hip_nn_grid_build(fvgp_handle *h, const double *xr, int64_t nr, int d, 
     if (!xr) return -2;
     if (nr < 1 || nr > 0x7fffffffLL) return -3;
     if (d < 1 || d > NG_MAX_DIM) { fvgp_set_error("nn_grid_build: the cell grid takes 1 .. 3 dimensions; fvgp_hip_nn_search has no such limit"); return -4; }
-    double scale[NG_MAX_DIM] = {1.0, 1.0, 1.0}, is[NG_MAX_DIM] = {1.0, 1.0, 1.0};
-    if (scales_host)
-        for (int k = 0; k < d; ++k) {
-            if (!(scales_host[k] > 0.0) || !std::isfinite(scales_host[k])) { fvgp_set_error("nn_grid_build: scales must be positive and finite"); return -5; }
-            scale[k] = scales_host[k]; is[k] = 1.0 / scales_host[k];
-        }
+    double scale[NG_MAX_DIM], is[NG_MAX_DIM];
+    if (!nn_scales("nn_grid_build", scales_host, d, NG_MAX_DIM, is, scale)) return -5;
     if (!grid_dev || ((uintptr_t)grid_dev & 7)) return -6;
     if (grid_bytes < fvgp_hip_nn_grid_bytes(nr, d)) { fvgp_set_error("nn_grid_build: grid buffer smaller than fvgp_hip_nn_grid_bytes(nr, d)"); return -7; }
     if (!work || ((uintptr_t)work & 7)) return -8;

@@ -4,14 +4,13 @@
 //     points, a few per thread, and keeps their distance to the nearest pick in the workspace (-1: picked).  The launch of step t
 //       1. reduces the partials {score, index} that step t - 1 left, one per workgroup, to the pick j -- every workgroup for itself, all
 //          to the same j, since the order of argmax.h (ties to the lowest index) makes the argmax associative; workgroup 0 records it;
-//       2. lowers its own points' distances by the one to x_j (the search's arithmetic) and leaves its best point as its partial in the
+//       2. lowers its own points' distances by the one to x_j (nn_geometry.h: nn_dist2) and leaves its best point as its partial in the
 //          OTHER of two partial arrays (t & 1): a workgroup may still read step t - 1's while another writes step t's.
 //     Step 0 takes j = first and sets the distances instead of lowering them.  No atomics, no communication inside a launch, every loop
 //     bounded by launch arguments.  O(q n d) flops; a step reads 8 (d + 1) bytes per point not picked yet and writes the distances that fell.
 #include "argmax.h"
+#include "nn_geometry.h"
 #include "../../include/fvgp_hip_nn.h"
-#include <math.h>
-#include <type_traits>
 
 namespace {
 
@@ -75,10 +74,7 @@ __global__ __launch_bounds__(NO_THREADS) void nn_maxmin_step_kernel(NoArgs a) {
         double m = m0;
         if (i == j) m = -1.0;
         else if (m >= 0.0) {
-            double dist = 0.0;
-#pragma unroll
-            for (int k = 0; k < DD; ++k)
-                if (k < d) { const double e = (a.x[i * d + k] - xj[k]) * is[k]; dist = fma(e, e, dist); }
+            double dist = nn_dist2<DD>(a.x + i * d, xj, is, d);
             if (!(dist >= 0.0)) dist = 0.0;        // a distance that is no number counts as 0: the order stays total
             if (dist < m) m = dist;
         }
@@ -88,18 +84,6 @@ __global__ __launch_bounds__(NO_THREADS) void nn_maxmin_step_kernel(NoArgs a) {
     }
     b = block_best(b, sb);
     if (tid == 0) a.part[(long)(a.t & 1) * NO_MAX_WGS + blockIdx.x] = b;
-}
-
-// f(std::integral_constant<int, D>) with the dimensions that have an instantiation of their own (those of the search)
-template <class F>
-inline void dispatch_dim(int d, F &&f) {
-    switch (d) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        default: f(std::integral_constant<int, 0>{}); break;
-    }
 }
 
 // work, in doubles: the n distances, then the two rows of partials (a Best is two doubles wide)
@@ -123,12 +107,7 @@ int fvgp_hip_nn_maxmin_order(fvgp_handle *h, const double *x, int64_t n, int d, 
     if (n < 1 || n > 0x7fffffffLL) return -3;
     if (d < 1 || d > FVGP_MAX_DIM) { fvgp_set_error("input dimension out of range"); return -4; }
     NoArgs a;
-    for (int k = 0; k < FVGP_MAX_DIM; ++k) a.is[k] = 1.0;
-    if (scales_host)
-        for (int k = 0; k < d; ++k) {
-            if (!(scales_host[k] > 0.0) || !std::isfinite(scales_host[k])) { fvgp_set_error("nn_maxmin_order: scales must be positive and finite"); return -5; }
-            a.is[k] = 1.0 / scales_host[k];
-        }
+    if (!nn_scales("nn_maxmin_order", scales_host, d, FVGP_MAX_DIM, a.is)) return -5;
     if (first < 0 || first >= n) { fvgp_set_error("nn_maxmin_order: first must be one of the n points"); return -6; }
     if (q < 1 || q > n) { fvgp_set_error("nn_maxmin_order: 1 .. n points to order"); return -7; }
     if (!perm_out) return -8;

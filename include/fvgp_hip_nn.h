@@ -1,5 +1,5 @@
 /*
- * fvgp_hip_nn.h -- the nearest-neighbour (Vecchia / NNGP "response") entries of libfvgp_hip.so (csrc/nn.hip).
+ * fvgp_hip_nn.h -- the nearest-neighbour (Vecchia / NNGP "response") entries of libfvgp_hip.so (csrc/nn.hip, csrc/nn_search.hip).
  *
  * The likelihood of n points as a product of n small conditionals, p(y) ~ prod_i p(y_i | y_c(i)), c(i) the m nearest of the points
  * that come earlier in the ordering; prediction at x* conditions on the m nearest data points.  O(n m^3) time, O(n m) memory, no

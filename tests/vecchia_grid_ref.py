@@ -86,7 +86,7 @@ def build_ref(xr, scales=None, occupancy=OCCUPANCY, shuffle=None, h=None):
     if not 1 <= d <= 3:
         raise ValueError("the cell grid takes 1 .. 3 dimensions")
     g = Grid()
-    g.inv = np.ones(d) if scales is None else 1.0 / np.asarray(scales, dtype=np.float64)
+    g.inv = vr.inv_scales(scales, d)
     g.lo, hi = xr.min(axis=0), xr.max(axis=0)
     with np.errstate(over="ignore", invalid="ignore"):
         ext = (hi - g.lo) * g.inv

@@ -21,30 +21,16 @@ LD = vr.LD
 U = LD(2) ** -53                 # the unit roundoff of a double
 
 
-def _inv(scales, d, dtype):
-    return np.ones(d, dtype=dtype) if scales is None else dtype(1) / np.asarray(scales, dtype=dtype)
-
-
-def _dist_to(x, j, inv, dtype):
-    """(n,): sum_k ((x_ik - x_jk) * inv_k)^2 in ascending k, in dtype"""
-    out = np.zeros(len(x), dtype=dtype)
-    for k in range(x.shape[1]):
-        e = (x[:, k] - x[j, k]) * inv[k]
-        out = out + e * e
-    return out
-
-
 def maxmin_ref(x, scales, first, q):
     """(perm (q,) int64, dist2 (q,) float64): perm[0] = first, perm[t] the point not picked yet with the largest squared scaled distance
     to its nearest earlier pick (ties to the lowest index), dist2[t] that distance, dist2[0] = inf"""
     x = np.asarray(x, dtype=np.float64)
-    inv = _inv(scales, x.shape[1], np.float64)
     mind = np.full(len(x), np.inf)
     perm, dist2 = np.empty(q, dtype=np.int64), np.empty(q)
     j, dj = int(first), np.inf
     for t in range(q):
         perm[t], dist2[t] = j, dj
-        mind = np.minimum(mind, _dist_to(x, j, inv, np.float64))
+        mind = np.minimum(mind, vr.distances(x, x[j:j + 1], scales)[:, 0])
         mind[perm[:t + 1]] = -1.0                      # picked (a duplicate of a pick has 0, and is still to come)
         j = int(np.argmax(mind))                       # the first of the largest: the lowest index
         dj = mind[j]
@@ -54,7 +40,7 @@ def maxmin_ref(x, scales, first, q):
 def first_point(x, scales):
     """the facade's rule: the point nearest, in the scaled coordinates, to their mean; ties to the lowest index"""
     x = np.asarray(x, dtype=np.float64)
-    z = x if scales is None else x * (1.0 / np.asarray(scales, dtype=np.float64))
+    z = x if scales is None else x * vr.inv_scales(scales, x.shape[1])
     return int(np.argmin(np.sum((z - np.mean(z, axis=0)) ** 2, axis=1)))
 
 
@@ -84,12 +70,12 @@ def check_maxmin(perm, dist2, x, scales, first):
     assert len(np.unique(perm)) == q, "a repeated index"
     assert dist2[0] == np.inf
     assert np.all(dist2[2:] <= dist2[1:-1]), "the entry distances increase somewhere"
-    xl, inv = x.astype(LD), _inv(scales, d, LD)
+    xl = x.astype(LD)
     slack, tol = 1 + (2 * d + 12) * U, (d + 6) * U
     mind = np.full(n, np.inf, dtype=LD)
     free = np.ones(n, dtype=bool)
     for t in range(1, q):
-        mind = np.minimum(mind, _dist_to(xl, perm[t - 1], inv, LD))
+        mind = np.minimum(mind, vr.distances(xl, xl[perm[t - 1]:perm[t - 1] + 1], scales, LD)[:, 0])
         free[perm[t - 1]] = False
         mine, best = mind[perm[t]], np.max(mind[free])
         assert mine * slack >= best, ("not the farthest point", t, int(perm[t]), float(mine), float(best))

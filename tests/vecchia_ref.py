@@ -34,11 +34,16 @@ FLOOR = {"mu": 3.40e-14, "d": 7.05e-14, "loglik": 4.51e-15, "fit": 3.90e-15, "lo
 
 
 # ---- the search ---------------------------------------------------------------------------------------------------------------------
+def inv_scales(scales, d, dtype=np.float64):
+    """(d,): 1 / scale_k in dtype, ones for scales None -- the one place the twins of the search, the ordering and the grid take it from"""
+    return np.ones(d, dtype=dtype) if scales is None else dtype(1) / np.asarray(scales, dtype=dtype)
+
+
 def distances(xq, xr, scales=None, dtype=np.float64):
     """(nq, nr): sum_k ((xq_ik - xr_jk) * (1 / scale_k))^2 added in ascending k (float64: every operation as the device rounds it,
     except that the device fuses each square into the sum)"""
     xq, xr = np.asarray(xq, dtype=dtype), np.asarray(xr, dtype=dtype)
-    inv = np.ones(xq.shape[1], dtype=dtype) if scales is None else dtype(1) / np.asarray(scales, dtype=dtype)
+    inv = inv_scales(scales, xq.shape[1], dtype)
     out = np.zeros((len(xq), len(xr)), dtype=dtype)
     for k in range(xq.shape[1]):
         e = (xq[:, k][:, None] - xr[:, k][None, :]) * inv[k]
