@@ -40,7 +40,8 @@ int fvgp_hip_nn_search(fvgp_handle *h, const double *xq, int64_t nq, const doubl
                        int m, int64_t c0, int *idx_out, int64_t ld);
 
 /* The conditionals.  For query row i with the neighbour list c = idx[i][0 .. m) (entries outside 0 .. nr - 1, the -1 of the search among
- * them, are skipped) and each of the B rows theta_b of thetas_host (B, ntheta):
+ * them, are skipped wherever in the list they stand, between neighbours too; a list of such entries alone is an empty list, bit for bit;
+ * columns m .. ld of idx are never read) and each of the B rows theta_b of thetas_host (B, ntheta):
  *     A = K(x_c, x_c) + diag(v_c),  k = K(x_c, x_i),  A = L L^T,  w = L^-1 k,  z = L^-1 r_c,
  *     mu[b][i] = w^T z,     var[b][i] = (k(x_i, x_i) + s_i) - w^T w
  * r (nr): the caller's centred data on the reference rows, v (nr): their noise, s_or_null (nq): a per-query addend (the row's own noise
@@ -90,7 +91,7 @@ int64_t fvgp_hip_nn_workspace_bytes(int what, int64_t nq, int B);
  * sum_{p > q'} (b_p q_q' + b_q' q_p) dSigma[p][q'] + sum_p b_p q_p dSigma[p][p], one more sweep over the (m + 1)(m + 2) / 2 entries, each
  * evaluated with its derivative: dK / d sigma^2 = phi, dK / d l_k = cf e2[k] invl[k]; a kernel with one length scale for every dimension
  * adds the d terms into it.  A row without neighbours has the sigma^2 term of d = k(x, x) + v alone.  score (B, n, ntheta) device:
- * columns past the kernel's own hyperparameters receive 0.
+ * columns past the kernel's own hyperparameters receive +0.0 (so does grad_host there), and nothing else depends on ntheta.
  * BIT CONTRACT: out_host, mu and var are bit for bit those of fvgp_hip_nn_loglik on the same inputs.  score[b][i][:] is a function of
  * (x_i, v_i, the listed rows in their listed order, theta_b, m) alone: not of n, B, or the position in either.  The rows' scores are added
  * as the likelihood's terms are (slices of 256 rows by a halving tree, the slices to 0 in ascending order, one thread per (b, h)): the
@@ -119,7 +120,7 @@ int64_t fvgp_hip_nn_grad_workspace_bytes(int64_t n, int B, int ntheta);
  * tree.  A row without neighbours has 1/2 delta delta^T / var^2 alone, delta = (1, 0, ..).  With every earlier point a neighbour the sum
  * is the dense 1/2 tr((K + V)^-1 d_h K (K + V)^-1 d_k K).
  * fisher_rows (B, n, P) device, P = ntheta (ntheta + 1) / 2: the packed lower triangle of F_i, (h, k <= h) at h (h + 1) / 2 + k; entries
- * that involve a column past the kernel's own hyperparameters receive 0.  fisher_host (B, ntheta, ntheta) host: the sums, full symmetric.
+ * that involve a column past the kernel's own hyperparameters receive +0.0.  fisher_host (B, ntheta, ntheta) host: the sums, full symmetric.
  * BIT CONTRACT: out_host, mu, var, score and grad_host are bit for bit those of fvgp_hip_nn_loglik_grad on the same inputs.
  * fisher_rows[b][i][:] is a function of (x_i, v_i, the listed rows in their listed order, theta_b, m) alone: not of n, B, or the position in
  * either, and -- unlike the score -- not of r.  The rows' terms are added as the scores are (slices of 256 rows by a halving tree, the

@@ -1,4 +1,5 @@
-"""What the GPU tests of the nearest-neighbour likelihood share (test_gpu_vecchia.py, test_gpu_vecchia_grad.py, test_gpu_vecchia_fisher.py):
+"""What the GPU tests of the nearest-neighbour likelihood share (test_gpu_vecchia.py, test_gpu_vecchia_grad.py, test_gpu_vecchia_fisher.py,
+test_gpu_vecchia_family.py):
 canary-framed device outputs and the three likelihood entries of Handle called into them.  Each test file keeps its own H fixture."""
 import numpy as np
 
@@ -39,7 +40,8 @@ def _device(H, level, name, x, thetas, idx, m, r, v):
     n = len(x)
     shapes = [(B, n), (B, n), (B, n, nth), (B, n, nth * (nth + 1) // 2)][:2 + level]
     bigs, views = zip(*(_framed(H, *s) for s in shapes))
-    idx_d = H.torch.as_tensor(np.ascontiguousarray(idx), device=views[0].device)
+    # (a device tensor goes in as it is: a view with a leading dimension of its own)
+    idx_d = idx if isinstance(idx, H.torch.Tensor) else H.torch.as_tensor(np.ascontiguousarray(idx), device=views[0].device)
     call = (H.nn_loglik, H.nn_loglik_grad, H.nn_loglik_fisher)[level]
     host = call(_kid(name), H.to_device(x), thetas, idx_d, m, H.to_device(r), H.to_device(v), *views)
     assert all(_frame_untouched(b) for b in bigs)
