@@ -134,8 +134,10 @@ static void batch_results(int64_t n, int ncol, int64_t B, const double *r, const
     }
 }
 
-// B independent evaluations side by side (batch.hip): assembly, appended rows, then per 128 columns one leaf launch, one panel TRSM
-// (product with the block inverse) and one update of the trailing lower tiles (K = 128), each over every problem, then one tail.
+// B independent evaluations side by side (batch.hip): assembly, appended rows, then the factorisation by recursive halving over the
+// block columns (batch_recursion) -- per 128 columns one leaf launch and one panel TRSM (product with the block inverse), between the
+// two halves of every halving ONE update of the right half's lower tiles with K = the left half's width --, each launch over every
+// problem, then one tail.
 int fvgp_hip_loglik_batch(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
                           const double *thetas, int ntheta, int64_t B,
                           const double *vdiag, int64_t vdiag_stride, const double *ymean, int64_t ymean_stride, int ncol,
