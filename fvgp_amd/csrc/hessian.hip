@@ -11,6 +11,9 @@
 // of every partial sum and ONE synchronisation.  No atomics: a workgroup owns its row of partial sums and the host adds the rows in
 // index order, so the same inputs give the same bits.  K_i is zero in the padding and W finite there, so nothing of the padding
 // reaches an entry < n.
+//
+// KV is destroyed: it holds KV^-1, both triangles, on return -- nothing writes it after the mirror (the products only read it).  The
+// header states this as part of the contract; the tests read W back from there (tests/test_gpu_hessian_family.py).
 #include "radial.h"
 #include "kernel_family.h"
 #include <math.h>

@@ -432,8 +432,10 @@ int fvgp_hip_loglik_grad(fvgp_handle *h, int kernel_id, const double *x, int64_t
  * gradient of fvgp_hip_loglik_grad from the same call (no counterpart in the reference, whose gp_marginal_likelihood.py:312-336
  * differences the gradient).  With W = KV^-1, b = KVinvY[:, component], K_i = dK/dtheta_i, G_i = W K_i W, w_i = W K_i b:
  *   H_ij = 1/2 sum_ab (W - b b^T)_ab (d2K/dtheta_i dtheta_j)_ab - [ 1/2 tr(G_i K_j) - b^T K_j w_i ]
- *   KV on entry: the factor L from fvgp_hip_loglik / potrf (its strict upper triangle is never read).  KV, work and work2 -- three
- *   padded_dim(n)-row scratches, each 16-byte aligned with an even leading dimension >= padded_dim(n) -- are destroyed.
+ *   KV on entry: the factor L from fvgp_hip_loglik / potrf (its strict upper triangle is never read) -- any lower factor, with any
+ *   alpha: W is the inverse of L L^T.  KV, work and work2 -- three padded_dim(n)-row scratches, each 16-byte aligned with an even
+ *   leading dimension >= padded_dim(n) -- are destroyed: KV holds KV^-1, both triangles, on return (nothing writes it after the
+ *   mirror), work and work2 the last hyperparameter's products.
  *   ws: device scratch of fvgp_hip_loglik_hess_workspace_bytes(n, d) bytes, 8-byte aligned.
  *   grad_host: ntheta doubles (kernel-owned entries, the rest 0).
  *   hess_host: nk x nk doubles, row-major, nk = the kernel's parameter count (d + 1, or 2 for an isotropic kernel): the RAW block --

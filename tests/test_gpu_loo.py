@@ -24,6 +24,10 @@ ABI_CASES = ([(name, 300, 3, 1, 0) for name in NAMES]           # an interior of
                 ("rbf_ard", 200, 5, 1, 0),                      # the runtime-dimension instantiation
                 ("rbf_ard", 1100, 2, 1, 0),                     # padded 1152 > POTRI's 1024-wide panel: two panels
                 ("matern52_iso", 300, 3, 2, 1)])
+# every (name, d) of the family grid that ABI_CASES does not hold, by rule, at n = 261: the smallest size with an interior tile strictly
+# below the diagonal (tile (1, 0): the two-rows-per-trip path of the two-vector trace), partial edge tiles (tile row 2 has five rows),
+# an odd n and padding to 384 -- the list tests/hessian_ref.py builds for the Hessian
+FAMILY_CASES = [(name, 261, d, 1, 0) for name in NAMES for d in kf.DIMS if (name, d) not in {(c[0], c[2]) for c in ABI_CASES}]
 
 
 @pytest.fixture(scope="module")
@@ -84,14 +88,12 @@ def _loo(H, name, x, theta, KV, alpha, comp, grad=True):
     return out, g, host(resid), host(var), host(u), host(md), A
 
 
-@pytest.mark.parametrize("name,n,d,ncol,comp", ABI_CASES)
-def test_abi_against_extended_precision(H, name, n, d, ncol, comp):
-    (x, ym, V, theta), (value, resid_r, var_r, grad_r, u_r, md_r) = _reference(name, n, d, ncol, comp)
-    KV, alpha = _factor(H, name, x, ym, V, theta)
-    out, g, resid, var, u, md, _ = _loo(H, name, x, theta, KV, alpha, comp)
+def bar_ratios(out, g, resid, var, u, md, ref):
+    """the eight figures of a result (device, or the float64 twin of tests/test_loo_host.py) over their bars, against _reference's"""
+    value, resid_r, var_r, grad_r, u_r, md_r = ref
     f = lambda a: np.asarray(a, dtype=np.float64)
-    rel_max = lambda got, ref: float(np.max(np.abs(got - ref)) / np.max(np.abs(ref)))
-    ratios = {
+    rel_max = lambda got, want: float(np.max(np.abs(got - want)) / np.max(np.abs(want)))
+    return {
         "value": abs(out[0] - float(value)) / (1e-10 * abs(float(value))),
         "sum resid^2": abs(out[1] - float(np.sum(resid_r ** 2))) / (1e-10 * float(np.sum(resid_r ** 2))),
         "sum log q": abs(out[2] + float(np.sum(np.log(var_r)))) / (1e-10 * float(np.sum(np.abs(np.log(var_r))))),
@@ -101,12 +103,31 @@ def test_abi_against_extended_precision(H, name, n, d, ncol, comp):
         "u": rel_max(u, f(u_r)) / 1e-8,
         "diag M": rel_max(md, f(md_r)) / 1e-8,
     }
+
+
+def _abi_case(H, name, n, d, ncol, comp):
+    (x, ym, V, theta), ref = _reference(name, n, d, ncol, comp)
+    KV, alpha = _factor(H, name, x, ym, V, theta)
+    out, g, resid, var, u, md, _ = _loo(H, name, x, theta, KV, alpha, comp)
+    ratios = bar_ratios(out, g, resid, var, u, md, ref)
     for key, r in ratios.items():
         _report(f"{key} / bar", name, d, n, r)
     assert out[3] == 0
     assert g.shape == theta.shape
     worst = max(ratios, key=ratios.get)
     assert ratios[worst] <= 1.0, f"{worst}: {ratios[worst]:.3g} times its bar"
+
+
+@pytest.mark.parametrize("name,n,d,ncol,comp", ABI_CASES)
+def test_abi_against_extended_precision(H, name, n, d, ncol, comp):
+    _abi_case(H, name, n, d, ncol, comp)
+
+
+@pytest.mark.parametrize("name,n,d,ncol,comp", FAMILY_CASES)
+def test_abi_against_extended_precision_every_instantiation(H, name, n, d, ncol, comp):
+    """the same eight ratios under the same bars on the rest of the (kind, D) grid: with ABI_CASES every instantiation of the two-vector
+    gradient trace (grad_trace_kernel<KIND, D, TWO = true>) runs, its interior, edge and diagonal tiles each"""
+    _abi_case(H, name, n, d, ncol, comp)
 
 
 def _lower_tile_mask(dim, np_):

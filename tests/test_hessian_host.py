@@ -67,9 +67,20 @@ def test_hessian_equals_central_difference_of_its_gradient(name, d):
     assert asym <= 1e-14
 
 
-@pytest.mark.parametrize("name,n,d,ncol,comp,dup", hr.ABI_CASES)
+def test_family_cases_complete_the_grid():
+    """ABI_CASES and FAMILY_CASES hold every (name, d) of the family grid, FAMILY_CASES each at n = 261 and none twice: 8 of the 15
+    <KIND, D> cells before, 15 with the sweep"""
+    have = [(c[0], c[2]) for c in hr.FAMILY_CASES]
+    assert len(set(have)) == len(have) and all(c[1] == hr.FAMILY_N == 261 for c in hr.FAMILY_CASES)
+    assert not set(have) & {(c[0], c[2]) for c in hr.ABI_CASES}
+    assert set(have) | {(c[0], c[2]) for c in hr.ABI_CASES} == {(name, d) for name in kf.FAMILY for d in kf.DIMS}
+    cells = lambda cases: {hr.cell(c[0], c[2])[:2] for c in cases}
+    assert len(cells(hr.ABI_CASES)) == 8 and len(cells(hr.ABI_CASES + hr.FAMILY_CASES)) == 15
+
+
+@pytest.mark.parametrize("name,n,d,ncol,comp,dup", hr.ABI_CASES + hr.FAMILY_CASES)
 def test_float64_twin_sits_far_inside_the_device_bar(name, n, d, ncol, comp, dup):
-    """the same formulas in float64 against longdouble on every case of the device test: at most 1e-2 of the device's bar
+    """the same formulas in float64 against longdouble on every case of the device tests: at most 1e-2 of the device's bar
     (|dH_ij| <= 1e-8 |H_ij| + 1e-9 max|H|, gradient alike), so the bar judges the device and not the conditioning of the case"""
     (x, ym, V, theta), (g, raw) = hr.reference(name, n, d, ncol, comp, dup)
     g64, raw64 = hr.nll_hessian_ref(name, x, ym[:, comp], V, theta, dtype=np.float64)

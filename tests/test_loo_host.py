@@ -1,6 +1,6 @@
 """Leave-one-out cross-validation without a GPU: the extended-precision reference's closed forms (tests/loo_ref.py) against n brute-force
-refits, its gradient against a central difference of the brute-force value, the facade's host assembly of the noise and mean terms
-against hand-differentiated references, and the ABI surface of fvgp_hip_loo."""
+refits, its gradient against a central difference of the brute-force value, the float64 twin on the cases of the device test, the
+facade's host assembly of the noise and mean terms against hand-differentiated references, and the ABI surface of fvgp_hip_loo."""
 import ctypes
 
 import numpy as np
@@ -8,6 +8,7 @@ import pytest
 
 import kernel_family_ref as kf
 import loo_ref
+import test_gpu_loo as gl
 
 LD = np.longdouble
 
@@ -53,6 +54,31 @@ def test_gradient_equals_central_difference_of_brute_force(name, n, d):
     err = float(np.max(np.abs(fd - g)) / np.max(np.abs(g)))
     print(f"LOO|gradient vs central difference|{name}|{d}|{n}|{err:.3g}")
     assert err <= 1e-7
+
+
+def test_family_cases_complete_the_grid():
+    """ABI_CASES and FAMILY_CASES of the device test hold every (name, d) of the family grid, FAMILY_CASES each at n = 261, none twice"""
+    have = [(c[0], c[2]) for c in gl.FAMILY_CASES]
+    assert len(set(have)) == len(have) and all(c[1] == 261 for c in gl.FAMILY_CASES)
+    assert not set(have) & {(c[0], c[2]) for c in gl.ABI_CASES}
+    assert set(have) | {(c[0], c[2]) for c in gl.ABI_CASES} == {(name, d) for name in kf.FAMILY for d in kf.DIMS}
+    cells = lambda cases: {(kf.FAMILY[c[0]][0], c[2] if c[2] <= 4 else 0) for c in cases}
+    assert len(cells(gl.ABI_CASES)) == 6 and len(cells(gl.ABI_CASES + gl.FAMILY_CASES)) == 15
+
+
+@pytest.mark.parametrize("name,n,d,ncol,comp", [c for c in gl.ABI_CASES if c[1] <= 300] + gl.FAMILY_CASES)
+def test_float64_twin_sits_far_inside_the_device_bars(name, n, d, ncol, comp):
+    """the same closed forms in float64 against longdouble on the cases of the device test (the two-panel n = 1100 case left to the
+    device: its longdouble reference alone takes most of a minute): every one of the eight figures at most 1e-2 of its bar -- the cap
+    tests/test_hessian_host.py holds the Hessian's twin to --, so the bars judge the device and not the conditioning of the case"""
+    (x, ym, V, theta), ref = gl._reference(name, n, d, ncol, comp)
+    value, m_loo, v_loo, grad, u, md = loo_ref.loo_closed(name, x, ym[:, comp], V, theta, dtype=np.float64)
+    resid = ym[:, comp] - m_loo
+    out = [value, np.sum(resid ** 2), -np.sum(np.log(v_loo))]
+    ratios = gl.bar_ratios(out, grad, resid, v_loo, u, md, ref)
+    worst = max(ratios, key=ratios.get)
+    print(f"LOO|float64 twin / bar|{name}|{d}|{n}|worst {worst} {ratios[worst]:.3g}")
+    assert ratios[worst] <= 1e-2, f"{worst}: {ratios[worst]:.3g} of its bar"
 
 
 def _noise(x, a):
