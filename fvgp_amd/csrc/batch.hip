@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void kmat_batch_kernel(KBArgs a) {
     }
 }
 
-// rhs_rows_kernel (solve.hip) per problem (blockIdx.x): rows n .. n + ncol - 1 of the square <- (y - m)^T, diagonal entry
+// rhs_rows_kernel (reduce.hip) per problem (blockIdx.x): rows n .. n + ncol - 1 of the square <- (y - m)^T, diagonal entry
 // 1 + |y - m|^2 / min V (keeps the appended block positive definite; the factorisation leaves z^T = (L^-1 (y - m))^T there)
 __global__ __launch_bounds__(1024) void rhs_rows_batch_kernel(double *KV, long kv_stride, long n, long lda, const double *ymean, long ym_stride,
                                                                int ncol, const double *vdiag, long vd_stride) {

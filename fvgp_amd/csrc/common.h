@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/fvgp_hip.h"
 
@@ -95,7 +96,7 @@ struct fvgp_handle {
     // load and sleep while it is up (fp64 MFMA and the vector ALU share a pipe: beside an MFMA stream every dependent instruction
     // of the latency-bound leaf waits for a 64-cycle MFMA -- 3.5 to 6.7 times the standalone time).  Option "leaf_yield".
     int *cu_yield = nullptr; int leaf_yield = 1, chain_yield = 1;      // chain_yield 2: the resident panel kernel's block rows below the square raise it too
-    // backward sweep in one launch (solve.hip, bwd_sweep_kernel): granules of {value, tag}, the launch counter the tags come from,
+    // backward sweep in one launch (sweep.hip, bwd_sweep_kernel): granules of {value, tag}, the launch counter the tags come from,
     // the column ticket; option "bwd_sweep"
     double *sweep_gran = nullptr; size_t sweep_gran_cap = 0; unsigned long long sweep_tag = 0; int *sweep_ticket = nullptr; int bwd_sweep = 1, fwd_sweep = 1;
     // the panel chain as one resident kernel per panel (chain.hip): flag words, the launch tag and ticket bases; option "panel_chain"
@@ -168,6 +169,19 @@ int fvgp_hip_fail(hipError_t e, const char *what, int line);
 
 static inline int64_t pad128(int64_t n) { return (n + TILE - 1) / TILE * TILE; }
 static inline int64_t even_up(int64_t v) { return (v + 1) & ~(int64_t)1; }      // workspace pieces in doubles: every offset stays 16-byte aligned
+
+// the vector kernels are instantiated for 1, 2, 4 and 8 right-hand sides: the narrowest width that holds c (<= FVGP_MAX_RHS_VEC) columns
+static inline int rhs_width(int c) { return c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : 8; }
+// f(std::integral_constant<int, C>) for that width; the launch's status comes back
+template <class F>
+inline int dispatch_rhs_width(int c, F &&f) {
+    switch (rhs_width(c)) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        default: return f(std::integral_constant<int, 8>{});
+    }
+}
 
 // ---- launches implemented in the .hip units ------------------------------------------------
 struct GemmDesc {
@@ -292,7 +306,6 @@ int launch_coldot(fvgp_handle *h, const double *A, int64_t lda, const double *B,
 int launch_add_matrix(fvgp_handle *h, double *A, int64_t lda, const double *B, int64_t ldb, int64_t rows, int64_t cols, double alpha);
 int launch_pad_identity(fvgp_handle *h, double *A, int64_t n, int64_t np, int64_t lda);
 int launch_rhs_rows(fvgp_handle *h, double *A, int64_t n, int64_t lda, const double *ymean, int ncol, const double *vdiag);
-int launch_rows_to_vec(fvgp_handle *h, const double *A, int64_t lda, int64_t row0, int nrows, double *vec, int C, int64_t np);
 int launch_rowsumsq(fvgp_handle *h, const double *A, int64_t lda, int64_t row0, int nrows, int64_t ncols, double *out_dev);
 int launch_copy_cols(fvgp_handle *h, const double *src, int64_t lds, double *dst, int64_t ldd, int64_t rows, int64_t cols,
                      int64_t rows_pad, int64_t cols_pad);
@@ -303,8 +316,6 @@ int launch_colsumsq(fvgp_handle *h, const double *V, int64_t rows, int64_t ldv, 
 int launch_rows_dot(fvgp_handle *h, const double *KT, int64_t ldk, const double *alpha, int64_t lda, int ncol, int64_t n, int64_t P,
                     double *out, int64_t ldo);
 int launch_rows_sumsq_base(fvgp_handle *h, const double *KT, int64_t ldk, int64_t n, int64_t P, double base, double *out);
-int launch_splitk_reduce(fvgp_handle *h, const double *ws, int split, int64_t M, int64_t N, int lower, const double *C, int64_t ldc, double beta,
-                         double *out, int64_t ldo, int64_t tri_ksplit = 0);
 int launch_winv_seed(fvgp_handle *h, const double *linv, int64_t nblk, double *W, int64_t w = 1024);
 int launch_mfma_selftest(fvgp_handle *h, const double *A, const double *B, double *D);
 int launch_mfma_peak(fvgp_handle *h, double *out, int blocks, int iters);

@@ -16,6 +16,7 @@
 // header states this as part of the contract; the tests read W back from there (tests/test_gpu_hessian_family.py).
 #include "radial.h"
 #include "kernel_family.h"
+#include "reduce.h"
 #include <math.h>
 
 namespace {
@@ -244,11 +245,8 @@ __global__ __launch_bounds__(256) void rowdot_scale_kernel(const double *T, long
             s = fma(tv[1], b[(i + 1) * ldb], fma(tv[0], b[i * ldb], s));
         } else s = fma(row[i], b[i * ldb], s);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63) == 0) sp[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[p] = scale * ((sp[0] + sp[1]) + (sp[2] + sp[3]));
+    const double t = block_sum4(s, sp);
+    if (threadIdx.x == 0) out[p] = scale * t;
 }
 
 int launch_hess_trace(fvgp_handle *h, const KmatDesc &k, const double *W, int64_t ldw, const double *b, int64_t ldb, double *partial,

@@ -12,6 +12,7 @@
 // bits on every run.  Rows >= n of the scratch vectors are zero, so the identity padding of Q drops out of u, S and M.
 #include "common.h"
 #include "kernel_family.h"
+#include "reduce.h"
 #include <math.h>
 
 namespace {
@@ -74,8 +75,7 @@ __global__ __launch_bounds__(256) void symv_lower_kernel(const double *Q, long l
         double t0 = q0, t1 = q1;
         if (diag) { if (cl == rr) t0 = 0.0; if (cl + 1 == rr) t1 = 0.0; }
         a0 = fma(t0, wr, a0); a1 = fma(t1, wr, a1);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) rs += __shfl_down(rs, off, 64);
+        rs = wave_sum(rs);
         if (lane == 0) srow[rr] = rs;
     }
     scol[wave][cl] = a0; scol[wave][cl + 1] = a1;

@@ -11,6 +11,7 @@
 // fvgp_hip_pcg_lanczos      the solver with the coefficients of every column's first recurrence recorded (one driver serves both entries).
 #include "radial.h"
 #include "kernel_family.h"
+#include "reduce.h"
 #include "slice_sum.h"
 #include "pivot.h"
 #include "normal.h"
@@ -323,8 +324,7 @@ __global__ __launch_bounds__(256) void pcg_gr_kernel(const double *G, long ldg, 
                 double acc = 0.0;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) acc = fma(gk[k], sr[c][lane + 64 * k], acc);
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+                acc = wave_sum(acc);
                 if (lane == 0) { double *o = out + (long)t * PCG_LD + c; *o = ib == i0 ? acc : *o + acc; }
             }
         }
@@ -369,9 +369,7 @@ __global__ __launch_bounds__(256) void pcg_apply_kernel(const double *G, long ld
     // the block's r.z: lanes by the shuffle tree, then the four waves in order
 #pragma unroll
     for (int c = 0; c < PCG_LD; ++c) {
-        double w = rz[c];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
+        const double w = wave_sum(rz[c]);
         if (lane == 0) sp[wave][c] = w;
     }
     __syncthreads();

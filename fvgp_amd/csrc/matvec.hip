@@ -12,6 +12,7 @@
 // Both entries split by ONE rule (mv_plan): the chunk ranges dealt over gridDim.y, the chunk sums parked or not.
 #include "radial.h"
 #include "kernel_family.h"
+#include "reduce.h"
 #include "slice_sum.h"
 #include <math.h>
 
@@ -144,9 +145,7 @@ __device__ __forceinline__ void kg_block_sum(double (&tot)[DD + 1], int nh, int 
 #pragma unroll
     for (int hh = 0; hh < DD + 1; ++hh)
         if (hh < nh) {
-            double w = tot[hh];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
+            const double w = wave_sum(tot[hh]);
             if (lane == 0) out[hh] = w;
         }
 }

@@ -15,6 +15,7 @@
 //     LDS, the slices to 0 in ascending order by one thread per (b, column).  No atomics anywhere.  The triangle is mirrored on the host.
 #include "radial.h"
 #include "kernel_family.h"
+#include "reduce.h"
 #include "nn_geometry.h"
 #include "../../include/fvgp_hip_nn.h"
 #include <math.h>
@@ -37,13 +38,6 @@ __device__ __forceinline__ void wave_sync() {
 __device__ __forceinline__ double lane_value(const double v, const int j) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), j), hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
     return __hiloint2double(hi, lo);
-}
-
-// lane 0 <- the 64 lanes' values by the halving tree (lane i += lane i + 32, 16, .. 1)
-__device__ __forceinline__ double wave_tree_sum(double w) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
-    return w;
 }
 
 // the level of a likelihood call, and what nn_cond_kernel computes beside mu and var: nothing, every row's score, or the score and the
@@ -149,7 +143,7 @@ __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
         wave_sync();
     }
     if (lane >= M) { tw = 0.0; tz = 0.0; }
-    const double mu = wave_tree_sum(tw * tz), ww = wave_tree_sum(tw * tw);
+    const double mu = wave_sum(tw * tz), ww = wave_sum(tw * tw);
     if (lane == 0) {
         double kxx = radial<KIND>(0.0, sig);
         if (a.s) kxx += a.s[row];
@@ -208,7 +202,7 @@ __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
 #pragma unroll
         for (int h = 0; h <= DD; ++h)
             if (h < np) {
-                double s = wave_tree_sum(acc[h]);
+                double s = wave_sum(acc[h]);
                 if (h == 0) s += c2;               // the diagonal entry of x_i itself
                 if (lane == 0) out[h] = fail ? NAN : s;
             }
@@ -260,7 +254,7 @@ __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
                         if (h > 0) dk = iso ? cf * (r2 * il[0]) : cf * (ek[h ? h - 1 : 0] * ek[h ? h - 1 : 0] * il[h ? h - 1 : 0]);
                         double s = 0.0;
                         if (valid) { t[h] += dk; s = bl * (t[h] + dk); }
-                        s = wave_tree_sum(s);
+                        s = wave_sum(s);
                         dlt[h] = h == 0 ? s + 1.0 : s;
                     }
             }
@@ -284,7 +278,7 @@ __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
                 if (h < np) {
 #pragma unroll
                     for (int k = 0; k <= h; ++k) {
-                        const double s = wave_tree_sum(t[h] * t[k]);
+                        const double s = wave_sum(t[h] * t[k]);
                         if (lane == 0) fo[h * (h + 1) / 2 + k] = fail ? NAN : s / dv + 0.5 * (dlt[h] / dv) * (dlt[k] / dv);
                     }
                 }

@@ -8,7 +8,6 @@ int potrs_vec(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, double *B
     int rc = ensure_linv(h, L, n, ldl); if (rc) return rc;
     rc = ensure_scratch(h, np); if (rc) return rc;
     const int c = (int)nrhs;
-    const int C = c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : 8;
     double *Y = h->vec;
     if (h->fwd_sweep && c == 1) {               // one launch for the whole sweep (B is not touched)
         rc = launch_fwd_sweep(h, L, ldl, np, h->linv, B, ldb, Y); if (rc) return rc;
@@ -18,15 +17,14 @@ int potrs_vec(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, double *B
         if (rc) return rc;
     }
     if (!backward) {
-        // forward result lives in Y (np x C); copy back to B
-        return launch_copy_cols(h, Y, C, B, ldb, np, c, np, c);
+        // forward result lives in Y (np x rhs_width(c)); copy back to B
+        return launch_copy_cols(h, Y, rhs_width(c), B, ldb, np, c, np, c);
     }
     if (h->bwd_sweep && c == 1) return launch_bwd_sweep(h, L, ldl, np, h->linv, Y, B, ldb, c);        // one launch for the whole sweep
     for (int64_t k0 = np - TILE; k0 >= 0; k0 -= TILE) {
         rc = launch_bwd_step(h, L, ldl, np, k0, h->linv + (k0 / TILE) * LEAF_DOUBLES, Y, B, ldb, c);
         if (rc) return rc;
     }
-    (void)C;
     return 0;
 }
 

@@ -1,4 +1,4 @@
-"""Every path of the triangular solves (csrc/tri_solve.hip, csrc/solve.hip, fvgp_hip_panel_trsm) against the extended-precision reference
+"""Every path of the triangular solves (csrc/tri_solve.hip, csrc/sweep.hip, fvgp_hip_panel_trsm) against the extended-precision reference
 of tests/tri_solve_ref.py, which tests/test_tri_solve_ref.py proves on the host: the vector path at 1 .. 8 columns (C = 1, 2, 4, 8, the
 one-launch sweeps on and off), block substitution on GEMMs under three outer blocks, the transposed sweep with the 1024-wide inverted
 blocks (full, one whole block short, and the narrow last pair of the doubling at padded_dim 2432; in two halves and in one; with
