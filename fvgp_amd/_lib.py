@@ -63,6 +63,8 @@ class DistDesc(ctypes.Structure):
 P_coll, P_desc = ctypes.POINTER(Collectives), ctypes.POINTER(DistDesc)
 _PCG_ARGS = [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_i, c_d, c_i, c_i, c_i,
              c_p, c_l, P_i, P_d, P_i]
+# the sparse nearest-neighbour factor as fvgp_hip_nn_precond_apply and fvgp_hip_pcg_nn take it: idx, ld, m, coef, dinv, tr_start, tr_pos, nnz
+_NN_FACTOR_ARGS = [c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_l]
 
 # name -> (restype, [argtypes]) for every prototype of include/fvgp_hip.h, in the header's order under its section comments
 # (tests/test_host_logic.py::test_abi_table_matches_header parses the header and holds this table to it)
@@ -202,6 +204,13 @@ _ABI_NN = {
     "fvgp_hip_nn_grid_workspace_bytes": (c_l, [c_l, c_i]),
     "fvgp_hip_nn_grid_build": (c_i, [c_p, c_p, c_l, c_i, P_d, c_p, c_l, c_p, c_l, P_d]),
     "fvgp_hip_nn_grid_search": (c_i, [c_p, c_p, c_l, c_p, c_l, c_i, c_i, c_l, P_d, c_p, c_p, c_l]),
+    # ---- the nearest-neighbour factor as the matrix-free solves' preconditioner
+    "fvgp_hip_nn_factor_workspace_bytes": (c_l, [c_l]),
+    "fvgp_hip_nn_factor": (c_i, [c_p, c_i, c_p, c_l, c_i, P_d, c_i, c_p, c_l, c_i, c_p, c_p, c_l, c_p, c_p, c_l, P_l]),
+    "fvgp_hip_nn_precond_apply_workspace_bytes": (c_l, [c_l]),
+    "fvgp_hip_nn_precond_apply": (c_i, [c_p, c_l] + _NN_FACTOR_ARGS + [c_p, c_l, c_i, c_p, c_l, c_p, c_l]),
+    "fvgp_hip_pcg_nn_workspace_bytes": (c_l, [c_l]),
+    "fvgp_hip_pcg_nn": (c_i, _PCG_ARGS[:8] + _NN_FACTOR_ARGS + _PCG_ARGS[13:]),
     "fvgp_hip_nn_maxmin_workspace_bytes": (c_l, [c_l]),
     "fvgp_hip_nn_maxmin_order": (c_i, [c_p, c_p, c_l, c_i, P_d, c_l, c_l, c_p, c_p, c_p, c_l]),
 }
@@ -379,6 +388,47 @@ def nn_fisher_workspace_bytes(n, B=1, ntheta=2):
     """bytes of the caller-owned workspace of Handle.nn_loglik_fisher for n rows, B hyperparameter vectors of ntheta numbers
     (fvgp_hip_nn_fisher_workspace_bytes); -1 for bad arguments"""
     return _workspace_bytes("fvgp_hip_nn_fisher_workspace_bytes", n, B, ntheta)
+
+
+def nn_factor_workspace_bytes(n):
+    """bytes of the caller-owned workspace of Handle.nn_factor for n rows (fvgp_hip_nn_factor_workspace_bytes); -1 for n < 1"""
+    return _workspace_bytes("fvgp_hip_nn_factor_workspace_bytes", n)
+
+
+def nn_precond_apply_workspace_bytes(n):
+    """bytes of the caller-owned workspace of Handle.nn_precond_apply for n rows (fvgp_hip_nn_precond_apply_workspace_bytes); -1 for
+    n < 1"""
+    return _workspace_bytes("fvgp_hip_nn_precond_apply_workspace_bytes", n)
+
+
+def pcg_nn_workspace_bytes(n):
+    """bytes of the caller-owned workspace of Handle.pcg_nn for n rows (fvgp_hip_pcg_nn_workspace_bytes); -1 for n < 1"""
+    return _workspace_bytes("fvgp_hip_pcg_nn_workspace_bytes", n)
+
+
+def nn_transpose_lists(idx, n):
+    """the transposed neighbour lists of idx (rows, ld) integers, on the host: (tr_start (n + 1,) int64, tr_pos (nnz,) int64).  Bucket j =
+    tr_pos[tr_start[j]:tr_start[j + 1]] holds the flat positions i * ld + l of the entries with idx[i][l] == j in ascending i (and l):
+    a stable argsort of the flattened lists, so the order -- and with it every sum over a bucket -- is the same on every call.  Entries
+    outside 0 .. n - 1 belong to no bucket."""
+    flat = np.ascontiguousarray(idx).reshape(-1).astype(np.int64)
+    valid = (flat >= 0) & (flat < n)
+    pos = np.flatnonzero(valid)
+    order = np.argsort(flat[pos], kind="stable")
+    start = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(flat[pos], minlength=n), out=start[1:])
+    return start, pos[order].astype(np.int64)
+
+
+class NNFactor:
+    """The sparse inverse Cholesky factor W of Handle.nn_factor with its transposed lists, as Handle.nn_precond_apply and Handle.pcg_nn
+    take it: device tensors idx (n, ld) int32, coef (n, ld), dinv (n), tr_start (n + 1) int64, tr_pos (max(nnz, 1)) int64, and m, nnz."""
+
+    def __init__(self, idx, m, coef, dinv, tr_start, tr_pos, nnz):
+        self.idx, self.m, self.coef, self.dinv, self.tr_start, self.tr_pos, self.nnz = idx, int(m), coef, dinv, tr_start, tr_pos, int(nnz)
+
+    def _args(self):
+        return (_ptr(self.idx), self.idx.stride(0), self.m, _ptr(self.coef), _ptr(self.dinv), _ptr(self.tr_start), _ptr(self.tr_pos), self.nnz)
 
 
 def nn_maxmin_workspace_bytes(n):
@@ -1167,6 +1217,73 @@ class Handle(DistCalls):
         Returns (out (B, 3) and grad (B, ntheta) as nn_loglik_grad, fisher (B, ntheta, ntheta) ndarray = the rows' sum, symmetric, info).
         Synchronous."""
         return self._nn_likelihood(NN_FISHER, kernel_id, x, thetas, idx, m, r, v, mu, var, score, fisher_rows, work)
+
+    # -- the nearest-neighbour factor as a preconditioner (include/fvgp_hip_nn.h, DESIGN 30) --------------------------------------
+    def nn_transpose(self, idx, m=None):
+        """the transposed lists of the device tensor idx (n, ld) int32, columns 0 .. m - 1 (default: all): built on the host
+        (nn_transpose_lists: a stable sort, once per neighbour structure) and uploaded.  Returns (tr_start (n + 1), tr_pos (max(nnz, 1)))
+        int64 device tensors and nnz; positions are i * ld + l with ld = idx.stride(0)."""
+        n, ld = idx.shape[0], idx.stride(0)
+        m = idx.shape[1] if m is None else int(m)
+        host = np.full((n, ld), -1, dtype=np.int64)
+        host[:, :m] = idx[:, :m].cpu().numpy()
+        start, pos = nn_transpose_lists(host, n)
+        dev = idx.device
+        tr_pos = self.torch.zeros(max(len(pos), 1), dtype=self.torch.int64, device=dev)
+        tr_pos[:len(pos)] = self.torch.as_tensor(pos, device=dev)
+        return self.torch.as_tensor(start, device=dev), tr_pos, len(pos)
+
+    def nn_factor(self, kernel_id, x, theta, idx, m, v, coef=None, dinv=None, transposed=None, work=None):
+        """fvgp_hip_nn_factor: the rows of the sparse inverse Cholesky factor W of K(x, x) + diag(v) over the lists idx[i][:m] at ONE
+        theta -- coef (n, ld = idx.stride(0)) and dinv (n), allocated here unless given (coef starts as zeros: its columns past m are
+        never written).  transposed = (tr_start, tr_pos, nnz) of nn_transpose, built here when None.  Returns (NNFactor, info): info 0, or
+        1 + the first row whose conditional variance is not positive.  Synchronous."""
+        t, tp, nt = _theta(theta)
+        n, d = x.shape
+        if idx.dim() != 2 or idx.stride(1) != 1 or idx.dtype != self.torch.int32 or idx.shape[0] < n or idx.shape[1] < m:
+            raise ValueError(f"nn_factor: idx must be an int32 (n, >= m) tensor with unit column stride, got {tuple(idx.shape)}")
+        ld = idx.stride(0)
+        if coef is None:
+            coef = self.zeros(n, ld)
+        if dinv is None:
+            dinv = self.empty(n)
+        if coef.stride(0) != ld or coef.stride(1) != 1:
+            raise ValueError(f"nn_factor: coef must have idx's leading dimension {ld}, got stride {coef.stride()}")
+        if work is None:
+            work = self.empty(max(1, nn_factor_workspace_bytes(n)) // 8)
+        info = ctypes.c_int64(0)
+        self._call("fvgp_hip_nn_factor", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(idx), ld, int(m), _ptr(v), _ptr(coef), ld,
+                   _ptr(dinv), _ptr(work), work.numel() * 8, ctypes.byref(info))
+        tr_start, tr_pos, nnz = self.nn_transpose(idx, m) if transposed is None else transposed
+        return NNFactor(idx, m, coef, dinv, tr_start, tr_pos, nnz), int(info.value)
+
+    def nn_precond_apply(self, factor, R, Z, s=None, work=None):
+        """fvgp_hip_nn_precond_apply: Z[:, :s] = W^T (W R[:, :s]) for the NNFactor `factor`, s <= PCG_MAX_RHS; R, Z (n, >= s) device
+        tensors.  Asynchronous."""
+        n = factor.dinv.shape[0]
+        s = int(R.shape[1] if s is None else s)
+        if work is None:
+            work = self.empty(max(2, nn_precond_apply_workspace_bytes(n) // 8))
+        self._call("fvgp_hip_nn_precond_apply", n, *factor._args(), _ptr(R), R.stride(0), s, _ptr(Z), Z.stride(0),
+                   _ptr(work), work.numel() * 8)
+
+    def pcg_nn(self, kernel_id, x, theta, vdiag, B, X, factor, s=None, warm=False, tol=1e-10, max_iter=1000, check_every=8,
+               max_restarts=3, work=None):
+        """fvgp_hip_pcg_nn: Handle.pcg with z = W^T W r of the NNFactor `factor` as the preconditioner; x, vdiag, B, X in the factor's
+        ordering.  Returns (iters, relres, status) as Handle.pcg does.  Synchronous."""
+        t, tp, nt = _theta(theta)
+        n, d = x.shape
+        s = int(B.shape[1] if s is None else s)
+        if work is None:
+            work = self.empty(max(2, pcg_nn_workspace_bytes(n) // 8))
+        iters = np.zeros(max(s, 1), dtype=np.int32)
+        status = np.zeros(max(s, 1), dtype=np.int32)
+        relres = np.zeros(max(s, 1), dtype=np.float64)
+        self._call("fvgp_hip_pcg_nn", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(vdiag), *factor._args(),
+                   _ptr(B), B.stride(0), s, _ptr(X), X.stride(0), int(bool(warm)), float(tol), int(max_iter),
+                   int(check_every), int(max_restarts), _ptr(work), work.numel() * 8,
+                   iters.ctypes.data_as(P_i), relres.ctypes.data_as(P_d), status.ctypes.data_as(P_i))
+        return iters[:s], relres[:s], status[:s]
 
     def posterior_prepare(self, L, n):
         """enqueue the inverted diagonal blocks the posterior's sweep substitutes with (fvgp_hip_posterior_prepare)"""

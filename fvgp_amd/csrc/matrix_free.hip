@@ -15,6 +15,7 @@
 #include "slice_sum.h"
 #include "pivot.h"
 #include "normal.h"
+#include "../../include/fvgp_hip_nn.h"
 #include <math.h>
 #include <string.h>
 
@@ -414,8 +415,80 @@ int pcg_precond(fvgp_handle *h, const double *G, int64_t ldg, int q, const doubl
     return 0;
 }
 
-struct PcgLayout { int64_t R, Z, P, AP, part1, state, mv, total, mv_doubles; PrecondLayout pre; };
-PcgLayout pcg_layout(int64_t n, int q) {
+// ------------------------------------------------------------------------------- the nearest-neighbour preconditioner
+// the sparse inverse Cholesky factor W of fvgp_hip_nn_factor and its transposed lists (include/fvgp_hip_nn.h): idx and coef (n, ld), row i
+// of W is coef[i][.] at the columns idx[i][.] and dinv[i] on the diagonal; bucket j of tr_pos holds the flat positions of column j's
+// entries in ascending row
+struct NnFactor {
+    const int *idx; const double *coef, *dinv; const int64_t *tr_start, *tr_pos;
+    long n, ld, nnz; int m;
+};
+
+// T = W R.  A row of the solver's vectors is PCG_LD doubles = 128 bytes: 16 lanes take a row, one column each, so that every wave
+// instruction reads four whole rows; the 16 lanes of a row read the same list entry and coefficient (one address, a broadcast)
+__global__ __launch_bounds__(256) void nn_gather_kernel(NnFactor f, const double *R, int s, double *T) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    const int c = (int)(e & 15);
+    const long i = e >> 4;
+    if (i >= f.n || c >= s) return;
+    const int *li = f.idx + i * f.ld;
+    const double *ci = f.coef + i * f.ld;
+    double acc = f.dinv[i] * R[i * PCG_LD + c];
+    for (int l = 0; l < f.m; ++l) {
+        const long j = li[l];
+        if (j >= 0 && j < f.n) acc = fma(ci[l], R[j * PCG_LD + c], acc);
+    }
+    T[i * PCG_LD + c] = acc;
+}
+
+// Z = W^T T and part0 = r.z per 256 rows, where pcg_apply_kernel leaves it.  Thread (g, c) of a workgroup takes the rows g, g + 16, .. of
+// its 256 and column c; a row walks its own bucket in ascending order and nothing else: the loop is bounded by the bucket's length (clipped
+// to the list), a position outside the factor is skipped, no workgroup waits for another.  r.z: the thread's rows by fma in ascending
+// order, then the tree over g
+__global__ __launch_bounds__(256) void nn_transpose_kernel(NnFactor f, const double *T, PcgVec a) {
+    const int tid = threadIdx.x, c = tid & 15, g = tid >> 4;
+    const long r0 = (long)blockIdx.x * 256, r1 = r0 + 256 < f.n ? r0 + 256 : f.n;
+    const int64_t npos = (int64_t)f.n * f.ld;
+    double rz = 0.0;
+    if (c < a.s)
+        for (long j = r0 + g; j < r1; j += 16) {
+            int64_t e0 = f.tr_start[j], e1 = f.tr_start[j + 1];
+            e0 = e0 < 0 ? 0 : e0; e1 = e1 > f.nnz ? f.nnz : e1;
+            double z = f.dinv[j] * T[j * PCG_LD + c];
+            for (int64_t e = e0; e < e1; ++e) {
+                const int64_t pos = f.tr_pos[e];
+                if (pos >= 0 && pos < npos) z = fma(f.coef[pos], T[(pos / f.ld) * PCG_LD + c], z);
+            }
+            a.Z[j * PCG_LD + c] = z;
+            rz = fma(a.R[j * PCG_LD + c], z, rz);
+        }
+    dot_block(rz, a.part0, tid, true);
+}
+
+// Z = W^T (W R) for the solver's own vectors, part0 = r.z: the two launches in stream order
+int nn_precond(fvgp_handle *h, const NnFactor &f, const PcgVec &a, double *T) {
+    HIPLAUNCH(nn_gather_kernel, dim3((unsigned)((f.n * PCG_LD + 255) / 256)), dim3(256), h->stream, f, (const double *)a.R, a.s, T);
+    HIPLAUNCH(nn_transpose_kernel, dim3((unsigned)((f.n + 255) / 256)), dim3(256), h->stream, f, (const double *)T, a);
+    return 0;
+}
+
+// the factor's arguments as the two entries take them, positions p0 .. p0 + 7 of the entry: 0, or minus the position of the first bad one
+int nn_factor_check(const char *who, int64_t n, const int *idx, int64_t ld, int m, const double *coef, const double *dinv,
+                    const int64_t *tr_start, const int64_t *tr_pos, int64_t nnz, int p0) {
+    if (!idx) return -p0;
+    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error(std::string(who) + ": 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -(p0 + 2); }
+    if (ld < m) return -(p0 + 1);
+    if (!coef) return -(p0 + 3);
+    if (!dinv) return -(p0 + 4);
+    if (!tr_start) return -(p0 + 5);
+    if (!tr_pos) return -(p0 + 6);
+    if (nnz < 0 || nnz > n * ld) { fvgp_set_error(std::string(who) + ": nnz outside 0 .. n ld"); return -(p0 + 7); }
+    return 0;
+}
+
+// nn: the (n, PCG_LD) intermediate T of the nearest-neighbour preconditioner behind everything else (the other offsets do not move)
+struct PcgLayout { int64_t R, Z, P, AP, part1, state, mv, total, mv_doubles, nnT; PrecondLayout pre; };
+PcgLayout pcg_layout(int64_t n, int q, bool nn = false) {
     PcgLayout l;
     l.mv_doubles = mv_auto_split(n, n) > 1 ? mv_split_doubles(n, n, MV_MAXS) : 0;
     int64_t o = 0;
@@ -424,6 +497,7 @@ PcgLayout pcg_layout(int64_t n, int q) {
     l.part1 = o; o += (n + 255) / 256 * PCG_LD;
     l.state = o; o += even_up((int64_t)((sizeof(PcgState) + 7) / 8));
     l.mv = o; o += l.mv_doubles;
+    l.nnT = o; o += nn ? n * PCG_LD : 0;
     l.total = o;
     return l;
 }
@@ -443,9 +517,10 @@ struct PcgCall {
     const double *C; int64_t ldc; const double *B; int64_t ldb; int s; double *X; int64_t ldx; int warm; double tol;
     int max_iter, check_every, max_restarts; double *work; int64_t work_bytes; int *iters_host; double *relres_host; int *status_host;
     int L; double *alpha_host, *beta_host; int *steps_host; double *rho0_host;
+    const NnFactor *nn = nullptr;            // fvgp_hip_pcg_nn: the sparse factor in the place of (G, C); its entry has checked it
 };
 
-// the one driver of fvgp_hip_pcg (L == 0) and fvgp_hip_pcg_lanczos
+// the one driver of fvgp_hip_pcg (L == 0), fvgp_hip_pcg_lanczos and fvgp_hip_pcg_nn (p.nn: only the preconditioner's launches differ)
 int pcg_driver(fvgp_handle *h, PcgCall p) {
     if (!h) return -1;
     if (!kernel_id_known(p.kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
@@ -471,8 +546,9 @@ int pcg_driver(fvgp_handle *h, PcgCall p) {
     if (p.max_restarts < 0) return -23;
     if (!p.work || ((uintptr_t)p.work & 15)) { fvgp_set_error("pcg: work must be 16-byte aligned"); return -24; }
     if (p.L < 0 || p.L > FVGP_LANCZOS_MAX_STEPS) { fvgp_set_error("pcg_lanczos: lanczos_steps outside 0 .. FVGP_LANCZOS_MAX_STEPS"); return -29; }
-    if (p.work_bytes < (pcg_layout(p.n, p.q).total + pcg_rec_doubles(p.L)) * (int64_t)sizeof(double)) {
-        fvgp_set_error(p.L ? "pcg_lanczos: work smaller than fvgp_hip_pcg_lanczos_workspace_bytes(n, rank, lanczos_steps)"
+    if (p.work_bytes < (pcg_layout(p.n, p.q, p.nn).total + pcg_rec_doubles(p.L)) * (int64_t)sizeof(double)) {
+        fvgp_set_error(p.nn ? "pcg_nn: work smaller than fvgp_hip_pcg_nn_workspace_bytes(n)"
+                       : p.L ? "pcg_lanczos: work smaller than fvgp_hip_pcg_lanczos_workspace_bytes(n, rank, lanczos_steps)"
                          : "pcg: work smaller than fvgp_hip_pcg_workspace_bytes(n, rank)");
         return -25;
     }
@@ -489,7 +565,7 @@ int pcg_driver(fvgp_handle *h, PcgCall p) {
     KmatDesc k{};
     rc = kmat_desc_from_theta(p.kernel_id, p.d, p.theta, p.ntheta, &k); if (rc) return rc;
     k.x1 = p.x; k.n1 = p.n; k.x2 = p.x; k.n2 = p.n; k.vdiag = p.vdiag;
-    const PcgLayout lay = pcg_layout(p.n, p.q);
+    const PcgLayout lay = pcg_layout(p.n, p.q, p.nn);
     PcgRec rec{};                                                 // L == 0: every pointer NULL, the scalar kernel records nothing
     if (p.L > 0) {
         double *rw = p.work + lay.total;
@@ -517,7 +593,9 @@ int pcg_driver(fvgp_handle *h, PcgCall p) {
         HIPLAUNCH(pcg_scalar_kernel, dim3(1), dim3(256), st, v, nb, mode, p.tol, p.max_iter, rec);
         return 0;
     };
-    auto precond = [&]() -> int { return pcg_precond(h, p.G, p.ldg, p.q, p.C, p.ldc, a, p.work, lay.pre); };
+    auto precond = [&]() -> int {
+        return p.nn ? nn_precond(h, *p.nn, a, p.work + lay.nnT) : pcg_precond(h, p.G, p.ldg, p.q, p.C, p.ldc, a, p.work, lay.pre);
+    };
     PcgVec a1 = a; a1.part1 = a.part0;                            // (a scalar step that reads one partial array)
 
     if (p.warm) {
@@ -706,6 +784,58 @@ int fvgp_hip_pcg_lanczos(fvgp_handle *h, int kernel_id, const double *x, int64_t
     return pcg_driver(h, PcgCall{kernel_id, x, n, d, theta, ntheta, vdiag, G, ldg, q, C, ldc, B, ldb, s, X, ldx, warm, tol, max_iter, check_every,
                                  max_restarts, work, work_bytes, iters_host, relres_host, status_host, lanczos_steps, alpha_host, beta_host,
                                  steps_host, rho0_host});
+}
+
+int64_t fvgp_hip_pcg_nn_workspace_bytes(int64_t n) {
+    if (n < 1) return -1;
+    return pcg_layout(n, 0, true).total * (int64_t)sizeof(double);
+}
+
+int fvgp_hip_pcg_nn(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta, int ntheta,
+                    const double *vdiag, const int *idx, int64_t ld, int m, const double *coef, const double *dinv,
+                    const int64_t *tr_start, const int64_t *tr_pos, int64_t nnz,
+                    const double *B, int64_t ldb, int s, double *X, int64_t ldx, int warm,
+                    double tol, int max_iter, int check_every, int max_restarts,
+                    double *work, int64_t work_bytes, int *iters_host, double *relres_host, int *status_host) {
+    if (!h) return -1;
+    if (n >= 1) { const int rc = nn_factor_check("pcg_nn", n, idx, ld, m, coef, dinv, tr_start, tr_pos, nnz, 9); if (rc) return rc; }
+    const NnFactor f{idx, coef, dinv, tr_start, tr_pos, (long)n, (long)ld, (long)nnz, m};
+    const int rc = pcg_driver(h, PcgCall{kernel_id, x, n, d, theta, ntheta, vdiag, nullptr, 0, 0, nullptr, 0, B, ldb, s, X, ldx, warm, tol, max_iter,
+                                         check_every, max_restarts, work, work_bytes, iters_host, relres_host, status_host, 0, nullptr, nullptr,
+                                         nullptr, nullptr, &f});
+    // the driver numbers its errors by the positions of fvgp_hip_pcg: from B on this entry's are three further
+    return rc <= -14 && rc > -1000 ? rc - 3 : rc;
+}
+
+int64_t fvgp_hip_nn_precond_apply_workspace_bytes(int64_t n) {
+    if (n < 1) return -1;
+    return (3 * n * PCG_LD + (n + 255) / 256 * PCG_LD) * (int64_t)sizeof(double);
+}
+
+int fvgp_hip_nn_precond_apply(fvgp_handle *h, int64_t n, const int *idx, int64_t ld, int m, const double *coef, const double *dinv,
+                              const int64_t *tr_start, const int64_t *tr_pos, int64_t nnz, const double *R, int64_t ldr, int s,
+                              double *Z, int64_t ldz, double *work, int64_t work_bytes) {
+    if (!h) return -1;
+    if (n < 1 || n > 0x7fffffffLL) return -2;
+    int rc = nn_factor_check("nn_precond_apply", n, idx, ld, m, coef, dinv, tr_start, tr_pos, nnz, 3); if (rc) return rc;
+    if (!R) return -11;
+    if (s < 1 || s > FVGP_PCG_MAX_RHS) { fvgp_set_error("nn_precond_apply: 1 .. FVGP_PCG_MAX_RHS columns per call"); return -13; }
+    if (ldr < s) return -12;
+    if (!Z) return -14;
+    if (ldz < s) return -15;
+    if (!work || ((uintptr_t)work & 15)) { fvgp_set_error("nn_precond_apply: work must be 16-byte aligned"); return -16; }
+    if (work_bytes < fvgp_hip_nn_precond_apply_workspace_bytes(n)) {
+        fvgp_set_error("nn_precond_apply: work smaller than fvgp_hip_nn_precond_apply_workspace_bytes(n)"); return -17;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    const NnFactor f{idx, coef, dinv, tr_start, tr_pos, (long)n, (long)ld, (long)nnz, m};
+    PcgVec a{};
+    a.R = work; a.Z = work + n * PCG_LD; a.part0 = work + 3 * n * PCG_LD; a.n = n; a.s = s;
+    const dim3 gcopy((unsigned)((n * PCG_LD + 255) / 256));
+    HIPLAUNCH(mf_copy_cols_kernel, gcopy, dim3(256), h->stream, R, (long)ldr, a.R, (long)PCG_LD, (long)n, s);
+    rc = nn_precond(h, f, a, work + 2 * n * PCG_LD); if (rc) return rc;
+    HIPLAUNCH(mf_copy_cols_kernel, gcopy, dim3(256), h->stream, (const double *)a.Z, (long)PCG_LD, Z, (long)ldz, (long)n, s);
+    return 0;
 }
 
 int fvgp_hip_precond_probes(fvgp_handle *h, uint64_t seed, uint64_t stream, int64_t col0, const double *G, int64_t ldg, int q,

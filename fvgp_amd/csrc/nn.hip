@@ -41,13 +41,15 @@ __device__ __forceinline__ double lane_value(const double v, const int j) {
 }
 
 // the level of a likelihood call, and what nn_cond_kernel computes beside mu and var: nothing, every row's score, or the score and the
-// row's Fisher information
-constexpr int NN_VALUE = 0, NN_GRAD = 1, NN_FISHER = 2;
+// row's Fisher information.  NN_FACTOR is no likelihood level: the kernel stops behind the backward pass and writes the row of the sparse
+// inverse Cholesky factor (fvgp_hip_nn_factor)
+constexpr int NN_VALUE = 0, NN_GRAD = 1, NN_FISHER = 2, NN_FACTOR = 3;
 
 // f(std::integral_constant<int, MODE>) for the level
 template <class F>
 inline void dispatch_mode(int level, F &&f) {
-    if (level == NN_FISHER) f(std::integral_constant<int, NN_FISHER>{});
+    if (level == NN_FACTOR) f(std::integral_constant<int, NN_FACTOR>{});
+    else if (level == NN_FISHER) f(std::integral_constant<int, NN_FISHER>{});
     else if (level == NN_GRAD) f(std::integral_constant<int, NN_GRAD>{});
     else f(std::integral_constant<int, NN_VALUE>{});
 }
@@ -62,6 +64,7 @@ struct NcArgs {
     double *score;                                 // GRAD: (B, nq, nth), the row's d log p(y_i | y_c) / d theta
     int nth, iso;                                  // GRAD: columns of score; one length scale for every dimension
     double *fisher;                                // NN_FISHER: (B, nq, nth (nth + 1) / 2), the row's term of the Fisher information, packed lower
+    double *coef, *dinv; long ldc;                 // NN_FACTOR: (nq, ldc) and (nq), the row of W; r and mu are NULL there and var is d
 };
 
 // GRAD: the likelihood's conditionals (xq == xr, s == v) and each row's score.  Everything up to mu and var is the value kernel's code,
@@ -73,6 +76,9 @@ struct NcArgs {
 // score and from the same factor.  With dS = dSigma / d theta_h:  t_h = (dS b) on the neighbours (one full-row sweep over the block's
 // entries: the lanes the score's sweep masks take part), delta_h = b^T dS b = d var / d theta_h, u_h = L^-1 t_h (every right-hand side in
 // one forward pass), F_i[h][k] = u_h^T u_k / var + 1/2 delta_h delta_k / var^2.  It reads x, v, theta and the lists, never r.
+//
+// NN_FACTOR: the value path (xq == xr, s == v) and the backward pass for a = A^-1 k, then the row of the sparse inverse
+// Cholesky factor, dinv = 1 / sqrt(var) and coef = -(a dinv); it stops there, never reads r and writes no mu (var goes to the workspace).
 template <int KIND, int D, int M, int MODE>    // D == 0: runtime dimension; M: the padded block, m <= M
 __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
     constexpr bool GRAD = MODE >= NN_GRAD;
@@ -98,7 +104,7 @@ __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
 #pragma unroll
     for (int k = 0; k < DD; ++k) u[k] = k < d ? a.xr[cc * d + k] : 0.0;
     const double vc = valid ? a.v[cc] : 0.0;
-    double tz = valid ? a.r[cc] : 0.0;             // becomes z_l
+    double tz = (MODE != NN_FACTOR && valid) ? a.r[cc] : 0.0;      // becomes z_l
     double tw = 0.0;                               // k_l = k(x_c, x_i), becomes w_l
     {
         double r2 = 0.0;
@@ -147,7 +153,7 @@ __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
     if (lane == 0) {
         double kxx = radial<KIND>(0.0, sig);
         if (a.s) kxx += a.s[row];
-        a.mu[b * a.nq + row] = fail ? NAN : mu;
+        if (MODE != NN_FACTOR) a.mu[b * a.nq + row] = fail ? NAN : mu;
         a.var[b * a.nq + row] = fail ? NAN : kxx - ww;
     }
     if constexpr (GRAD) {
@@ -162,6 +168,12 @@ __global__ __launch_bounds__(64 * NN_WAVES) void nn_cond_kernel(NcArgs a) {
         }
         double kxx = radial<KIND>(0.0, sig);
         if (a.s) kxx += a.s[row];
+        if constexpr (MODE == NN_FACTOR) {
+            const double di = 1.0 / sqrt(kxx - lane_value(ww, 0));
+            if (lane < a.m) a.coef[row * a.ldc + lane] = fail ? NAN : valid ? -(ta * di) : 0.0;
+            if (lane == 0) a.dinv[row] = fail ? NAN : di;
+            return;
+        }
         const double dv = kxx - lane_value(ww, 0), e = a.r[row] - lane_value(mu, 0);
         const double ed = e / dv, c2 = 0.5 * (ed * ed - 1.0 / dv);
         // b = (-a, 1), q = (e / d) (beta, 0) + c2 b: this lane's entries; the entry of x_i itself is (1, c2)
@@ -402,7 +414,8 @@ NnLayout nn_layout(int level, int64_t n, int B, int ntheta) {
 // score (B, nq, ntheta) from NN_GRAD and fisher (B, nq, P) at NN_FISHER, else NULL (the likelihood's structure only: xq == xr, s == v)
 int nn_run_conditionals(fvgp_handle *h, int level, int kernel_id, const double *xq, int64_t nq, const double *xr, int64_t nr, int d,
                         const double *thetas, int ntheta, int B, const int *idx, int64_t ld, int m, const double *r, const double *v,
-                        const double *s, double *mu, double *var, double *work, double *score, double *fisher) {
+                        const double *s, double *mu, double *var, double *work, double *score, double *fisher,
+                        double *coef = nullptr, int64_t ldc = 0, double *dinv = nullptr) {
     std::vector<double> tab((size_t)B * NN_TAB);
     KmatDesc k{};
     for (int b = 0; b < B; ++b) {
@@ -419,6 +432,7 @@ int nn_run_conditionals(fvgp_handle *h, int level, int kernel_id, const double *
     a.nq = nq; a.nr = nr; a.ld = ld; a.d = d; a.m = m;
     a.score = score; a.nth = ntheta; a.iso = KERNEL_FAMILY[kernel_id].iso ? 1 : 0;
     a.fisher = fisher;
+    a.coef = coef; a.ldc = ldc; a.dinv = dinv;
     const dim3 grid((unsigned)((nq + NN_WAVES - 1) / NN_WAVES), (unsigned)B), block(64 * NN_WAVES);
     dispatch_kind_dim(k.kind, d, [&](auto KIND, auto D) {
         dispatch_pad(m, [&](auto M) {
@@ -549,6 +563,42 @@ int fvgp_hip_nn_conditionals(fvgp_handle *h, int kernel_id, const double *xq, in
     if (!info_host) return -21;
     HIPCHK(hipSetDevice(h->device));
     rc = nn_run_conditionals(h, NN_VALUE, kernel_id, xq, nq, xr, nr, d, thetas_host, ntheta, B, idx, ld, m, r, v, s_or_null, mu, var, work, nullptr, nullptr);
+    if (rc) return rc;
+    long long info = 0;
+    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *info_host = info;
+    return 0;
+}
+
+// the factor's work: the conditionals' (info word, theta table of one vector), then the n conditional variances
+int64_t fvgp_hip_nn_factor_workspace_bytes(int64_t n) {
+    if (n < 1) return -1;
+    return (nn_layout(NN_VALUE, n, 1, 0).out + n) * (int64_t)sizeof(double);
+}
+
+int fvgp_hip_nn_factor(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta_host, int ntheta,
+                       const int *idx, int64_t ld, int m, const double *v, double *coef, int64_t ldc, double *dinv,
+                       double *work, int64_t work_bytes, int64_t *info_host) {
+    if (!h) return -1;
+    if (!kernel_id_known(kernel_id)) { fvgp_set_error("unknown kernel id"); return -2; }
+    if (!x) return -3;
+    if (n < 1 || n > 0x7fffffffLL) return -4;
+    int rc = check_kernel_args(kernel_id, d, theta_host, ntheta, 5, 6, 7); if (rc) return rc;
+    if (!idx) return -8;
+    if (m < 1 || m > FVGP_NN_MAX_NEIGHBORS) { fvgp_set_error("nn_factor: 1 .. FVGP_NN_MAX_NEIGHBORS neighbours"); return -10; }
+    if (ld < m) return -9;
+    if (!v) return -11;
+    if (!coef) return -12;
+    if (ldc < m) return -13;
+    if (!dinv) return -14;
+    if (!work || ((uintptr_t)work & 7)) return -15;
+    if (work_bytes < fvgp_hip_nn_factor_workspace_bytes(n)) { fvgp_set_error("nn_factor: work smaller than fvgp_hip_nn_factor_workspace_bytes(n)"); return -16; }
+    if (!info_host) return -17;
+    HIPCHK(hipSetDevice(h->device));
+    double *dvar = work + nn_layout(NN_VALUE, n, 1, 0).out;
+    rc = nn_run_conditionals(h, NN_FACTOR, kernel_id, x, n, x, n, d, theta_host, ntheta, 1, idx, ld, m, nullptr, v, v, nullptr, dvar, work,
+                             nullptr, nullptr, coef, ldc, dinv);
     if (rc) return rc;
     long long info = 0;
     HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));

@@ -1,6 +1,6 @@
 // The neighbour geometry of the nearest-neighbour path, written once for the brute search (nn_search.hip), the maxmin ordering
 // (nn_order.hip) and the cell-grid search (nn_grid.hip): the scaled squared distance, the sorted top-m list of a lane, the dimension and
-// list-size dispatch, and the host's check of the scales (DESIGN 29).  What the path promises -- the grid returns the brute lists element
+// list-size dispatch, and the host's check of the scales (DESIGN 30).  What the path promises -- the grid returns the brute lists element
 // for element, the ordering's distances are the search's -- holds because all three call nn_dist2 and take 1 / scale from nn_scales.
 #pragma once
 #include "common.h"

@@ -20,6 +20,13 @@ z_c ~ N(0, M) (fvgp_hip_precond_probes):   log det A = log det M + mean_c rho_0 
 preconditioned CG on A u_c = z_c records (fvgp_hip_pcg_lanczos), log det M in closed form;   tr(A^-1 dK_j) = mean_c u_c^T dK_j (M^-1 z_c)
 (fvgp_hip_precond_apply, fvgp_hip_kgrad_form).  Only the kernel's own hyperparameters get a gradient: the noise is numbers here.  The
 exact Hessian stays with the dense GP.
+
+A second preconditioner, args={"preconditioner": "vecchia"}: the sparse inverse Cholesky factor W of the nearest-neighbour
+approximation, (K + V)^-1 ~ W^T W (fvgp_hip_nn_factor, fvgp_hip_pcg_nn).  It is local where the pivoted Cholesky is global: its iteration
+count stays flat once the data outnumber what q columns can span, and it loses on small, globally smooth problems, which is why "pchol"
+stays the default.  The object then owns a VecchiaGP over the same data for the ordering and the neighbour lists and holds its rows in
+that ordering; the caller's order shows in solve and in x_data / y_data / noise_variances alone.  The stochastic likelihood needs probes
+z ~ N(0, M), a sparse triangular solve that is not built: those names raise NotImplementedError under this preconditioner.
 """
 import warnings
 
@@ -45,9 +52,15 @@ class MatrixFreeGP:
     residual), "max_iter" (1000), "check_every" (8), "max_restarts" (3), "pchol_tol" (1e-12), "z_max_bytes"; for the stochastic
     likelihood "probe_tol" (1e-6: the relative residual of the probe solves, a default and not a measured optimum; alpha keeps "tol"),
     "lanczos_steps" (64: CG coefficients recorded per probe) and "stochastic_likelihood" (False; True lets the fvgp.GP method names
-    log_likelihood, neg_log_likelihood, neg_log_likelihood_gradient and train return the estimates)."""
+    log_likelihood, neg_log_likelihood, neg_log_likelihood_gradient and train return the estimates).
 
-    def __init__(self, x_data, y_data, hyperparameters, noise_variances=None, kernel_function="matern32_ard", args=None):
+    "preconditioner": "pchol" (default: the rank-q pivoted Cholesky above) or "vecchia": the nearest-neighbour factor, with
+    "precond_neighbors" (32; 1 .. 64), "precond_ordering" ("random" (default), "maxmin", "given" or a permutation), "seed" (0),
+    "maxmin_points", "neighbor_scales" and "neighbor_search" as VecchiaGP takes them (its checks and messages).  The lists and their
+    transpose are built once per data set (the transpose on the host: a stable sort); set_hyperparameters keeps them and recomputes the
+    factor alone, lazily.  neighbors() and preconditioner_factor() show the structure."""
+
+    def __init__(self, x_data, y_data, hyperparameters, noise_variances=None, kernel_function="matern32_ard", args=None, _vecchia=None):
         native = _kernels.resolve(kernel_function) if not callable(kernel_function) or isinstance(kernel_function, _kernels.NativeKernel) \
             else None
         if native is None:
@@ -58,6 +71,11 @@ class MatrixFreeGP:
         assert len(x_data) == len(y_data), "x_data and y_data do not have the same lengths."
         self._native = native
         self.args = {} if args is None else dict(args)
+        self.preconditioner = self.args.get("preconditioner", "pchol")
+        if self.preconditioner not in ("pchol", "vecchia"):
+            raise ValueError(f"args['preconditioner'] must be 'pchol' or 'vecchia', got {self.preconditioner!r}")
+        self._vecchia_given = _vecchia          # VecchiaGP.matrix_free: the object whose ordering and lists this one shares
+        self._init_hps = hyperparameters
         self.precond_rank = int(self.args.get("precond_rank", 128))
         assert 0 <= self.precond_rank <= _lib.PCG_MAX_RANK, f"precond_rank must lie in 0 .. {_lib.PCG_MAX_RANK}"
         self.tol = float(self.args.get("tol", 1e-10))
@@ -95,11 +113,78 @@ class MatrixFreeGP:
         self.noise_variances = noise_variances
         self._V = np.ascontiguousarray(V)
         self._m = float(np.mean(self.y_data))
-        self._x_dev, self._V_dev = H.to_device(self.x_data), H.to_device(self._V)
-        self._ym_dev = H.to_device((self.y_data - self._m)[:, None])
-        self._G = self._C = None
+        self._G = self._C = self._W = None
+        if self.preconditioner == "vecchia":
+            self._set_structure()
+        else:
+            self._x_dev, self._V_dev = H.to_device(self.x_data), H.to_device(self._V)
+            self._ym_dev = H.to_device((self.y_data - self._m)[:, None])
         self._scratch = {}
         self._rank = 0
+
+    def _set_structure(self):
+        """the "vecchia" preconditioner's structure for the data as they are: a VecchiaGP over them (the one given by
+        VecchiaGP.matrix_free the first time, else one of this object's own) lends its ordering, its ordered device arrays and its
+        lists; the transposed lists are built here, once"""
+        from .gp_vecchia import VecchiaGP
+        nn, a = self._vecchia_given, self.args
+        if nn is None:
+            hps = getattr(self, "_hps", None)
+            kw = {k: a[k] for k in ("maxmin_points", "neighbor_scales", "neighbor_search") if k in a}
+            nn = VecchiaGP(self.x_data, self.y_data, self._init_hps if hps is None else hps, noise_variances=self._V,
+                           kernel_function=self._native, n_neighbors=a.get("precond_neighbors", 32),
+                           ordering=a.get("precond_ordering", "random"), seed=a.get("seed", 0), args=kw)
+        else:
+            # (an update of this object's data makes its own structure by the given object's rules)
+            self.args.update({"precond_neighbors": nn.n_neighbors, "precond_ordering": nn._ordering_rule[0], "seed": nn._ordering_rule[1]})
+            self.args.update({k: nn.args[k] for k in ("maxmin_points", "neighbor_scales", "neighbor_search") if k in nn.args})
+            self._vecchia_given = None
+        if not isinstance(self.args.get("precond_ordering", "random"), str):
+            self.args["precond_ordering"] = "given"     # (a permutation orders the data it came with; later data come as given)
+        self._nn = nn
+        self.precond_neighbors = nn.n_neighbors
+        self.ordering = nn.ordering
+        self._x_dev, self._V_dev, self._ym_dev, self._idx = nn._x_dev, nn._V_dev, nn._r_dev[:, None], nn._idx
+        self._perm_dev = self._H.torch.as_tensor(self.ordering, device=self._x_dev.device)
+        self._transposed = self._H.nn_transpose(self._idx, self.precond_neighbors)
+
+    def neighbors(self):
+        """("vecchia" preconditioner) (N, m) int64: row i lists the neighbours of the caller's data point i as the caller's indices,
+        nearest first, -1 where the ordering leaves fewer than m earlier points"""
+        self._vecchia_only("neighbors")
+        idx = self._idx.cpu().numpy().astype(np.int64)
+        out = np.full_like(idx, -1)
+        out[self.ordering] = np.where(idx >= 0, self.ordering[np.clip(idx, 0, None)], -1)
+        return out
+
+    def preconditioner_factor(self):
+        """("vecchia" preconditioner) the _lib.NNFactor at the current hyperparameters, rows in the ordering: built once per
+        hyperparameter vector; the lists and their transpose are those of the data"""
+        self._vecchia_only("preconditioner_factor")
+        if self._W is None:
+            H = self._H
+            self._W, info = H.nn_factor(self._native.kernel_id, self._x_dev, self._hps, self._idx, self.precond_neighbors, self._V_dev,
+                                        transposed=self._transposed)
+            if info:
+                self._W = None
+                raise NonPositiveDefiniteError(
+                    f"the nearest-neighbour preconditioner: the conditional of data point {int(self.ordering[int(info) - 1])} is not "
+                    f"positive definite in double precision -- its {self.precond_neighbors} x {self.precond_neighbors} neighbour block "
+                    "K + V or its conditional variance has a pivot that is not positive; duplicated points need positive noise, or "
+                    "rethink the hyperparameters")
+        return self._W
+
+    def _vecchia_only(self, what):
+        if self.preconditioner != "vecchia":
+            raise NotImplementedError(f"{what} belongs to args={{'preconditioner': 'vecchia'}}: the pivoted-Cholesky preconditioner has "
+                                      "no neighbour lists")
+
+    def _no_probes(self, what):
+        if self.preconditioner == "vecchia":
+            raise NotImplementedError(
+                f"{what}: the stochastic likelihood draws probes z ~ N(0, M) from the preconditioner, which for the nearest-neighbour "
+                "factor is a sparse triangular solve that is not built.  Use preconditioner=\"pchol\" for the estimates, or VecchiaGP, "
+                "whose deterministic likelihood (log_likelihood, neg_log_likelihood_and_gradient, train) is built on the same factor")
 
     @property
     def hyperparameters(self):
@@ -113,7 +198,7 @@ class MatrixFreeGP:
         assert hps.shape == (self._native.n_hyperparameters(self.index_set_dim),), "wrong number of hyperparameters for this kernel"
         self._hps = hps
         self._alpha = self._alpha_info = None
-        self._G = self._C = None
+        self._G = self._C = self._W = None
 
     def _build_preconditioner(self, hps):
         """(G, q, C) at hps: the pivoted Cholesky of K and the factor of I + G V^-1 G^T; nothing is kept"""
@@ -152,8 +237,13 @@ class MatrixFreeGP:
         """one solver call of s <= 16 columns; at = (hps, G, q, C) solves at other hyperparameters than the object's; lanczos_steps > 0
         also returns the records (alpha, beta, steps, rho0)"""
         H, n = self._H, self.point_number
-        hps, G, q, C = at if at is not None else (self._hps,) + self._preconditioner()
         tol = self.tol if tol is None else tol
+        if self.preconditioner == "vecchia":
+            assert at is None and not lanczos_steps, "the nearest-neighbour preconditioner serves the plain solves at the object's hyperparameters"
+            work = self._buffer("pcg", _lib.pcg_nn_workspace_bytes(n) // 8)
+            return H.pcg_nn(self._native.kernel_id, self._x_dev, self._hps, self._V_dev, B, X, self.preconditioner_factor(), s=s, warm=warm,
+                            tol=tol, max_iter=self.max_iter, check_every=self.check_every, max_restarts=self.max_restarts, work=work)
+        hps, G, q, C = at if at is not None else (self._hps,) + self._preconditioner()
         kw = dict(G=G, q=q, C=C, s=s, warm=warm, tol=tol, max_iter=self.max_iter, check_every=self.check_every,
                   max_restarts=self.max_restarts)
         if lanczos_steps:
@@ -189,10 +279,16 @@ class MatrixFreeGP:
         """(K + V)^-1 b for b (n,) or (n, c); the prediction state (alpha) is not touched"""
         b = np.asarray(b, dtype=np.float64)
         one = b.ndim == 1
-        B = self._H.to_device(b.reshape(self.point_number, -1))
+        b = b.reshape(self.point_number, -1)
+        ordered = self.preconditioner == "vecchia"      # (the rows are held in the ordering: b goes in permuted, x comes out permuted)
+        B = self._H.to_device(b[self.ordering] if ordered else b)
         X = self._H.empty(*B.shape)
         its, res, ok = self._solve_device(B, X)
         x = self._H.to_host(X)
+        if ordered:
+            xo = x
+            x = np.empty_like(xo)
+            x[self.ordering] = xo
         return {"x": x[:, 0].copy() if one else x, "iterations": its, "relative_residual": res, "converged": bool(np.all(ok))}
 
     def _ensure_alpha(self, warm_from=None):
@@ -280,6 +376,9 @@ class MatrixFreeGP:
         with zeros"""
         assert isinstance(x_new, np.ndarray) and np.ndim(x_new) == 2 and isinstance(y_new, np.ndarray) and np.ndim(y_new) == 1
         old = self._alpha if append else None
+        if old is not None and self.preconditioner == "vecchia":
+            old = self._H.torch.empty_like(old)
+            old[self._perm_dev] = self._alpha           # (the old alpha in the caller's order)
         if append:
             if (self.noise_variances is None) != (noise_variances_new is None):
                 raise Exception("noise_variances_new must be given exactly when the object was built with noise_variances")
@@ -291,6 +390,10 @@ class MatrixFreeGP:
         self._alpha = self._alpha_info = None
         if old is not None:
             # (the prior mean moved with the data: the old alpha still nearly solves the old rows, which is all a start needs)
+            if self.preconditioner == "vecchia":        # (into the new ordering, the new rows zero)
+                full = self._H.zeros(self.point_number, 1)
+                full[:old.shape[0]] = old
+                old = full[self._perm_dev]
             self._ensure_alpha(warm_from=old)
 
     # ---- the stochastic likelihood -----------------------------------------------------------------------------------
@@ -317,6 +420,7 @@ class MatrixFreeGP:
         "neg_gradient" over the kernel's own hyperparameters, d(-log L)/dtheta_j = -1/2 alpha^T dK_j alpha + 1/2 tr((K + V)^-1 dK_j), and
         "neg_gradient_std_error": half the spread of the trace over groups of 4 probes (one fvgp_hip_kgrad_form call each).  The same
         (hyperparameters, n_probes, seed) returns the same bits: the probes are a pure function of the seed."""
+        self._no_probes("log_likelihood_estimate")
         H, n, kid = self._H, self.point_number, self._native.kernel_id
         n_probes = int(n_probes)
         assert n_probes >= 1, "n_probes must be at least 1"
@@ -381,15 +485,19 @@ class MatrixFreeGP:
         return out
 
     def stochastic_log_likelihood(self, hyperparameters=None, n_probes=16, seed=0):
+        self._no_probes("stochastic_log_likelihood")
         return self.log_likelihood_estimate(hyperparameters, n_probes, seed)["log_likelihood"]
 
     def stochastic_neg_log_likelihood(self, hyperparameters=None, n_probes=16, seed=0):
+        self._no_probes("stochastic_neg_log_likelihood")
         return -self.log_likelihood_estimate(hyperparameters, n_probes, seed)["log_likelihood"]
 
     def stochastic_neg_log_likelihood_gradient(self, hyperparameters=None, n_probes=16, seed=0):
+        self._no_probes("stochastic_neg_log_likelihood_gradient")
         return self.log_likelihood_estimate(hyperparameters, n_probes, seed, gradient=True)["neg_gradient"]
 
     def stochastic_neg_log_likelihood_and_gradient(self, hyperparameters=None, n_probes=16, seed=0):
+        self._no_probes("stochastic_neg_log_likelihood_and_gradient")
         e = self.log_likelihood_estimate(hyperparameters, n_probes, seed, gradient=True)
         return -e["log_likelihood"], e["neg_gradient"]
 
@@ -398,6 +506,7 @@ class MatrixFreeGP:
         """Adam (gp_training.adam_optimize) on the estimated negative log-likelihood with the SAME seed at every step -- common random
         numbers: the objective is then a deterministic function of theta -- every iterate clipped into hyperparameter_bounds (H, 2).
         Ends with set_hyperparameters(theta) and returns (theta, history)."""
+        self._no_probes("train_stochastic")
         bounds = np.asarray(hyperparameter_bounds, dtype=np.float64)
         assert bounds.ndim == 2 and bounds.shape == (len(self._hps), 2), "wrong bounds format"
         theta0 = np.array(self._hps if init_hyperparameters is None else init_hyperparameters, dtype=np.float64)

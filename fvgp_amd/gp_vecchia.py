@@ -511,6 +511,21 @@ class VecchiaGP:
         self._build_grid()
         self._idx = self._H.torch.cat([old_idx, self._search(self._x_dev[n_old:], n_old)], dim=0)
 
+    # ---- the exact answer beside the approximation ------------------------------------------------------------------------------------
+    def matrix_free(self, args=None):
+        """A MatrixFreeGP over the same data, kernel and CURRENT hyperparameters whose conjugate gradients are preconditioned by this
+        object's own factor (args["preconditioner"] = "vecchia"): it shares this object's ordering, ordered device arrays and
+        neighbour lists -- no second search -- and solves with the exact K + V.  args: MatrixFreeGP's other ones ("tol", "max_iter", ..)."""
+        from .gp_matrix_free import MatrixFreeGP
+        args = dict(args or {})
+        if args.setdefault("preconditioner", "vecchia") != "vecchia":
+            raise ValueError("VecchiaGP.matrix_free preconditions with this object's factor: args['preconditioner'] is 'vecchia' here; "
+                             "MatrixFreeGP(...) itself takes 'pchol'")
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")       # (the noise rule's warning was given when this object was built)
+            return MatrixFreeGP(self.x_data, self.y_data, self._hps.copy(), noise_variances=self.noise_variances, kernel_function=self._native,
+                                args=args, _vecchia=self)
+
     # ---- training ----------------------------------------------------------------------------------------------------------------
     def neg_log_likelihood_gradient(self, hyperparameters=None, component=0):
         """with args={"likelihood_gradient": True}: the exact gradient (H,) of neg_log_likelihood"""

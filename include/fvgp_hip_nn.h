@@ -194,6 +194,79 @@ int fvgp_hip_nn_grid_build(fvgp_handle *h, const double *xr, int64_t nr, int d, 
 int fvgp_hip_nn_grid_search(fvgp_handle *h, const double *xq, int64_t nq, const double *xr, int64_t nr, int d, int m, int64_t c0,
                             const double *info_host, const void *grid_dev, int *idx_out, int64_t ld);
 
+/* ---- the nearest-neighbour factor as a preconditioner of the matrix-free solves (csrc/nn.hip, csrc/matrix_free.hip) ----
+ * With every row's conditional, the sparse lower-triangular W whose row i is (-a, 1) / sqrt(d_i) -- a = A^-1 k on the row's neighbours,
+ * d_i its conditional variance -- satisfies (K + V)^-1 ~ W^T W, exactly with m >= n - 1: the Vecchia / KL-optimal sparse inverse
+ * Cholesky factor.  W^T W is symmetric positive definite whenever every d_i is positive, costs O(n m) to hold and to apply, and stays
+ * local where the rank-q pivoted Cholesky of fvgp_hip.h is global. */
+
+/* bytes of the caller-owned `work` of fvgp_hip_nn_factor for n rows: the info word, the theta table and the n conditional variances
+ * d_i.  -1 for n < 1. */
+int64_t fvgp_hip_nn_factor_workspace_bytes(int64_t n);
+
+/* The factor's rows.  x (n, d) in the ordering, idx (n, ld >= m) the lists of the likelihood (the conventions of the conditionals entry:
+ * entries outside 0 .. n - 1 are skipped wherever they stand, an empty list is legal, columns m .. ld are never read), ONE theta, v (n)
+ * the noise.  With A = K(x_c, x_c) + diag(v_c) = L L^T, k = K(x_c, x_i), w = L^-1 k, a = L^-T w (the backward pass of the gradient
+ * entry), d_i = (k(x_i, x_i) + v_i) - w^T w:
+ *     dinv[i] = 1 / sqrt(d_i),      coef[i][l] = -(a_l dinv[i]),  +0.0 where entry l of the list is skipped.
+ * coef (n, ldc >= m), columns m .. ldc are not written; dinv (n).  The assembly, the factorisation and d_i are the conditionals entry's
+ * own code (one more level of the same kernel); the data values r are never read.
+ * BIT CONTRACT: row i of coef and dinv[i] are functions of (x_i, v_i, the listed rows in their listed order, theta, m) alone: not of n
+ * or the position in it.  d_i has the bits of var[i] of the conditionals entry on the same inputs with s = v, and dinv[i] is the
+ * correctly rounded 1 / (correctly rounded sqrt(d_i)).
+ * A pivot that is not positive gives NaN in dinv[i] and in columns 0 .. m - 1 of coef's row; nothing traps.  info_host: 0, or 1 + i of
+ * the first row whose d_i is not positive (NaN included).  Synchronises the stream.
+ * work: device, 8-byte aligned, fvgp_hip_nn_factor_workspace_bytes(n) bytes.
+ * Errors: -1 h, -2 unknown kernel_id, -3 x, -4 n < 1 or past 2^31 - 1, -5 d outside 1 .. FVGP_MAX_DIM, -6 theta_host, -7 too few
+ * hyperparameters, -8 idx, -9 ld < m, -10 m outside 1 .. FVGP_NN_MAX_NEIGHBORS, -11 v, -12 coef, -13 ldc < m, -14 dinv, -15 work NULL or
+ * misaligned, -16 work_bytes too small, -17 info_host. */
+int fvgp_hip_nn_factor(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta_host, int ntheta,
+                       const int *idx, int64_t ld, int m, const double *v, double *coef, int64_t ldc, double *dinv,
+                       double *work, int64_t work_bytes, int64_t *info_host);
+
+/* bytes of the caller-owned `work` of fvgp_hip_nn_precond_apply for n rows: R, the intermediate T and Z in the solver's layout of
+ * FVGP_PCG_MAX_RHS columns, and one partial per 256 rows and column.  -1 for n < 1. */
+int64_t fvgp_hip_nn_precond_apply_workspace_bytes(int64_t n);
+
+/* Z[:, :s] = W^T (W R[:, :s]), s <= FVGP_PCG_MAX_RHS.  The factor is (idx, coef, dinv) with ONE leading dimension ld >= m for idx and
+ * coef, and the transposed lists: tr_start (n + 1) int64, tr_pos (nnz) int64 -- bucket j = tr_pos[tr_start[j] .. tr_start[j + 1]) holds
+ * the flat positions i ld + l of the entries with idx[i][l] == j in ascending i (the binding builds them on the host by a stable sort,
+ * once per neighbour structure).  Two launches in stream order over the solver's layout (a row is 16 doubles, 16 lanes take a row, one
+ * column each, so that a wave instruction reads four whole 128-byte rows):
+ *     gather     T[i][c] = dinv[i] R[i][c] + sum_{l = 0 .. m - 1} coef[i][l] R[idx[i][l]][c]     fused multiply-adds in ascending l,
+ *     transpose  Z[j][c] = dinv[j] T[j][c] + sum_{e in bucket j, ascending} coef_flat[pos_e] T[pos_e / ld][c].
+ * An entry of idx outside 0 .. n - 1 and a position outside 0 .. n ld - 1 are skipped, not read; bucket bounds are clipped to
+ * 0 .. nnz, and nothing of tr_pos at or past tr_start[n] is read.  A bucket's loop is bounded by its length alone (with coincident
+ * points one bucket can hold most rows); no atomics, no grid barrier, no dependence between workgroups.
+ * BIT CONTRACT: Z[.][c] is a function of (the factor, R[.][c]) alone: the same bits whatever s, the other columns or the launch geometry.
+ * Asynchronous.  work: device, 16-byte aligned, fvgp_hip_nn_precond_apply_workspace_bytes(n) bytes.
+ * Errors: -1 h, -2 n < 1 or past 2^31 - 1, -3 idx, -4 ld < m, -5 m outside 1 .. FVGP_NN_MAX_NEIGHBORS, -6 coef, -7 dinv, -8 tr_start,
+ * -9 tr_pos, -10 nnz < 0 or past n ld, -11 R, -12 ldr < s, -13 s outside 1 .. FVGP_PCG_MAX_RHS, -14 Z, -15 ldz < s, -16 work NULL or
+ * misaligned, -17 work_bytes too small. */
+int fvgp_hip_nn_precond_apply(fvgp_handle *h, int64_t n, const int *idx, int64_t ld, int m, const double *coef, const double *dinv,
+                              const int64_t *tr_start, const int64_t *tr_pos, int64_t nnz, const double *R, int64_t ldr, int s,
+                              double *Z, int64_t ldz, double *work, int64_t work_bytes);
+
+/* bytes of the caller-owned `work` of fvgp_hip_pcg_nn: the solver's with no low-rank part, and the (n, FVGP_PCG_MAX_RHS) intermediate
+ * T.  -1 for n < 1. */
+int64_t fvgp_hip_pcg_nn_workspace_bytes(int64_t n);
+
+/* The preconditioned conjugate gradients of fvgp_hip.h (the entry fvgp_hip_pcg: same recurrences, same kernels, same stopping rules, same
+ * outputs) with z = W^T W r in the place of the low-rank preconditioner: the arguments of that entry, the sparse factor (as
+ * fvgp_hip_nn_precond_apply takes it) where it has (G, ldg, q, C, ldc).  x, vdiag, B and X are in the factor's ordering.  The apply
+ * leaves the r.z partials per 256 rows where the low-rank apply leaves them, and the scalar steps are the same kernel.
+ * BIT CONTRACT: that of the entry fvgp_hip_pcg -- a column's iterates do not depend on s or on the other columns.
+ * Errors: -1 h, -2 unknown kernel_id, -3 x, -4 n < 1, -5 d, -6 theta, -7 too few hyperparameters, -8 vdiag, -9 idx, -10 ld < m, -11 m
+ * outside 1 .. FVGP_NN_MAX_NEIGHBORS, -12 coef, -13 dinv, -14 tr_start, -15 tr_pos, -16 nnz < 0 or past n ld, -17 B, -18 ldb < s, -19 s
+ * outside 1 .. FVGP_PCG_MAX_RHS, -20 X, -21 ldx < s, -23 tol not positive, -24 max_iter < 1, -25 check_every < 1, -26 max_restarts < 0,
+ * -27 work NULL or misaligned (16 bytes), -28 work_bytes too small, -29 iters_host, -30 relres_host, -31 status_host. */
+int fvgp_hip_pcg_nn(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta, int ntheta,
+                    const double *vdiag, const int *idx, int64_t ld, int m, const double *coef, const double *dinv,
+                    const int64_t *tr_start, const int64_t *tr_pos, int64_t nnz,
+                    const double *B, int64_t ldb, int s, double *X, int64_t ldx, int warm,
+                    double tol, int max_iter, int check_every, int max_restarts,
+                    double *work, int64_t work_bytes, int *iters_host, double *relres_host, int *status_host);
+
 /* bytes of the caller-owned `work` of the maxmin ordering below: the n distances to the nearest pick and two rows of per-workgroup
  * partials.  -1 for n < 1. */
 int64_t fvgp_hip_nn_maxmin_workspace_bytes(int64_t n);
