@@ -97,7 +97,7 @@ class StubOps(_lib.DistCalls):
         return torch.zeros(*shape, dtype=dtype or torch.float64)
 
     def to_device(self, a):
-        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64))
+        return torch.from_numpy(np.array(a, dtype=np.float64, order="C"))       # a copy, as an upload is: set_targets writes into it
 
     def kmat(self, kernel_id, x1, x2, theta, out, vdiag=None, pad=2):
         k = orc.KERNELS[NAMES[kernel_id]](x1.numpy(), x2.numpy(), np.asarray(theta))
