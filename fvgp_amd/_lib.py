@@ -597,6 +597,11 @@ class Handle(DistCalls):
         """the ABI entry `name` on this handle; a non-zero status raises"""
         _check(getattr(lib(), name)(self._h, *args), name)
 
+    def _work(self, work, query, *sizes):
+        """`work`, or for None a fresh device tensor of what the size query `query` asks for at `sizes` (none where it refuses them: the
+        entry then names the bad argument)"""
+        return self.empty(max(1, _workspace_bytes(query, *sizes)) // 8) if work is None else work
+
     def empty(self, *shape):
         return self.torch.empty(*shape, dtype=self.torch.float64, device=f"cuda:{self.device}")
 
@@ -929,8 +934,7 @@ class Handle(DistCalls):
         tensor that receives the normals, work None (allocated here) or a flat device tensor of mvn_sample_workspace_bytes(n, nsamp)
         bytes.  Asynchronous; a sample's bits depend on (seed, stream, its index) and L only."""
         nsamp = int(Y.shape[0])
-        if work is None:
-            work = self.empty(max(1, mvn_sample_workspace_bytes(n, nsamp)) // 8)
+        work = self._work(work, "fvgp_hip_mvn_sample_workspace_bytes", n, nsamp)
         self._call("fvgp_hip_mvn_sample", _ptr(L), int(n), L.stride(0), _ptr(mean), int(seed), int(stream), int(samp0), nsamp,
                    _ptr(Y), Y.stride(0), _ptr(Z_out), 0 if Z_out is None else Z_out.stride(0),
                    _ptr(work), work.numel() * 8)
@@ -945,8 +949,7 @@ class Handle(DistCalls):
         t, tp, nt = _theta(theta)
         n, d = x.shape
         P = int(xcand.shape[0])
-        if work is None:
-            work = self.empty(max(1, select_workspace_bytes(n, P, q)) // 8)
+        work = self._work(work, "fvgp_hip_select_workspace_bytes", n, P, q)
         self._call("fvgp_hip_select_batch", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(L), L.stride(0), _ptr(xcand), P,
                    _ptr(noise), _ptr(var), int(q), int(criterion), int(bool(allow_repeats)), float(tol),
                    _ptr(work), work.numel() * 8, _ptr(idx_out), _ptr(pick_var_out), _ptr(G_out),
@@ -967,8 +970,7 @@ class Handle(DistCalls):
         (-1 from the achieved rank on, the rows of G there are zero); returns the achieved rank (synchronises)."""
         t, tp, nt = _theta(theta)
         n, d = x.shape
-        if work is None:
-            work = self.empty(max(1, pchol_workspace_bytes(n, q)) // 8)
+        work = self._work(work, "fvgp_hip_pchol_workspace_bytes", n, q)
         rank = ctypes.c_int(0)
         self._call("fvgp_hip_pchol", int(kernel_id), _ptr(x), n, d, tp, nt, int(q), float(tol), _ptr(G), G.stride(0),
                    _ptr(piv_out), _ptr(resid_diag_out), _ptr(work), work.numel() * 8, ctypes.byref(rank))
@@ -976,8 +978,7 @@ class Handle(DistCalls):
 
     def precond_factor(self, G, q, n, vdiag, C, work=None):
         """fvgp_hip_precond_factor: C (padded_dim(q) square) <- the factor of I + G D^-1 G^T; returns info (0 = factored)"""
-        if work is None:
-            work = self.empty(max(1, precond_workspace_bytes(n, q)) // 8)
+        work = self._work(work, "fvgp_hip_precond_workspace_bytes", n, q)
         info = ctypes.c_int(0)
         self._call("fvgp_hip_precond_factor", _ptr(G), G.stride(0), int(q), int(n), _ptr(vdiag), _ptr(C), C.stride(0),
                    _ptr(work), work.numel() * 8, ctypes.byref(info))
@@ -992,8 +993,7 @@ class Handle(DistCalls):
         n, d = x.shape
         s = int(B.shape[1] if s is None else s)
         q = 0 if G is None else int(q)
-        if work is None:
-            work = self.empty(max(1, pcg_workspace_bytes(n, q)) // 8)
+        work = self._work(work, "fvgp_hip_pcg_workspace_bytes", n, q)
         iters = np.zeros(max(s, 1), dtype=np.int32)
         status = np.zeros(max(s, 1), dtype=np.int32)
         relres = np.zeros(max(s, 1), dtype=np.float64)
@@ -1013,8 +1013,7 @@ class Handle(DistCalls):
         s = int(B.shape[1] if s is None else s)
         q = 0 if G is None else int(q)
         L = int(lanczos_steps)
-        if work is None:
-            work = self.empty(max(1, pcg_lanczos_workspace_bytes(n, q, L)) // 8)
+        work = self._work(work, "fvgp_hip_pcg_lanczos_workspace_bytes", n, q, L)
         iters = np.zeros(max(s, 1), dtype=np.int32)
         status = np.zeros(max(s, 1), dtype=np.int32)
         relres = np.zeros(max(s, 1), dtype=np.float64)
@@ -1037,8 +1036,7 @@ class Handle(DistCalls):
         t, tp, nt = _theta(theta)
         s = int(U.shape[1] if s is None else s)
         n1, n2 = x1.shape[0], x2.shape[0]
-        if work is None:
-            work = self.empty(max(1, kgrad_form_workspace_bytes(n1, n2)) // 8)
+        work = self._work(work, "fvgp_hip_kgrad_form_workspace_bytes", n1, n2)
         out = np.zeros(max(nt, 1), dtype=np.float64)
         self._call("fvgp_hip_kgrad_form", int(kernel_id), _ptr(x1), n1, _ptr(x2), n2, x1.shape[1], tp, nt, _ptr(U), U.stride(0),
                    _ptr(W), W.stride(0), s, _ptr(work), work.numel() * 8, out.ctypes.data_as(P_d))
@@ -1057,8 +1055,7 @@ class Handle(DistCalls):
         n = R.shape[0]
         s = int(R.shape[1] if s is None else s)
         q = 0 if G is None else int(q)
-        if work is None:
-            work = self.empty(max(1, precond_apply_workspace_bytes(n, q)) // 8)
+        work = self._work(work, "fvgp_hip_precond_apply_workspace_bytes", n, q)
         self._call("fvgp_hip_precond_apply", _ptr(G), 0 if G is None else G.stride(0), q, _ptr(C),
                    0 if C is None else C.stride(0), n, _ptr(vdiag), _ptr(R), R.stride(0), s, _ptr(W),
                    W.stride(0), _ptr(work), work.numel() * 8)
@@ -1079,8 +1076,7 @@ class Handle(DistCalls):
         """fvgp_hip_chol_delete: the factor of the points that remain when the strictly increasing indices `idx` (host) leave, in the same
         buffer and as potrf leaves a factor of n - len(idx) points.  Asynchronous; call invalidate_factor() before the next solve."""
         idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).ravel())
-        if work is None:
-            work = self.empty(max(1, chol_update_workspace_bytes(n, len(idx))) // 8)
+        work = self._work(work, "fvgp_hip_chol_update_workspace_bytes", n, len(idx))
         self._call("fvgp_hip_chol_delete", _ptr(L), int(n), L.stride(0), idx.ctypes.data_as(P_l), len(idx),
                    _ptr(work), work.numel() * 8)
 
@@ -1109,7 +1105,7 @@ class Handle(DistCalls):
             raise ValueError(f"nn_grid_build: the cell grid takes 1 .. {NN_GRID_MAX_DIM} dimensions, got {d}; nn_search has no such limit")
         sp = _scales_ptr("nn_grid_build", scales, d)
         buf = self.empty(max(1, nn_grid_bytes(nr, d)) // 8)
-        work = self.empty(max(1, nn_grid_workspace_bytes(nr, d)) // 8)
+        work = self._work(None, "fvgp_hip_nn_grid_workspace_bytes", nr, d)
         info = np.zeros(NN_GRID_INFO)
         self._call("fvgp_hip_nn_grid_build", _ptr(xr), nr, d, sp, _ptr(buf), buf.numel() * 8, _ptr(work), work.numel() * 8,
                    info.ctypes.data_as(P_d))
@@ -1137,7 +1133,7 @@ class Handle(DistCalls):
         sp = _scales_ptr("nn_maxmin_order", scales, d)
         perm = self.torch.empty((max(q, 1),), dtype=self.torch.int64, device=x.device)
         dist = self.empty(max(q, 1)) if want_distances else None
-        work = self.empty(max(1, nn_maxmin_workspace_bytes(n)) // 8)
+        work = self._work(None, "fvgp_hip_nn_maxmin_workspace_bytes", n)
         self._call("fvgp_hip_nn_maxmin_order", _ptr(x), n, d, sp, int(first), q, _ptr(perm), _ptr(dist), _ptr(work), work.numel() * 8)
         self.sync()
         return perm.cpu().numpy(), None if dist is None else dist.cpu().numpy()
@@ -1162,8 +1158,7 @@ class Handle(DistCalls):
         1 + b nq + i of the first (b, i) whose variance is not positive (a failed pivot leaves NaN).  Synchronous."""
         nq = xq.shape[0]
         t, B = self._nn_operands("nn_conditionals", thetas, idx, nq, m, mu, var)
-        if work is None:
-            work = self.empty(max(1, nn_workspace_bytes(NN_CONDITIONALS, nq, B)) // 8)
+        work = self._work(work, "fvgp_hip_nn_workspace_bytes", NN_CONDITIONALS, nq, B)
         info = ctypes.c_int64(0)
         self._call("fvgp_hip_nn_conditionals", int(kernel_id), _ptr(xq), nq, _ptr(xr), xr.shape[0], xq.shape[1], t.ctypes.data_as(P_d),
                    t.shape[1], B, _ptr(idx), idx.stride(0), int(m), _ptr(r), _ptr(v), _ptr(s), _ptr(mu), _ptr(var),
@@ -1182,10 +1177,9 @@ class Handle(DistCalls):
         if level == NN_FISHER and (not fisher_rows.is_contiguous() or fisher_rows.numel() < B * n * (nth * (nth + 1) // 2)):
             raise ValueError(f"{who}: fisher_rows must be a contiguous (B, n, ntheta (ntheta + 1) / 2) tensor, got "
                              f"{tuple(fisher_rows.shape)}")
-        if work is None:
-            size = nn_workspace_bytes(NN_LOGLIK, n, B) if level == NN_VALUE else \
-                nn_grad_workspace_bytes(n, B, nth) if level == NN_GRAD else nn_fisher_workspace_bytes(n, B, nth)
-            work = self.empty(max(1, size) // 8)
+        query = ("fvgp_hip_nn_workspace_bytes", NN_LOGLIK, n, B) if level == NN_VALUE else \
+            ("fvgp_hip_nn_grad_workspace_bytes" if level == NN_GRAD else "fvgp_hip_nn_fisher_workspace_bytes", n, B, nth)
+        work = self._work(work, *query)
         out = np.empty((B, 3), dtype=np.float64)
         grad = np.empty((B, nth), dtype=np.float64) if level >= NN_GRAD else None
         fisher = np.empty((B, nth, nth), dtype=np.float64) if level == NN_FISHER else None
@@ -1249,8 +1243,7 @@ class Handle(DistCalls):
             dinv = self.empty(n)
         if coef.stride(0) != ld or coef.stride(1) != 1:
             raise ValueError(f"nn_factor: coef must have idx's leading dimension {ld}, got stride {coef.stride()}")
-        if work is None:
-            work = self.empty(max(1, nn_factor_workspace_bytes(n)) // 8)
+        work = self._work(work, "fvgp_hip_nn_factor_workspace_bytes", n)
         info = ctypes.c_int64(0)
         self._call("fvgp_hip_nn_factor", int(kernel_id), _ptr(x), n, d, tp, nt, _ptr(idx), ld, int(m), _ptr(v), _ptr(coef), ld,
                    _ptr(dinv), _ptr(work), work.numel() * 8, ctypes.byref(info))
@@ -1262,8 +1255,7 @@ class Handle(DistCalls):
         tensors.  Asynchronous."""
         n = factor.dinv.shape[0]
         s = int(R.shape[1] if s is None else s)
-        if work is None:
-            work = self.empty(max(2, nn_precond_apply_workspace_bytes(n) // 8))
+        work = self._work(work, "fvgp_hip_nn_precond_apply_workspace_bytes", n)
         self._call("fvgp_hip_nn_precond_apply", n, *factor._args(), _ptr(R), R.stride(0), s, _ptr(Z), Z.stride(0),
                    _ptr(work), work.numel() * 8)
 
@@ -1274,8 +1266,7 @@ class Handle(DistCalls):
         t, tp, nt = _theta(theta)
         n, d = x.shape
         s = int(B.shape[1] if s is None else s)
-        if work is None:
-            work = self.empty(max(2, pcg_nn_workspace_bytes(n) // 8))
+        work = self._work(work, "fvgp_hip_pcg_nn_workspace_bytes", n)
         iters = np.zeros(max(s, 1), dtype=np.int32)
         status = np.zeros(max(s, 1), dtype=np.int32)
         relres = np.zeros(max(s, 1), dtype=np.float64)

@@ -11,30 +11,47 @@ int64_t fvgp_hip_loglik_batch_dim(int64_t n, int ncol) {
     if (dim < 0) return -1;
     return dim <= FVGP_BATCH_MAX_DIM ? dim : 0;
 }
-// per problem: the inverse of the diagonal block of the current step, the reciprocal pivots of every step, the theta table row, two
-// reductions, the info word (fvgp_hip_loglik_batch's layout, in this order)
+// The handle's buffer for B problems of one batched evaluation.  Per problem: the block inverses (BATCH_VALUE: one slot, the current step's;
+// else every leaf's, dim / 128 of them), the reciprocal pivots of every step, the theta table row; BATCH_GRAD: z and b (2 padded_dim(n)) and
+// the trace's partial sums (T (T + 1) / 2 tiles x (1 + FVGP_MAX_DIM), T = padded_dim(n) / 128); then, packed, the block the host reads back
+// in ONE copy of back_bytes from `red` on: two reductions, BATCH_GRAD: the gradient row, the info word
+enum { BATCH_VALUE = 0, BATCH_GRAD = 1, BATCH_POSTERIOR = 2 };
+struct BatchWs { double *linv, *logdet, *tab, *zb, *partial, *red, *grad; int *info; int64_t lstride, zstride, pstride, ntiles; size_t back_bytes; };
+static BatchWs batch_layout(Carve &c, int which, int64_t n, int64_t dim, int64_t B) {
+    constexpr int64_t TW = 1 + FVGP_MAX_DIM, D = sizeof(double);
+    const int64_t np = pad128(n), T = np / TILE;
+    BatchWs l{};
+    l.lstride = which == BATCH_VALUE ? LEAF_DOUBLES : (dim / TILE) * LEAF_DOUBLES;
+    l.linv = c.take<double>(B * l.lstride, D); l.logdet = c.take<double>(B * dim, D); l.tab = c.take<double>(B * TW, D);
+    if (which == BATCH_GRAD) {
+        l.zstride = 2 * np; l.ntiles = T * (T + 1) / 2; l.pstride = l.ntiles * TW;
+        l.zb = c.take<double>(B * l.zstride, D); l.partial = c.take<double>(B * l.pstride, D);
+    }
+    const int64_t back = c.bytes();
+    l.red = c.take<double>(2 * B, D);
+    if (which == BATCH_GRAD) l.grad = c.take<double>(B * TW, D);
+    l.info = c.take<int>(B, sizeof(int));
+    l.back_bytes = (size_t)(c.bytes() - back);
+    return l;
+}
+
 int64_t fvgp_hip_loglik_batch_workspace_bytes(int64_t n, int ncol, int64_t B) {
     const int64_t dim = fvgp_hip_loglik_batch_dim(n, ncol);
     if (dim <= 0 || B < 1) return -1;
-    return B * (LEAF_DOUBLES + dim + (1 + FVGP_MAX_DIM) + 2) * (int64_t)sizeof(double) + B * (int64_t)sizeof(int);
+    return carve_bytes(batch_layout, BATCH_VALUE, n, dim, B);
 }
 
-// per problem: every leaf's block inverse (dim / 128 of them), the reciprocal pivots, the theta table row, z and b (2 padded_dim(n)),
-// the trace's partial sums (T (T + 1) / 2 tiles x (1 + FVGP_MAX_DIM), T = padded_dim(n) / 128), two reductions, the gradient row, the
-// info word (fvgp_hip_loglik_grad_batch's layout, in this order)
 int64_t fvgp_hip_loglik_grad_batch_workspace_bytes(int64_t n, int ncol, int64_t B) {
     const int64_t dim = fvgp_hip_loglik_batch_dim(n, ncol);
     if (dim <= 0 || B < 1) return -1;
-    const int64_t np = pad128(n), T = np / TILE, TW = 1 + FVGP_MAX_DIM;
-    return B * ((dim / TILE) * LEAF_DOUBLES + dim + TW + 2 * np + T * (T + 1) / 2 * TW + 2 + TW) * (int64_t)sizeof(double) + B * (int64_t)sizeof(int);
+    return carve_bytes(batch_layout, BATCH_GRAD, n, dim, B);
 }
 
-// per problem: every leaf's block inverse (dim / 128 of them), the reciprocal pivots, the theta table row, two reductions, the info word
-// (fvgp_hip_posterior_batch's layout, in this order; the prediction rows live in the caller's scratch, so P_chunk adds nothing here)
+// (the prediction rows live in the caller's scratch, so P_chunk adds nothing here)
 int64_t fvgp_hip_posterior_batch_workspace_bytes(int64_t n, int ncol, int64_t B, int64_t P_chunk) {
     const int64_t dim = fvgp_hip_loglik_batch_dim(n, ncol);
     if (dim <= 0 || B < 1 || P_chunk < TILE || P_chunk % TILE) return -1;
-    return B * ((dim / TILE) * LEAF_DOUBLES + dim + (1 + FVGP_MAX_DIM) + 2) * (int64_t)sizeof(double) + B * (int64_t)sizeof(int);
+    return carve_bytes(batch_layout, BATCH_POSTERIOR, n, dim, B);
 }
 
 // kmat_desc_from_theta numbers a bad d or ntheta as fvgp_hip_kmat's arguments (7, 9); in the batched entries they are arguments 5 and 7
@@ -55,13 +72,16 @@ static int batch_theta_table(fvgp_handle *h, int kernel_id, int d, const double 
     return 0;
 }
 
-static int batch_workspace(fvgp_handle *h, size_t ws) {
+// the handle's buffer grown to what the evaluation `which` needs, and carved
+static int batch_workspace(fvgp_handle *h, int which, int64_t n, int64_t dim, int64_t B, BatchWs *l) {
+    const size_t ws = (size_t)carve_bytes(batch_layout, which, n, dim, B);
     if (ws > h->bat_cap) {
         if (h->bat_ws) HIPCHK(hipFree(h->bat_ws));
         h->bat_ws = nullptr; h->bat_cap = 0;
         HIPCHK(hipMalloc((void **)&h->bat_ws, ws));
         h->bat_cap = ws;
     }
+    Carve c(h->bat_ws); *l = batch_layout(c, which, n, dim, B);
     return 0;
 }
 
@@ -163,13 +183,11 @@ int fvgp_hip_loglik_batch(fvgp_handle *h, int kernel_id, const double *x, int64_
     if (B > 1 && (kv_stride < dim * ld || (kv_stride & 1))) { fvgp_set_error("loglik_batch: kv_stride must be even and >= dim * ld"); return -16; }
     if (!out_host) return -17;
     HIPCHK(hipSetDevice(h->device));
-    rc = batch_workspace(h, (size_t)fvgp_hip_loglik_batch_workspace_bytes(n, ncol, B)); if (rc) return rc;
+    BatchWs l;
+    rc = batch_workspace(h, BATCH_VALUE, n, dim, B, &l); if (rc) return rc;
     constexpr int TW = 1 + FVGP_MAX_DIM;
-    double *linv = reinterpret_cast<double *>(h->bat_ws);
-    double *logdet = linv + B * LEAF_DOUBLES;
-    double *tab = logdet + B * dim;
-    double *red = tab + B * TW;
-    int *info = reinterpret_cast<int *>(red + 2 * B);
+    double *linv = l.linv, *logdet = l.logdet, *tab = l.tab, *red = l.red;
+    int *info = l.info;
     rc = batch_theta_table(h, kernel_id, d, thetas, ntheta, B, tab); if (rc) return rc;
     HIPCHK(hipMemsetAsync(info, 0, (size_t)B * sizeof(int), h->stream));
     const int64_t stride = B > 1 ? kv_stride : 0;
@@ -182,9 +200,8 @@ int fvgp_hip_loglik_batch(fvgp_handle *h, int kernel_id, const double *x, int64_
         if (rc) return rc;
     }
     // ONE host round trip: the B reductions and the B info words in one copy
-    const size_t rbytes = (size_t)B * (2 * sizeof(double) + sizeof(int));
-    h->bat_out_host.resize(rbytes);
-    HIPCHK(hipMemcpyAsync(h->bat_out_host.data(), red, rbytes, hipMemcpyDeviceToHost, h->stream));
+    h->bat_out_host.resize(l.back_bytes);
+    HIPCHK(hipMemcpyAsync(h->bat_out_host.data(), red, l.back_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     const double *r = reinterpret_cast<const double *>(h->bat_out_host.data());
     batch_results(n, ncol, B, r, reinterpret_cast<const int *>(r + 2 * B), out_host, info_host);
@@ -228,19 +245,12 @@ int fvgp_hip_loglik_grad_batch(fvgp_handle *h, int kernel_id, const double *x, i
     if (!out_host) return -21;
     if (!grad_host) return -22;
     HIPCHK(hipSetDevice(h->device));
-    rc = batch_workspace(h, (size_t)fvgp_hip_loglik_grad_batch_workspace_bytes(n, ncol, B)); if (rc) return rc;
+    BatchWs l;
+    rc = batch_workspace(h, BATCH_GRAD, n, dim, B, &l); if (rc) return rc;
     constexpr int TW = 1 + FVGP_MAX_DIM;
-    const int64_t T = np / TILE, ntiles = T * (T + 1) / 2, lstride = (dim / TILE) * LEAF_DOUBLES, zstride = 2 * np, pstride = ntiles * TW;
-    // workspace layout (fvgp_hip_loglik_grad_batch_workspace_bytes): every leaf inverse, reciprocal pivots, theta table, z and b,
-    // partial sums, then {reductions, gradients, info words} -- the block the host copies back
-    double *linv = reinterpret_cast<double *>(h->bat_ws);
-    double *logdet = linv + B * lstride;
-    double *tab = logdet + B * dim;
-    double *zb = tab + B * TW;
-    double *partial = zb + B * zstride;
-    double *red = partial + B * pstride;
-    double *grad = red + 2 * B;
-    int *info = reinterpret_cast<int *>(grad + B * TW);
+    const int64_t ntiles = l.ntiles, lstride = l.lstride, zstride = l.zstride, pstride = l.pstride;
+    double *linv = l.linv, *logdet = l.logdet, *tab = l.tab, *zb = l.zb, *partial = l.partial, *red = l.red, *grad = l.grad;
+    int *info = l.info;
     rc = batch_theta_table(h, kernel_id, d, thetas, ntheta, B, tab); if (rc) return rc;
     HIPCHK(hipMemsetAsync(info, 0, (size_t)B * sizeof(int), h->stream));
     const int kind = k0d.kind, iso = k0d.iso, nk = kernel_param_count(kernel_id, d);
@@ -284,9 +294,8 @@ int fvgp_hip_loglik_grad_batch(fvgp_handle *h, int kernel_id, const double *x, i
         }
     }
     // ONE host round trip: reductions, gradients and info words in one copy
-    const size_t rbytes = (size_t)B * ((2 + TW) * sizeof(double) + sizeof(int));
-    h->bat_out_host.resize(rbytes);
-    HIPCHK(hipMemcpyAsync(h->bat_out_host.data(), red, rbytes, hipMemcpyDeviceToHost, h->stream));
+    h->bat_out_host.resize(l.back_bytes);
+    HIPCHK(hipMemcpyAsync(h->bat_out_host.data(), red, l.back_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     const double *r = reinterpret_cast<const double *>(h->bat_out_host.data()), *g = r + 2 * B;
     const int *inf = reinterpret_cast<const int *>(g + B * TW);
@@ -342,16 +351,12 @@ int fvgp_hip_posterior_batch(fvgp_handle *h, int kernel_id, const double *x, int
         if (B > 1 && (s_stride < Pp * lds || (s_stride & 1))) { fvgp_set_error("posterior_batch: s_stride must be even and >= padded_dim(P) * lds"); return -24; }
     }
     HIPCHK(hipSetDevice(h->device));
-    rc = batch_workspace(h, (size_t)fvgp_hip_posterior_batch_workspace_bytes(n, ncol, B, P_chunk)); if (rc) return rc;
+    BatchWs l;
+    rc = batch_workspace(h, BATCH_POSTERIOR, n, dim, B, &l); if (rc) return rc;
     constexpr int TW = 1 + FVGP_MAX_DIM;
-    const int64_t lstride = (dim / TILE) * LEAF_DOUBLES;
-    // workspace layout (fvgp_hip_posterior_batch_workspace_bytes): every leaf inverse, reciprocal pivots, theta table, then {reductions,
-    // info words} -- the block the host copies back
-    double *linv = reinterpret_cast<double *>(h->bat_ws);
-    double *logdet = linv + B * lstride;
-    double *tab = logdet + B * dim;
-    double *red = tab + B * TW;
-    int *info = reinterpret_cast<int *>(red + 2 * B);
+    const int64_t lstride = l.lstride;
+    double *linv = l.linv, *logdet = l.logdet, *tab = l.tab, *red = l.red;
+    int *info = l.info;
     rc = batch_theta_table(h, kernel_id, d, thetas, ntheta, B, tab); if (rc) return rc;
     HIPCHK(hipMemsetAsync(info, 0, (size_t)B * sizeof(int), h->stream));
     const int kind = k0d.kind;
@@ -387,9 +392,8 @@ int fvgp_hip_posterior_batch(fvgp_handle *h, int kernel_id, const double *x, int
         }
     }
     // ONE host round trip: the B reductions and the B info words in one copy
-    const size_t rbytes = (size_t)B * (2 * sizeof(double) + sizeof(int));
-    h->bat_out_host.resize(rbytes);
-    HIPCHK(hipMemcpyAsync(h->bat_out_host.data(), red, rbytes, hipMemcpyDeviceToHost, h->stream));
+    h->bat_out_host.resize(l.back_bytes);
+    HIPCHK(hipMemcpyAsync(h->bat_out_host.data(), red, l.back_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     const double *r = reinterpret_cast<const double *>(h->bat_out_host.data());
     const int *inf = reinterpret_cast<const int *>(r + 2 * B);

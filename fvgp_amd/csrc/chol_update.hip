@@ -244,14 +244,24 @@ int update_passes(fvgp_handle *h, double *L, int64_t n, int64_t ldl, double *W, 
     return 0;
 }
 
+// the coefficient table, all an update uses of its workspace (FVGP_CHOL_UPDATE_TABLE_BYTES) and the first piece of a removal's
+static_assert(CU_TAB_DOUBLES * sizeof(double) == FVGP_CHOL_UPDATE_TABLE_BYTES, "the table's size is part of the ABI");
+double *cu_table(Carve &c) { return c.take<double>(CU_TAB_DOUBLES); }
+
+// a removal's workspace: the table, the removed and the kept indices, W = L[S, R] (n rows of ldw), the strip (srows rows of lds)
+struct DeleteWs { double *tab; long *R, *S; double *W, *strip; int64_t ldw, lds, srows; };
+DeleteWs delete_layout(Carve &c, int64_t n, int64_t k) {
+    const int64_t ldw = even_up(k), lds = even_up(n), srows = strip_rows(n);
+    return {cu_table(c), c.take<long>(k), c.take<long>(n), c.take<double>(n * ldw), c.take<double>(srows * lds), ldw, lds, srows};
+}
+
 }  // namespace
 
 extern "C" {
 
 int64_t fvgp_hip_chol_update_workspace_bytes(int64_t n, int64_t k) {
     if (n < 1 || k < 1) return -1;
-    const int64_t doubles = CU_TAB_DOUBLES + even_up(k) + even_up(n) + n * even_up(k) + strip_rows(n) * even_up(n);
-    return doubles * (int64_t)sizeof(double);
+    return carve_bytes(delete_layout, n, k);
 }
 
 int fvgp_hip_chol_update(fvgp_handle *h, double *L, int64_t n, int64_t ldl, double *W, int64_t k, int64_t ldw, int64_t row0,
@@ -264,9 +274,10 @@ int fvgp_hip_chol_update(fvgp_handle *h, double *L, int64_t n, int64_t ldl, doub
     if (ldw < k) { fvgp_set_error("chol_update: ldw below k"); return -7; }
     if (row0 < 0 || row0 > n) { fvgp_set_error("chol_update: row0 outside 0 .. n"); return -8; }
     if (!ws || ((uintptr_t)ws & 15)) { fvgp_set_error("chol_update: ws must be 16-byte aligned"); return -9; }
-    if (ws_bytes < (int64_t)FVGP_CHOL_UPDATE_TABLE_BYTES) { fvgp_set_error("chol_update: ws smaller than FVGP_CHOL_UPDATE_TABLE_BYTES"); return -10; }
+    Carve c(ws); double *tab = cu_table(c);
+    if (ws_bytes < c.bytes()) { fvgp_set_error("chol_update: ws smaller than FVGP_CHOL_UPDATE_TABLE_BYTES"); return -10; }
     HIPCHK(hipSetDevice(h->device));
-    return update_passes(h, L, n, ldl, W, (int)k, ldw, nullptr, row0, ws);
+    return update_passes(h, L, n, ldl, W, (int)k, ldw, nullptr, row0, tab);
 }
 
 int fvgp_hip_chol_delete(fvgp_handle *h, double *L, int64_t n, int64_t ldl, const int64_t *idx_host, int64_t k, double *ws, int64_t ws_bytes) {
@@ -280,17 +291,14 @@ int fvgp_hip_chol_delete(fvgp_handle *h, double *L, int64_t n, int64_t ldl, cons
             fvgp_set_error("chol_delete: indices must be strictly increasing and inside 0 .. n - 1"); return -5;
         }
     if (!ws || ((uintptr_t)ws & 15)) { fvgp_set_error("chol_delete: ws must be 16-byte aligned"); return -7; }
-    if (ws_bytes < fvgp_hip_chol_update_workspace_bytes(n, k)) {
+    Carve c(ws); const DeleteWs l = delete_layout(c, n, k);
+    if (ws_bytes < c.bytes()) {
         fvgp_set_error("chol_delete: ws smaller than fvgp_hip_chol_update_workspace_bytes(n, k)"); return -8;
     }
     HIPCHK(hipSetDevice(h->device));
-    const int64_t m = n - k, ldw = even_up(k), np = pad128(n), first = idx_host[0];
-    double *tab = ws;
-    long *R = reinterpret_cast<long *>(tab + CU_TAB_DOUBLES);
-    long *S = R + even_up(k);
-    double *W = reinterpret_cast<double *>(S + even_up(n));
-    double *strip = W + n * ldw;
-    const int64_t lds = even_up(n), srows = strip_rows(n);
+    const int64_t m = n - k, ldw = l.ldw, np = pad128(n), first = idx_host[0], lds = l.lds, srows = l.srows;
+    double *tab = l.tab, *W = l.W, *strip = l.strip;
+    long *R = l.R, *S = l.S;
     static_assert(sizeof(long) == sizeof(int64_t), "index words");
     HIPCHK(hipMemcpyAsync(R, idx_host, (size_t)k * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(kept_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, R, (int)k, (long)n, S);

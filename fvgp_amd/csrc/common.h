@@ -7,6 +7,7 @@
 #include <type_traits>
 #include <vector>
 #include "../../include/fvgp_hip.h"
+#include "carve.h"
 
 constexpr int TILE = FVGP_TILE;        // 128: tile edge of every kernel and the leaf Cholesky block
 constexpr int LEAF_DOUBLES = TILE * TILE;
@@ -168,7 +169,7 @@ int fvgp_hip_fail(hipError_t e, const char *what, int line);
     do { hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__); HIPCHK(hipGetLastError()); } while (0)
 
 static inline int64_t pad128(int64_t n) { return (n + TILE - 1) / TILE * TILE; }
-static inline int64_t even_up(int64_t v) { return (v + 1) & ~(int64_t)1; }      // workspace pieces in doubles: every offset stays 16-byte aligned
+static inline int64_t even_up(int64_t v) { return (v + 1) & ~(int64_t)1; }      // leading dimensions in doubles: every row stays 16-byte aligned
 
 // the vector kernels are instantiated for 1, 2, 4 and 8 right-hand sides: the narrowest width that holds c (<= FVGP_MAX_RHS_VEC) columns
 static inline int rhs_width(int c) { return c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : 8; }
@@ -259,6 +260,8 @@ constexpr int MV_MAXS = 16;                          // widest column group
 static inline int64_t mv_chunks(int64_t n2) { return (n2 + MATVEC_CHUNK - 1) / MATVEC_CHUNK; }
 static inline int mv_group(int left) { return left >= MV_MAXS ? MV_MAXS : left > 4 ? 8 : left > 1 ? 4 : 1; }      // the narrowest group that holds what is left
 static inline int64_t mv_split_doubles(int64_t n1, int64_t n2, int s) { return mv_chunks(n2) * n1 * mv_group(s); }
+// the split form's per-chunk sums as a piece of a workspace
+static inline double *mv_park_layout(Carve &c, int64_t n1, int64_t n2, int s) { return c.take<double>(mv_split_doubles(n1, n2, s), sizeof(double)); }
 // the launches' gridDim.y when nothing is forced: chunk ranges are dealt out only while the 64-row blocks alone cannot fill the chip
 static inline int64_t mv_auto_split(int64_t n1, int64_t n2) {
     const int64_t bx = (n1 + 63) / 64, nch = mv_chunks(n2);

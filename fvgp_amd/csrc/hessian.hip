@@ -290,15 +290,23 @@ int launch_rowdot_scale(fvgp_handle *h, const double *T, int64_t ldt, const doub
 // doubles of the second-derivative pass's partial sums for an input dimension d
 int64_t hess_partial_doubles(int64_t nb, int d) { return nb * (d > 4 ? (int64_t)d * hess_row_width(0) : (int64_t)hess_row_width(d)); }
 
+// fvgp_hip_loglik_hess's scratch: ONE piece that the host reads back in one copy -- the second-derivative pass's rows (hpart, nh doubles)
+// and behind them, as the view tpart, the trace passes' (room for d + 1 passes of nb rows of d + 1 sums; a kernel with nk parameters
+// fills nk passes of nb rows of nk) --, then the vector 2 w_i
+struct HessWs { double *hpart, *tpart, *w2; int64_t nb, nh; };
+HessWs hess_layout(Carve &c, int64_t n, int d) {
+    const int64_t np = pad128(n), T = np / TILE, nk = d + 1, nb = T * (T + 1) / 2, nh = hess_partial_doubles(nb, d);
+    double *sums = c.take<double>(nh + nk * nk * nb, sizeof(double));
+    return {sums, c.view<double>(sums, nh), c.take<double>(np, sizeof(double)), nb, nh};
+}
+
 }  // namespace
 
 extern "C" {
 
 int64_t fvgp_hip_loglik_hess_workspace_bytes(int64_t n, int d) {
     if (n < 1 || d < 1 || d > FVGP_MAX_DIM) return -1;
-    const int64_t np = pad128(n), T = np / TILE, nb = T * (T + 1) / 2, nk = d + 1;
-    // the second-derivative pass's rows, nk trace passes of nb rows of nk sums, the vector 2 w_i
-    return (hess_partial_doubles(nb, d) + nk * nk * nb + np) * (int64_t)sizeof(double);
+    return carve_bytes(hess_layout, n, d);
 }
 
 int fvgp_hip_loglik_hess(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
@@ -321,16 +329,17 @@ int fvgp_hip_loglik_hess(fvgp_handle *h, int kernel_id, const double *x, int64_t
     rc = check_square(work2, n, ldw2, 15, 4, 16);
     if (rc) return rc;
     if (!ws || ((uintptr_t)ws & 7)) return -17;
-    if (ws_bytes < fvgp_hip_loglik_hess_workspace_bytes(n, d)) { fvgp_set_error("loglik_hess: ws smaller than fvgp_hip_loglik_hess_workspace_bytes(n, d)"); return -18; }
+    Carve c(ws); const HessWs l = hess_layout(c, n, d);
+    if (ws_bytes < c.bytes()) { fvgp_set_error("loglik_hess: ws smaller than fvgp_hip_loglik_hess_workspace_bytes(n, d)"); return -18; }
     if (!grad_host) return -19;
     if (!hess_host) return -20;
     GradDesc g{};
     rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &g.k); if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    const int64_t np = pad128(n), T = np / TILE, nb = T * (T + 1) / 2;
+    const int64_t np = pad128(n), nb = l.nb;
     g.k.x1 = x; g.k.n1 = n; g.k.x2 = x; g.k.n2 = n;
     const double *b = alpha + component;
-    double *hpart = ws, *tpart = ws + hess_partial_doubles(nb, d), *w2 = tpart + (int64_t)nk * nk * nb;
+    double *hpart = l.hpart, *tpart = l.tpart, *w2 = l.w2;
 
     rc = fvgp_hip_potri(h, KV, n, ld, work, ldw); if (rc) return rc;                     // W in the lower tiles of KV; `work` is dead
     long hblocks = 0; int hw = 0;
@@ -348,9 +357,9 @@ int fvgp_hip_loglik_hess(fvgp_handle *h, int kernel_id, const double *x, int64_t
         rc = launch_grad_trace(h, g, &nblocks); if (rc) return rc;
         if (nblocks != nb) { fvgp_set_error("loglik_hess: the trace pass left an unexpected number of rows"); return -100; }
     }
-    const size_t nh = (size_t)hess_partial_doubles(nb, d), nt = (size_t)nk * nk * nb;
+    const size_t nh = (size_t)l.nh, nt = (size_t)nk * nk * nb;
     std::vector<double> part(nh + nt);
-    HIPCHK(hipMemcpyAsync(part.data(), ws, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(part.data(), hpart, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     rc = fvgp_ipc_check(h); if (rc) return rc;
 

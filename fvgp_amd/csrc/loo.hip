@@ -159,12 +159,18 @@ int launch_diag_copy(fvgp_handle *h, const double *M, int64_t ldm, int64_t n, do
     return 0;
 }
 
+// fvgp_hip_loo's vector scratch: w, c, sqrt c (padded n each); four partial sums per 128 rows
+struct LooWs { double *w, *c, *sc, *spart; };
+static LooWs loo_layout(Carve &cv, int64_t n) {
+    const int64_t np = pad128(n);
+    return {cv.take<double>(np, 8), cv.take<double>(np, 8), cv.take<double>(np, 8), cv.take<double>(4 * (np / TILE), 8)};
+}
+
 extern "C" {
 
 int64_t fvgp_hip_loo_workspace_bytes(int64_t n) {
     if (n < 1) return -1;
-    const int64_t np = pad128(n);
-    return (3 * np + 4 * (np / TILE)) * (int64_t)sizeof(double);      // w, c, sqrt c; four partial sums per 128 rows
+    return carve_bytes(loo_layout, n);
 }
 
 int fvgp_hip_loo(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
@@ -184,7 +190,8 @@ int fvgp_hip_loo(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int 
     rc = check_square(work, n, ldw, 13, 4, 14);
     if (rc) return rc;
     if (!ws || ((uintptr_t)ws & 7)) return -15;
-    if (ws_bytes < fvgp_hip_loo_workspace_bytes(n)) { fvgp_set_error("loo: ws smaller than fvgp_hip_loo_workspace_bytes(n)"); return -16; }
+    Carve cv(ws); const LooWs l = loo_layout(cv, n);
+    if (ws_bytes < cv.bytes()) { fvgp_set_error("loo: ws smaller than fvgp_hip_loo_workspace_bytes(n)"); return -16; }
     if (!out_host) return -17;
     if (!resid_out) return -18;
     if (!var_out) return -19;
@@ -198,17 +205,16 @@ int fvgp_hip_loo(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int 
     }
     HIPCHK(hipSetDevice(h->device));
     const int64_t np = pad128(n), T = np / TILE;
-    double *w = ws, *c = ws + np, *sc = ws + 2 * np, *spart = ws + 3 * np;
 
     rc = fvgp_hip_potri(h, KV, n, ld, work, ldw); if (rc) return rc;                     // Q in the lower tiles of KV; `work` is dead
-    rc = launch_loo_stats(h, KV, ld, alpha, ncol, component, n, np, resid_out, var_out, w, c, sc, spart); if (rc) return rc;
+    rc = launch_loo_stats(h, KV, ld, alpha, ncol, component, n, np, resid_out, var_out, l.w, l.c, l.sc, l.spart); if (rc) return rc;
     std::vector<double> sp((size_t)(4 * T)), part;
-    HIPCHK(hipMemcpyAsync(sp.data(), spart, sp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(sp.data(), l.spart, sp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     int nblocks = 0;
     if (grad_host) {
         // the per-row slots of u = Q w live in `work` (np rows of T <= ldw slots) until M takes it over
-        rc = launch_symv_lower(h, KV, ld, np, w, work, ldw, n, u_out); if (rc) return rc;
-        rc = launch_mirror_scale(h, KV, ld, np, sc); if (rc) return rc;                  // KV <- S = Q diag(sqrt c), full
+        rc = launch_symv_lower(h, KV, ld, np, l.w, work, ldw, n, u_out); if (rc) return rc;
+        rc = launch_mirror_scale(h, KV, ld, np, l.sc); if (rc) return rc;                  // KV <- S = Q diag(sqrt c), full
         rc = launch_gemm(h, gemm_desc(0, 0, np, np, np, 1.0, KV, ld, KV, ld, 0.0, work, ldw).lower_tiles()); if (rc) return rc;   // M = S S^T
         rc = launch_diag_copy(h, work, ldw, n, mdiag_out); if (rc) return rc;
         g.k.x1 = x; g.k.n1 = n; g.k.x2 = x; g.k.n2 = n;

@@ -380,31 +380,37 @@ __global__ __launch_bounds__(256) void pcg_apply_kernel(const double *G, long ld
     }
 }
 
-// the preconditioner's pieces of a workspace from offset o on: T (pad128(q) rows of PCG_LD whose padding stays zero), the chunks' partials
-// of G (D^-1 R), part0 (r.z by blocks of 256 points: >= the DOT_ROWS blocks of the solver's other partials)
-struct PrecondLayout { int64_t T, tpart, part0, end, qp, tchunks; };
-PrecondLayout precond_layout(int64_t n, int q, int64_t o) {
-    PrecondLayout l;
+// a piece of `rows` rows of PCG_LD doubles (128 bytes each: every such piece begins 16-byte aligned behind others of its kind)
+inline double *mf_rows(Carve &c, int64_t rows) { return c.take<double>(rows * PCG_LD, sizeof(double)); }
+// the pieces the entries of this unit share: R and Z (n rows), behind them the solver's P and AP; the intermediate T = W R of the
+// nearest-neighbour preconditioner; part0 (r.z by blocks of 256 points: >= the DOT_ROWS blocks of the solver's other partials)
+inline void vec_layout(Carve &c, int64_t n, bool solver, PcgVec &a) {
+    a.R = mf_rows(c, n); a.Z = mf_rows(c, n);
+    if (solver) { a.P = mf_rows(c, n); a.AP = mf_rows(c, n); }
+}
+inline double *nn_t_layout(Carve &c, int64_t n) { return mf_rows(c, n); }
+inline void part0_layout(Carve &c, int64_t n, PcgVec &a) { a.part0 = mf_rows(c, (n + 255) / 256); }
+
+// the low-rank preconditioner's pieces: T (pad128(q) rows whose padding stays zero), the chunks' partials of G (D^-1 R), part0
+struct PrecondWs { double *T, *tpart; int64_t qp, tchunks; };
+PrecondWs precond_layout(Carve &c, int64_t n, int q, PcgVec &a) {
+    PrecondWs l;
     l.qp = q > 0 ? pad128(q) : 0;
     l.tchunks = (n + PT_CHUNK - 1) / PT_CHUNK;
-    l.T = o; o += l.qp * PCG_LD;
-    l.tpart = o; o += l.tchunks * q * PCG_LD;
-    l.part0 = o; o += (n + 255) / 256 * PCG_LD;
-    l.end = o;
+    l.T = mf_rows(c, l.qp); l.tpart = mf_rows(c, l.tchunks * q);
+    part0_layout(c, n, a);
     return l;
 }
 
-// before the first pcg_precond on a workspace: the padding of T is zeroed, a.part0 points at the layout's
-int precond_begin(fvgp_handle *h, double *work, const PrecondLayout &l, PcgVec &a) {
-    a.part0 = work + l.part0;
-    if (l.qp) HIPCHK(hipMemsetAsync(work + l.T, 0, (size_t)l.qp * PCG_LD * sizeof(double), h->stream));
+// before the first pcg_precond on a workspace: the padding of T is zeroed
+int precond_begin(fvgp_handle *h, const PrecondWs &l) {
+    if (l.qp) HIPCHK(hipMemsetAsync(l.T, 0, (size_t)l.qp * PCG_LD * sizeof(double), h->stream));
     return 0;
 }
 
 // Z = M^-1 R for the solver's own vectors, part0 = r.z: G (D^-1 R) in chunks, one potrs per column, the apply kernel
-int pcg_precond(fvgp_handle *h, const double *G, int64_t ldg, int q, const double *C, int64_t ldc, const PcgVec &a, double *work,
-                const PrecondLayout &l) {
-    double *T = work + l.T, *tpart = work + l.tpart;
+int pcg_precond(fvgp_handle *h, const double *G, int64_t ldg, int q, const double *C, int64_t ldc, const PcgVec &a, const PrecondWs &l) {
+    double *T = l.T, *tpart = l.tpart;
     if (q > 0) {
         HIPLAUNCH(pcg_gr_kernel, dim3((unsigned)l.tchunks), dim3(256), h->stream, G, (long)ldg, q, a, tpart);
         HIPLAUNCH(pcg_gr_finish_kernel, dim3((unsigned)((q * PCG_LD + 255) / 256)), dim3(256), h->stream, tpart, (long)l.tchunks, q, a.s, T);
@@ -486,29 +492,40 @@ int nn_factor_check(const char *who, int64_t n, const int *idx, int64_t ld, int 
     return 0;
 }
 
-// nn: the (n, PCG_LD) intermediate T of the nearest-neighbour preconditioner behind everything else (the other offsets do not move)
-struct PcgLayout { int64_t R, Z, P, AP, part1, state, mv, total, mv_doubles, nnT; PrecondLayout pre; };
-PcgLayout pcg_layout(int64_t n, int q, bool nn = false) {
-    PcgLayout l;
+// the solver's workspace: its vectors (into a), the low-rank preconditioner's pieces, the second partials, the state, the split product's
+// parking room while the product deals chunk ranges by itself, nn: the intermediate T of the nearest-neighbour preconditioner, L > 0:
+// the Lanczos record -- alpha and beta (PCG_LD, L), rho0, steps and first (PCG_LD ints each) and PCG_LD doubles that nothing uses
+// (the size has always counted the two rows of ints as rows of doubles)
+struct PcgWs { PrecondWs pre; double *mv, *nnT; int64_t mv_doubles; PcgRec rec; size_t rec_bytes; };
+PcgWs pcg_layout(Carve &c, int64_t n, int q, bool nn, int L, PcgVec &a) {
+    PcgWs l{};
+    vec_layout(c, n, true, a);
+    l.pre = precond_layout(c, n, q, a);
+    a.part1 = mf_rows(c, (n + 255) / 256); a.st = c.take<PcgState>(1);
     l.mv_doubles = mv_auto_split(n, n) > 1 ? mv_split_doubles(n, n, MV_MAXS) : 0;
-    int64_t o = 0;
-    l.R = o; o += n * PCG_LD; l.Z = o; o += n * PCG_LD; l.P = o; o += n * PCG_LD; l.AP = o; o += n * PCG_LD;
-    l.pre = precond_layout(n, q, o); o = l.pre.end;
-    l.part1 = o; o += (n + 255) / 256 * PCG_LD;
-    l.state = o; o += even_up((int64_t)((sizeof(PcgState) + 7) / 8));
-    l.mv = o; o += l.mv_doubles;
-    l.nnT = o; o += nn ? n * PCG_LD : 0;
-    l.total = o;
+    l.mv = l.mv_doubles ? mv_park_layout(c, n, n, MV_MAXS) : nullptr;
+    l.nnT = nn ? nn_t_layout(c, n) : nullptr;
+    if (L > 0) {                                                  // L == 0: every pointer NULL, the scalar kernel records nothing
+        const int64_t at = c.bytes();
+        l.rec.alpha = mf_rows(c, L); l.rec.beta = mf_rows(c, L); l.rec.rho0 = mf_rows(c, 1);
+        l.rec.steps = c.take<int>(PCG_LD, sizeof(int)); l.rec.first = c.take<int>(PCG_LD, sizeof(int));
+        mf_rows(c, 1); l.rec.L = L; l.rec_bytes = (size_t)(c.bytes() - at);
+    }
     return l;
 }
 
-inline int64_t pcg_rec_doubles(int L) { return L > 0 ? (int64_t)PCG_LD * (2 * L + 3) : 0; }      // alpha, beta, rho0, and steps and first (ints) in two rows
+// fvgp_hip_precond_apply's workspace: R and Z, the low-rank preconditioner's pieces
+PrecondWs apply_layout(Carve &c, int64_t n, int q, PcgVec &a) {
+    vec_layout(c, n, false, a);
+    return precond_layout(c, n, q, a);
+}
 
-struct ApplyLayout { int64_t R, Z, total; PrecondLayout pre; };
-ApplyLayout apply_layout(int64_t n, int q) {
-    ApplyLayout l{0, n * PCG_LD, 0, precond_layout(n, q, 2 * n * PCG_LD)};
-    l.total = l.pre.end;
-    return l;
+// fvgp_hip_nn_precond_apply's: R and Z, T, part0
+double *nn_apply_layout(Carve &c, int64_t n, PcgVec &a) {
+    vec_layout(c, n, false, a);
+    double *T = nn_t_layout(c, n);
+    part0_layout(c, n, a);
+    return T;
 }
 
 // what the two solver entries ask of the driver: the arguments of fvgp_hip_pcg_lanczos (include/fvgp_hip.h); fvgp_hip_pcg leaves L = 0
@@ -546,7 +563,9 @@ int pcg_driver(fvgp_handle *h, PcgCall p) {
     if (p.max_restarts < 0) return -23;
     if (!p.work || ((uintptr_t)p.work & 15)) { fvgp_set_error("pcg: work must be 16-byte aligned"); return -24; }
     if (p.L < 0 || p.L > FVGP_LANCZOS_MAX_STEPS) { fvgp_set_error("pcg_lanczos: lanczos_steps outside 0 .. FVGP_LANCZOS_MAX_STEPS"); return -29; }
-    if (p.work_bytes < (pcg_layout(p.n, p.q, p.nn).total + pcg_rec_doubles(p.L)) * (int64_t)sizeof(double)) {
+    Carve c(p.work); PcgVec a;
+    const PcgWs lay = pcg_layout(c, p.n, p.q, p.nn, p.L, a);
+    if (p.work_bytes < c.bytes()) {
         fvgp_set_error(p.nn ? "pcg_nn: work smaller than fvgp_hip_pcg_nn_workspace_bytes(n)"
                        : p.L ? "pcg_lanczos: work smaller than fvgp_hip_pcg_lanczos_workspace_bytes(n, rank, lanczos_steps)"
                          : "pcg: work smaller than fvgp_hip_pcg_workspace_bytes(n, rank)");
@@ -565,23 +584,12 @@ int pcg_driver(fvgp_handle *h, PcgCall p) {
     KmatDesc k{};
     rc = kmat_desc_from_theta(p.kernel_id, p.d, p.theta, p.ntheta, &k); if (rc) return rc;
     k.x1 = p.x; k.n1 = p.n; k.x2 = p.x; k.n2 = p.n; k.vdiag = p.vdiag;
-    const PcgLayout lay = pcg_layout(p.n, p.q, p.nn);
-    PcgRec rec{};                                                 // L == 0: every pointer NULL, the scalar kernel records nothing
-    if (p.L > 0) {
-        double *rw = p.work + lay.total;
-        rec.alpha = rw; rec.beta = rw + (int64_t)PCG_LD * p.L; rec.rho0 = rw + 2 * (int64_t)PCG_LD * p.L;
-        rec.steps = reinterpret_cast<int *>(rw + 2 * (int64_t)PCG_LD * p.L + PCG_LD); rec.first = rec.steps + PCG_LD;
-        rec.L = p.L;
-        HIPCHK(hipMemsetAsync(rw, 0, (size_t)pcg_rec_doubles(p.L) * sizeof(double), h->stream));
-    }
-    PcgVec a;
-    a.R = p.work + lay.R; a.Z = p.work + lay.Z; a.P = p.work + lay.P; a.AP = p.work + lay.AP;
+    const PcgRec &rec = lay.rec;
+    if (p.L > 0) HIPCHK(hipMemsetAsync(rec.alpha, 0, lay.rec_bytes, h->stream));
     a.X = p.X; a.ldx = p.ldx; a.B = p.B; a.ldb = p.ldb; a.v = p.vdiag;
-    a.st = reinterpret_cast<PcgState *>(p.work + lay.state);
-    a.part1 = p.work + lay.part1;
     a.n = p.n; a.s = p.s;
-    rc = precond_begin(h, p.work, lay.pre, a); if (rc) return rc;
-    double *mvws = lay.mv_doubles ? p.work + lay.mv : nullptr;
+    rc = precond_begin(h, lay.pre); if (rc) return rc;
+    double *mvws = lay.mv;
     const long nblk = (long)((p.n + DOT_ROWS - 1) / DOT_ROWS), nblk_apply = (long)((p.n + 255) / 256);
     const dim3 gdot((unsigned)nblk), gdir((unsigned)((p.n * PCG_LD + 255) / 256));
     hipStream_t st = h->stream;
@@ -594,7 +602,7 @@ int pcg_driver(fvgp_handle *h, PcgCall p) {
         return 0;
     };
     auto precond = [&]() -> int {
-        return p.nn ? nn_precond(h, *p.nn, a, p.work + lay.nnT) : pcg_precond(h, p.G, p.ldg, p.q, p.C, p.ldc, a, p.work, lay.pre);
+        return p.nn ? nn_precond(h, *p.nn, a, lay.nnT) : pcg_precond(h, p.G, p.ldg, p.q, p.C, p.ldc, a, lay.pre);
     };
     PcgVec a1 = a; a1.part1 = a.part0;                            // (a scalar step that reads one partial array)
 
@@ -665,13 +673,22 @@ int pcg_driver(fvgp_handle *h, PcgCall p) {
     return 0;
 }
 
+// fvgp_hip_pchol's workspace: the core's pieces, then the residual diagonal
+void pchol_layout(Carve &c, int64_t n, PivotArgs &a) {
+    pivot_layout(c, n, 2, a);
+    a.var = c.take<double>(n);
+}
+
+// fvgp_hip_precond_factor's: the partial Gram sums of the nch chunks
+double *pf_layout(Carve &c, int64_t n, int q, int64_t &nch) { nch = (n + PF_CHUNK - 1) / PF_CHUNK; return c.take<double>(nch * q * q, sizeof(double)); }
+
 }  // namespace
 
 extern "C" {
 
 int64_t fvgp_hip_pchol_workspace_bytes(int64_t n, int q) {
     if (n < 1 || q < 1) return -1;
-    return (pivot_layout(0, n, 2).end + even_up(n)) * (int64_t)sizeof(double);      // the core's pieces, then the residual diagonal
+    return carve_bytes_for<PivotArgs>(pchol_layout, n);
 }
 
 int fvgp_hip_pchol(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta, int ntheta,
@@ -688,18 +705,15 @@ int fvgp_hip_pchol(fvgp_handle *h, int kernel_id, const double *x, int64_t n, in
     if (ldg < n) return -11;
     if (!piv_out) return -12;
     if (!work || ((uintptr_t)work & 15)) { fvgp_set_error("pchol: work must be 16-byte aligned"); return -14; }
-    if (work_bytes < fvgp_hip_pchol_workspace_bytes(n, q)) { fvgp_set_error("pchol: work smaller than fvgp_hip_pchol_workspace_bytes(n, q)"); return -15; }
+    // selection's run with the data as their own candidates: no conditioning, no noise, d = sigma^2 at the start, G the caller's
+    Carve c(work); PivotArgs a{};
+    pchol_layout(c, n, a);
+    if (work_bytes < c.bytes()) { fvgp_set_error("pchol: work smaller than fvgp_hip_pchol_workspace_bytes(n, q)"); return -15; }
     if (!rank_host) return -16;
     HIPCHK(hipSetDevice(h->device));
     KmatDesc k{};
     rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
-    const PivotLayout lay = pivot_layout(0, n, 2);
-    // selection's run with the data as their own candidates: no conditioning, no noise, d = sigma^2 at the start, G the caller's
-    PivotArgs a{};
-    a.x = x; a.xc = x; a.var = work + lay.end; a.G = G; a.ldg_in = ldg;
-    a.slot = work + lay.slot; a.best = work + lay.best;
-    a.st = reinterpret_cast<PivotState *>(work + lay.state);
-    a.taken = reinterpret_cast<unsigned char *>(work + lay.taken);
+    a.x = x; a.xc = x; a.G = G; a.ldg_in = ldg;
     a.idx = reinterpret_cast<long long *>(piv_out);
     a.n = n; a.P = n; a.cn = n; a.d = d; a.q = q; a.sig = k.sig; a.tol = tol;
     for (int i = 0; i < FVGP_MAX_DIM; ++i) a.il[i] = k.invl[i];
@@ -730,7 +744,7 @@ int fvgp_hip_pchol(fvgp_handle *h, int kernel_id, const double *x, int64_t n, in
 
 int64_t fvgp_hip_precond_workspace_bytes(int64_t n, int q) {
     if (n < 1 || q < 1) return -1;
-    return (n + PF_CHUNK - 1) / PF_CHUNK * (int64_t)q * q * (int64_t)sizeof(double);
+    return carve_bytes_for<int64_t>(pf_layout, n, q);
 }
 
 int fvgp_hip_precond_factor(fvgp_handle *h, const double *G, int64_t ldg, int q, int64_t n, const double *vdiag,
@@ -744,21 +758,22 @@ int fvgp_hip_precond_factor(fvgp_handle *h, const double *G, int64_t ldg, int q,
     int rc = check_square(C, q, ldc, 7, 4, 8);
     if (rc) return rc;
     if (!work || ((uintptr_t)work & 7)) return -9;
-    if (work_bytes < fvgp_hip_precond_workspace_bytes(n, q)) { fvgp_set_error("precond_factor: work smaller than fvgp_hip_precond_workspace_bytes(n, q)"); return -10; }
+    Carve c(work); int64_t nch;
+    double *gram = pf_layout(c, n, q, nch);
+    if (work_bytes < c.bytes()) { fvgp_set_error("precond_factor: work smaller than fvgp_hip_precond_workspace_bytes(n, q)"); return -10; }
     if (!info_host) return -11;
     HIPCHK(hipSetDevice(h->device));
-    const int64_t nch = (n + PF_CHUNK - 1) / PF_CHUNK;
     if (nch > 65535) { fvgp_set_error("precond_factor: n too large"); return -5; }
     const int nt = (q + 15) / 16;
-    HIPLAUNCH(pf_gram_kernel, dim3((unsigned)(nt * nt), (unsigned)nch), dim3(256), h->stream, G, (long)ldg, q, (long)n, vdiag, work);
-    HIPLAUNCH(pf_finish_kernel, dim3((unsigned)(((int64_t)q * q + 255) / 256)), dim3(256), h->stream, work, (long)nch, q, C, (long)ldc);
+    HIPLAUNCH(pf_gram_kernel, dim3((unsigned)(nt * nt), (unsigned)nch), dim3(256), h->stream, G, (long)ldg, q, (long)n, vdiag, gram);
+    HIPLAUNCH(pf_finish_kernel, dim3((unsigned)(((int64_t)q * q + 255) / 256)), dim3(256), h->stream, gram, (long)nch, q, C, (long)ldc);
     rc = launch_pad_identity(h, C, q, pad128(q), ldc); if (rc) return rc;
     return potrf_driver(h, C, q, ldc, info_host);
 }
 
 int64_t fvgp_hip_pcg_workspace_bytes(int64_t n, int q) {
     if (n < 1 || q < 0) return -1;
-    return pcg_layout(n, q).total * (int64_t)sizeof(double);
+    return carve_bytes_for<PcgVec>(pcg_layout, n, q, false, 0);
 }
 
 int fvgp_hip_pcg(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta, int ntheta,
@@ -772,7 +787,7 @@ int fvgp_hip_pcg(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int 
 
 int64_t fvgp_hip_pcg_lanczos_workspace_bytes(int64_t n, int q, int lanczos_steps) {
     if (n < 1 || q < 0 || lanczos_steps < 0 || lanczos_steps > FVGP_LANCZOS_MAX_STEPS) return -1;
-    return (pcg_layout(n, q).total + pcg_rec_doubles(lanczos_steps)) * (int64_t)sizeof(double);
+    return carve_bytes_for<PcgVec>(pcg_layout, n, q, false, lanczos_steps);
 }
 
 int fvgp_hip_pcg_lanczos(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta, int ntheta,
@@ -788,7 +803,7 @@ int fvgp_hip_pcg_lanczos(fvgp_handle *h, int kernel_id, const double *x, int64_t
 
 int64_t fvgp_hip_pcg_nn_workspace_bytes(int64_t n) {
     if (n < 1) return -1;
-    return pcg_layout(n, 0, true).total * (int64_t)sizeof(double);
+    return carve_bytes_for<PcgVec>(pcg_layout, n, 0, true, 0);
 }
 
 int fvgp_hip_pcg_nn(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta, int ntheta,
@@ -809,7 +824,7 @@ int fvgp_hip_pcg_nn(fvgp_handle *h, int kernel_id, const double *x, int64_t n, i
 
 int64_t fvgp_hip_nn_precond_apply_workspace_bytes(int64_t n) {
     if (n < 1) return -1;
-    return (3 * n * PCG_LD + (n + 255) / 256 * PCG_LD) * (int64_t)sizeof(double);
+    return carve_bytes_for<PcgVec>(nn_apply_layout, n);
 }
 
 int fvgp_hip_nn_precond_apply(fvgp_handle *h, int64_t n, const int *idx, int64_t ld, int m, const double *coef, const double *dinv,
@@ -824,16 +839,17 @@ int fvgp_hip_nn_precond_apply(fvgp_handle *h, int64_t n, const int *idx, int64_t
     if (!Z) return -14;
     if (ldz < s) return -15;
     if (!work || ((uintptr_t)work & 15)) { fvgp_set_error("nn_precond_apply: work must be 16-byte aligned"); return -16; }
-    if (work_bytes < fvgp_hip_nn_precond_apply_workspace_bytes(n)) {
+    Carve c(work); PcgVec a{};
+    double *T = nn_apply_layout(c, n, a);
+    if (work_bytes < c.bytes()) {
         fvgp_set_error("nn_precond_apply: work smaller than fvgp_hip_nn_precond_apply_workspace_bytes(n)"); return -17;
     }
     HIPCHK(hipSetDevice(h->device));
     const NnFactor f{idx, coef, dinv, tr_start, tr_pos, (long)n, (long)ld, (long)nnz, m};
-    PcgVec a{};
-    a.R = work; a.Z = work + n * PCG_LD; a.part0 = work + 3 * n * PCG_LD; a.n = n; a.s = s;
+    a.n = n; a.s = s;
     const dim3 gcopy((unsigned)((n * PCG_LD + 255) / 256));
     HIPLAUNCH(mf_copy_cols_kernel, gcopy, dim3(256), h->stream, R, (long)ldr, a.R, (long)PCG_LD, (long)n, s);
-    rc = nn_precond(h, f, a, work + 2 * n * PCG_LD); if (rc) return rc;
+    rc = nn_precond(h, f, a, T); if (rc) return rc;
     HIPLAUNCH(mf_copy_cols_kernel, gcopy, dim3(256), h->stream, (const double *)a.Z, (long)PCG_LD, Z, (long)ldz, (long)n, s);
     return 0;
 }
@@ -864,7 +880,7 @@ int fvgp_hip_precond_probes(fvgp_handle *h, uint64_t seed, uint64_t stream, int6
 
 int64_t fvgp_hip_precond_apply_workspace_bytes(int64_t n, int q) {
     if (n < 1 || q < 0) return -1;
-    return apply_layout(n, q).total * (int64_t)sizeof(double);
+    return carve_bytes_for<PcgVec>(apply_layout, n, q);
 }
 
 int fvgp_hip_precond_apply(fvgp_handle *h, const double *G, int64_t ldg, int q, const double *C, int64_t ldc, int64_t n,
@@ -886,15 +902,15 @@ int fvgp_hip_precond_apply(fvgp_handle *h, const double *G, int64_t ldg, int q, 
     if (!W) return -12;
     if (ldw < s) return -13;
     if (!work || ((uintptr_t)work & 15)) { fvgp_set_error("precond_apply: work must be 16-byte aligned"); return -14; }
-    if (work_bytes < fvgp_hip_precond_apply_workspace_bytes(n, q)) { fvgp_set_error("precond_apply: work smaller than fvgp_hip_precond_apply_workspace_bytes(n, rank)"); return -15; }
+    Carve c(work); PcgVec a{};
+    const PrecondWs lay = apply_layout(c, n, q, a);
+    if (work_bytes < c.bytes()) { fvgp_set_error("precond_apply: work smaller than fvgp_hip_precond_apply_workspace_bytes(n, rank)"); return -15; }
     HIPCHK(hipSetDevice(h->device));
-    const ApplyLayout lay = apply_layout(n, q);
-    PcgVec a{};
-    a.R = work + lay.R; a.Z = work + lay.Z; a.v = vdiag; a.n = n; a.s = s;
-    int rc = precond_begin(h, work, lay.pre, a); if (rc) return rc;
+    a.v = vdiag; a.n = n; a.s = s;
+    int rc = precond_begin(h, lay); if (rc) return rc;
     const dim3 gcopy((unsigned)((n * PCG_LD + 255) / 256));
     HIPLAUNCH(mf_copy_cols_kernel, gcopy, dim3(256), h->stream, R, (long)ldr, a.R, (long)PCG_LD, (long)n, s);
-    rc = pcg_precond(h, G, ldg, q, C, ldc, a, work, lay.pre); if (rc) return rc;
+    rc = pcg_precond(h, G, ldg, q, C, ldc, a, lay); if (rc) return rc;
     HIPLAUNCH(mf_copy_cols_kernel, gcopy, dim3(256), h->stream, (const double *)a.Z, (long)PCG_LD, W, (long)ldw, (long)n, s);
     return 0;
 }

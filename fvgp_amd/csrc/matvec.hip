@@ -258,7 +258,14 @@ __global__ __launch_bounds__(64) void kgrad_sum_kernel(const double *bpart, long
     out[hh] = first ? acc : out[hh] + acc;
 }
 
-inline int64_t kg_base_doubles(int64_t n1) { return (1 + (n1 + 63) / 64) * KG_H; }
+// fvgp_hip_kgrad_form's workspace: the result row, a row of sums per block of 64 rows; `full`: what the size query adds behind them for
+// the split plan, every chunk's sums where the product deals chunk ranges by itself (the entry hands the plan what it finds there)
+struct KgWs { double *out, *bpart; };
+inline KgWs kg_layout(Carve &c, int64_t n1, int64_t n2, bool full) {
+    const KgWs l{c.take<double>(KG_H, sizeof(double)), c.take<double>((n1 + 63) / 64 * KG_H, sizeof(double))};
+    if (full && (n1 + 63) / 64 < 512 && mv_chunks(n2) > 1) c.take<double>(mv_chunks(n2) * n1 * KG_H, sizeof(double));
+    return l;
+}
 
 }  // namespace
 
@@ -294,7 +301,7 @@ extern "C" {
 
 int64_t fvgp_hip_kmatvec_workspace_bytes(int64_t n1, int64_t n2, int s) {
     if (n1 < 1 || n2 < 1 || s < 1) return -1;
-    return mv_split_doubles(n1, n2, s) * (int64_t)sizeof(double);
+    return carve_bytes(mv_park_layout, n1, n2, s);
 }
 
 int fvgp_hip_kmatvec(fvgp_handle *h, int kernel_id, const double *x1, int64_t n1, const double *x2, int64_t n2, int d,
@@ -326,8 +333,7 @@ int fvgp_hip_kmatvec(fvgp_handle *h, int kernel_id, const double *x1, int64_t n1
 
 int64_t fvgp_hip_kgrad_form_workspace_bytes(int64_t n1, int64_t n2) {
     if (n1 < 1 || n2 < 1) return -1;
-    const int64_t park = (n1 + 63) / 64 < 512 && mv_chunks(n2) > 1 ? mv_chunks(n2) * n1 * KG_H : 0;
-    return (kg_base_doubles(n1) + park) * (int64_t)sizeof(double);
+    return carve_bytes(kg_layout, n1, n2, true);
 }
 
 int fvgp_hip_kgrad_form(fvgp_handle *h, int kernel_id, const double *x1, int64_t n1, const double *x2, int64_t n2, int d,
@@ -346,7 +352,8 @@ int fvgp_hip_kgrad_form(fvgp_handle *h, int kernel_id, const double *x1, int64_t
     if (!W) return -12;
     if (ldw < s) return -13;
     if (!work || ((uintptr_t)work & 7)) return -15;
-    if (work_bytes < kg_base_doubles(n1) * (int64_t)sizeof(double)) { fvgp_set_error("kgrad_form: work smaller than fvgp_hip_kgrad_form_workspace_bytes(n1, n2)"); return -16; }
+    Carve c(work); const KgWs l = kg_layout(c, n1, n2, false);
+    if (work_bytes < c.bytes()) { fvgp_set_error("kgrad_form: work smaller than fvgp_hip_kgrad_form_workspace_bytes(n1, n2)"); return -16; }
     if (!out_host) return -17;
     HIPCHK(hipSetDevice(h->device));
     KmatDesc k{};
@@ -354,9 +361,10 @@ int fvgp_hip_kgrad_form(fvgp_handle *h, int kernel_id, const double *x1, int64_t
     k.x1 = x1; k.n1 = n1; k.x2 = x2; k.n2 = n2;
     const int nh = kernel_param_count(kernel_id, d);
     const long bx = (long)((n1 + 63) / 64);
-    double *out = work, *bpart = work + KG_H, *park = work + kg_base_doubles(n1);
     // the product's plan, split where `work` has room for the chunk sums behind the blocks' (the bits are the same either way)
-    const MvPlan p = mv_plan(h, n1, n2, work_bytes / 8 - kg_base_doubles(n1), KG_H);
+    const int64_t left = (work_bytes - c.bytes()) / (int64_t)sizeof(double);
+    double *out = l.out, *bpart = l.bpart, *park = c.take<double>(left, sizeof(double));
+    const MvPlan p = mv_plan(h, n1, n2, left, KG_H);
     KgArgs a;
     kmat_fill(a, k);
     a.cpy = p.cpy;

@@ -385,36 +385,38 @@ __global__ __launch_bounds__(64) void nn_total_kernel(const double *part, long n
 inline int64_t nn_slices(int64_t n) { return (n + NN_SUM_ROWS - 1) / NN_SUM_ROWS; }
 inline int64_t nn_packed(int ntheta) { return (int64_t)ntheta * (ntheta + 1) / 2; }
 
-// work, in doubles, every piece on an even offset: [0] the info word, `tab` the theta table (all a conditionals call takes: it ends at
-// `out`); the likelihood: `out` the three results per b, `part` the pair's sums per (b, slice); from NN_GRAD: `grad` (B, ntheta), `gpart`
-// the scores' sums per (b, slice, column); at NN_FISHER: `fis` (B, P) packed, `fpart` the rows' sums per (b, slice, entry).  `end`: the
-// call's size.  A level's layout is the one below it and its own two pieces behind.
-struct NnLayout { int64_t tab, out, part, grad, gpart, fis, fpart, end; };
+// all a conditionals call takes, and the head of every other workspace of this unit: the info word in the first 16 bytes (where the
+// caller's buffer begins), `tab` the theta table
+struct NnCondWs { long long *info; double *tab; };
+NnCondWs nn_cond_layout(Carve &c, int B) {
+    return {c.take<long long>(1), c.take<double>((int64_t)B * NN_TAB)};
+}
 
-NnLayout nn_layout(int level, int64_t n, int B, int ntheta) {
-    NnLayout l{};
-    l.tab = 2;
-    l.out = l.tab + even_up((int64_t)B * NN_TAB);
-    l.part = l.out + even_up((int64_t)B * 3);
-    l.end = l.part + 2 * (int64_t)B * nn_slices(n);
-    if (level >= NN_GRAD) {
-        l.grad = even_up(l.end);
-        l.gpart = l.grad + even_up((int64_t)B * ntheta);
-        l.end = l.gpart + (int64_t)B * nn_slices(n) * ntheta;
-    }
-    if (level >= NN_FISHER) {
-        l.fis = even_up(l.end);
-        l.fpart = l.fis + even_up((int64_t)B * nn_packed(ntheta));
-        l.end = l.fpart + (int64_t)B * nn_slices(n) * nn_packed(ntheta);
-    }
+// the likelihood's, every result piece 16-byte aligned and the sums behind it packed: `out` the three results per b, `part` the pair's
+// sums per (b, slice); from NN_GRAD: `grad` (B, ntheta), `gpart` the scores' sums per (b, slice, column); at NN_FISHER: `fis` (B, P)
+// packed, `fpart` the rows' sums per (b, slice, entry).  A level's layout is the one below it and its own two pieces behind.
+struct NnWs { NnCondWs cond; double *out, *part, *grad, *gpart, *fis, *fpart; };
+NnWs nn_layout(Carve &c, int level, int64_t n, int B, int ntheta) {
+    const int64_t sums = (int64_t)B * nn_slices(n);
+    NnWs l{};
+    l.cond = nn_cond_layout(c, B);
+    l.out = c.take<double>((int64_t)B * 3); l.part = c.take<double>(2 * sums, sizeof(double));
+    if (level >= NN_GRAD) { l.grad = c.take<double>((int64_t)B * ntheta); l.gpart = c.take<double>(sums * ntheta, sizeof(double)); }
+    if (level >= NN_FISHER) { l.fis = c.take<double>((int64_t)B * nn_packed(ntheta)); l.fpart = c.take<double>(sums * nn_packed(ntheta), sizeof(double)); }
     return l;
+}
+
+// the factor's: the conditionals' of one vector, then the n conditional variances
+struct NnFactorWs { NnCondWs cond; double *dvar; };
+NnFactorWs nn_factor_layout(Carve &c, int64_t n) {
+    return {nn_cond_layout(c, 1), c.take<double>(n, sizeof(double))};
 }
 
 // the theta table of B hyperparameter vectors into work, the conditionals over it at `level` and the info word; nothing is read back.
 // score (B, nq, ntheta) from NN_GRAD and fisher (B, nq, P) at NN_FISHER, else NULL (the likelihood's structure only: xq == xr, s == v)
 int nn_run_conditionals(fvgp_handle *h, int level, int kernel_id, const double *xq, int64_t nq, const double *xr, int64_t nr, int d,
                         const double *thetas, int ntheta, int B, const int *idx, int64_t ld, int m, const double *r, const double *v,
-                        const double *s, double *mu, double *var, double *work, double *score, double *fisher,
+                        const double *s, double *mu, double *var, const NnCondWs &w, double *score, double *fisher,
                         double *coef = nullptr, int64_t ldc = 0, double *dinv = nullptr) {
     std::vector<double> tab((size_t)B * NN_TAB);
     KmatDesc k{};
@@ -424,7 +426,7 @@ int nn_run_conditionals(fvgp_handle *h, int level, int kernel_id, const double *
         tab[(size_t)b * NN_TAB] = k.sig;
         for (int i = 0; i < FVGP_MAX_DIM; ++i) tab[(size_t)b * NN_TAB + 1 + i] = k.invl[i];
     }
-    double *tab_dev = work + nn_layout(NN_VALUE, nq, B, ntheta).tab;
+    double *tab_dev = w.tab;
     HIPCHK(hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));       // (the table leaves this frame)
     NcArgs a;
@@ -443,7 +445,7 @@ int nn_run_conditionals(fvgp_handle *h, int level, int kernel_id, const double *
         });
     });
     HIPCHK(hipGetLastError());
-    HIPLAUNCH(nn_info_kernel, dim3(1), dim3(256), h->stream, (const double *)var, (long)(nq * B), (long long *)work);
+    HIPLAUNCH(nn_info_kernel, dim3(1), dim3(256), h->stream, (const double *)var, (long)(nq * B), w.info);
     return 0;
 }
 
@@ -485,25 +487,25 @@ int nn_loglik(int level, const std::string &who, fvgp_handle *h, int kernel_id, 
     if (level == NN_FISHER && !fisher_rows) return -17;
     const int at = 15 + level;                     // the last device array's position: var, score or fisher_rows
     if (!work || ((uintptr_t)work & 7)) return -(at + 1);
-    const NnLayout l = nn_layout(level, n, B, ntheta);
-    if (work_bytes < l.end * (int64_t)sizeof(double)) { fvgp_set_error(who + ": work smaller than " + sizing[level]); return -(at + 2); }
+    Carve c(work); const NnWs l = nn_layout(c, level, n, B, ntheta);
+    if (work_bytes < c.bytes()) { fvgp_set_error(who + ": work smaller than " + sizing[level]); return -(at + 2); }
     if (!out_host) return -(at + 3);
     if (level >= NN_GRAD && !grad_host) return -(at + 4);
     if (level == NN_FISHER && !fisher_host) return -(at + 5);
     if (!info_host) return -(at + 4 + level);
     HIPCHK(hipSetDevice(h->device));
-    rc = nn_run_conditionals(h, level, kernel_id, x, n, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, v, mu, var, work, score, fisher_rows);
+    rc = nn_run_conditionals(h, level, kernel_id, x, n, x, n, d, thetas_host, ntheta, B, idx, ld, m, r, v, v, mu, var, l.cond, score, fisher_rows);
     if (rc) return rc;
     const int P = (int)nn_packed(ntheta);
-    rc = nn_sum_columns(h->stream, NnLikTerms{r, mu, var}, n, 2, B, work + l.part, work + l.out); if (rc) return rc;
-    if (level >= NN_GRAD) { rc = nn_sum_columns(h->stream, NnColumns{score}, n, ntheta, B, work + l.gpart, work + l.grad); if (rc) return rc; }
-    if (level == NN_FISHER) { rc = nn_sum_columns(h->stream, NnColumns{fisher_rows}, n, P, B, work + l.fpart, work + l.fis); if (rc) return rc; }
+    rc = nn_sum_columns(h->stream, NnLikTerms{r, mu, var}, n, 2, B, l.part, l.out); if (rc) return rc;
+    if (level >= NN_GRAD) { rc = nn_sum_columns(h->stream, NnColumns{score}, n, ntheta, B, l.gpart, l.grad); if (rc) return rc; }
+    if (level == NN_FISHER) { rc = nn_sum_columns(h->stream, NnColumns{fisher_rows}, n, P, B, l.fpart, l.fis); if (rc) return rc; }
     long long info = 0;
     std::vector<double> packed(level == NN_FISHER ? (size_t)B * P : 0);
-    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(out_host, work + l.out, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (level >= NN_GRAD) HIPCHK(hipMemcpyAsync(grad_host, work + l.grad, (size_t)B * ntheta * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (level == NN_FISHER) HIPCHK(hipMemcpyAsync(packed.data(), work + l.fis, packed.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&info, l.cond.info, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(out_host, l.out, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (level >= NN_GRAD) HIPCHK(hipMemcpyAsync(grad_host, l.grad, (size_t)B * ntheta * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (level == NN_FISHER) HIPCHK(hipMemcpyAsync(packed.data(), l.fis, packed.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *info_host = info;
     // the packed lower triangles into full symmetric matrices
@@ -523,18 +525,17 @@ extern "C" {
 
 int64_t fvgp_hip_nn_workspace_bytes(int what, int64_t nq, int B) {
     if (what < FVGP_NN_SEARCH || what > FVGP_NN_LOGLIK || nq < 1 || B < 1) return -1;
-    const NnLayout l = nn_layout(NN_VALUE, nq, B, 0);
-    return (what == FVGP_NN_SEARCH ? 0 : what == FVGP_NN_CONDITIONALS ? l.out : l.end) * (int64_t)sizeof(double);
+    return what == FVGP_NN_CONDITIONALS ? carve_bytes(nn_cond_layout, B) : what == FVGP_NN_LOGLIK ? carve_bytes(nn_layout, NN_VALUE, nq, B, 0) : 0;
 }
 
 int64_t fvgp_hip_nn_grad_workspace_bytes(int64_t n, int B, int ntheta) {
     if (n < 1 || B < 1 || ntheta < 1) return -1;
-    return nn_layout(NN_GRAD, n, B, ntheta).end * (int64_t)sizeof(double);
+    return carve_bytes(nn_layout, NN_GRAD, n, B, ntheta);
 }
 
 int64_t fvgp_hip_nn_fisher_workspace_bytes(int64_t n, int B, int ntheta) {
     if (n < 1 || B < 1 || ntheta < 1) return -1;
-    return nn_layout(NN_FISHER, n, B, ntheta).end * (int64_t)sizeof(double);
+    return carve_bytes(nn_layout, NN_FISHER, n, B, ntheta);
 }
 
 int fvgp_hip_nn_conditionals(fvgp_handle *h, int kernel_id, const double *xq, int64_t nq, const double *xr, int64_t nr, int d,
@@ -557,24 +558,24 @@ int fvgp_hip_nn_conditionals(fvgp_handle *h, int kernel_id, const double *xq, in
     if (!mu) return -17;
     if (!var) return -18;
     if (!work || ((uintptr_t)work & 7)) return -19;
-    if (work_bytes < fvgp_hip_nn_workspace_bytes(FVGP_NN_CONDITIONALS, nq, B)) {
+    Carve c(work); const NnCondWs l = nn_cond_layout(c, B);
+    if (work_bytes < c.bytes()) {
         fvgp_set_error("nn_conditionals: work smaller than fvgp_hip_nn_workspace_bytes(FVGP_NN_CONDITIONALS, nq, B)"); return -20;
     }
     if (!info_host) return -21;
     HIPCHK(hipSetDevice(h->device));
-    rc = nn_run_conditionals(h, NN_VALUE, kernel_id, xq, nq, xr, nr, d, thetas_host, ntheta, B, idx, ld, m, r, v, s_or_null, mu, var, work, nullptr, nullptr);
+    rc = nn_run_conditionals(h, NN_VALUE, kernel_id, xq, nq, xr, nr, d, thetas_host, ntheta, B, idx, ld, m, r, v, s_or_null, mu, var, l, nullptr, nullptr);
     if (rc) return rc;
     long long info = 0;
-    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&info, l.info, sizeof(info), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *info_host = info;
     return 0;
 }
 
-// the factor's work: the conditionals' (info word, theta table of one vector), then the n conditional variances
 int64_t fvgp_hip_nn_factor_workspace_bytes(int64_t n) {
     if (n < 1) return -1;
-    return (nn_layout(NN_VALUE, n, 1, 0).out + n) * (int64_t)sizeof(double);
+    return carve_bytes(nn_factor_layout, n);
 }
 
 int fvgp_hip_nn_factor(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d, const double *theta_host, int ntheta,
@@ -593,15 +594,15 @@ int fvgp_hip_nn_factor(fvgp_handle *h, int kernel_id, const double *x, int64_t n
     if (ldc < m) return -13;
     if (!dinv) return -14;
     if (!work || ((uintptr_t)work & 7)) return -15;
-    if (work_bytes < fvgp_hip_nn_factor_workspace_bytes(n)) { fvgp_set_error("nn_factor: work smaller than fvgp_hip_nn_factor_workspace_bytes(n)"); return -16; }
+    Carve c(work); const NnFactorWs l = nn_factor_layout(c, n);
+    if (work_bytes < c.bytes()) { fvgp_set_error("nn_factor: work smaller than fvgp_hip_nn_factor_workspace_bytes(n)"); return -16; }
     if (!info_host) return -17;
     HIPCHK(hipSetDevice(h->device));
-    double *dvar = work + nn_layout(NN_VALUE, n, 1, 0).out;
-    rc = nn_run_conditionals(h, NN_FACTOR, kernel_id, x, n, x, n, d, theta_host, ntheta, 1, idx, ld, m, nullptr, v, v, nullptr, dvar, work,
+    rc = nn_run_conditionals(h, NN_FACTOR, kernel_id, x, n, x, n, d, theta_host, ntheta, 1, idx, ld, m, nullptr, v, v, nullptr, l.dvar, l.cond,
                              nullptr, nullptr, coef, ldc, dinv);
     if (rc) return rc;
     long long info = 0;
-    HIPCHK(hipMemcpyAsync(&info, work, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&info, l.cond.info, sizeof(info), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *info_host = info;
     return 0;

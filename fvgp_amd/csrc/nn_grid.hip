@@ -43,27 +43,14 @@ constexpr double NG_BOUND_FLOOR = 1e-270;         // a bound below this stops no
 enum { NI_MAGIC = 0, NI_NR = 1, NI_D = 2, NI_SCALE = 3, NI_IS = 6, NI_LO = 9, NI_H = 12, NI_INVH = 13, NI_NC = 14, NI_CELLS = 17, NI_EARLY = 18 };
 
 inline int64_t ng_cell_cap(int64_t nr) { return nr < NG_MAX_CELLS ? nr : NG_MAX_CELLS; }
-inline int64_t even_ints(int64_t v) { return (v + 1) & ~(int64_t)1; }
 
-// the grid buffer, in bytes: bucketed coordinates (nr, d) doubles | start (cells + 1, at most cap + 1) ints | bucketed indices (nr) ints
-struct NgGridLayout { int64_t bx, start, bidx, end; };
-inline NgGridLayout ng_grid_layout(int64_t nr, int d) {
-    NgGridLayout l;
-    l.bx = 0;
-    l.start = nr * d * (int64_t)sizeof(double);
-    l.bidx = l.start + even_ints(ng_cell_cap(nr) + 1) * (int64_t)sizeof(int);
-    l.end = l.bidx + even_ints(nr) * (int64_t)sizeof(int);
-    return l;
-}
-// the build's workspace, in bytes: box partials | cell of every row | rank of every row in its cell | block sums of the scan
-struct NgWorkLayout { int64_t box, cid, rank, bsum, end; };
-inline NgWorkLayout ng_work_layout(int64_t nr) {
-    NgWorkLayout l;
-    l.box = 0;
-    l.cid = (int64_t)NG_BOX_WGS * NG_BOX_WORDS * sizeof(double);
-    l.rank = l.cid + even_ints(nr) * (int64_t)sizeof(int);
-    l.bsum = l.rank + even_ints(nr) * (int64_t)sizeof(int);
-    l.end = l.bsum + even_ints(NG_SCAN_MAX_BLOCKS) * (int64_t)sizeof(int);
+// the grid buffer, every piece a multiple of 8 bytes: bucketed coordinates (nr, d) | start (cells + 1, at most cap + 1) | bucketed indices (nr)
+struct NgGridBuf { double *bx; int *start, *bidx; };
+inline NgGridBuf ng_grid_layout(Carve &c, int64_t nr, int d) {
+    NgGridBuf l;
+    l.bx = c.take<double>(nr * d, 8);
+    l.start = c.take<int>(ng_cell_cap(nr) + 1, 8);
+    l.bidx = c.take<int>(nr, 8);
     return l;
 }
 
@@ -90,6 +77,14 @@ struct NbArgs {
     int nwg;
     NgGrid g;
 };
+// the build's workspace, every piece a multiple of 8 bytes: box partials | cell of every row | rank of every row in its cell | block
+// sums of the scan; the pointers go into the build's arguments
+inline void ng_work_layout(Carve &c, int64_t nr, NbArgs &a) {
+    a.box = c.take<double>((int64_t)NG_BOX_WGS * NG_BOX_WORDS, 8);
+    a.cid = c.take<int>(nr, 8);
+    a.rank = c.take<int>(nr, 8);
+    a.bsum = c.take<int>(NG_SCAN_MAX_BLOCKS, 8);
+}
 
 template <int D>
 __global__ __launch_bounds__(NG_THREADS) void ng_box_kernel(NbArgs a) {
@@ -368,12 +363,12 @@ extern "C" {
 
 int64_t fvgp_hip_nn_grid_bytes(int64_t nr, int d) {
     if (nr < 1 || nr > 0x7fffffffLL || d < 1 || d > NG_MAX_DIM) return -1;
-    return ng_grid_layout(nr, d).end;
+    return carve_bytes(ng_grid_layout, nr, d);
 }
 
 int64_t fvgp_hip_nn_grid_workspace_bytes(int64_t nr, int d) {
     if (nr < 1 || nr > 0x7fffffffLL || d < 1 || d > NG_MAX_DIM) return -1;
-    return ng_work_layout(nr).end;
+    return carve_bytes_for<NbArgs>(ng_work_layout, nr);
 }
 
 int fvgp_hip_nn_grid_build(fvgp_handle *h, const double *xr, int64_t nr, int d, const double *scales_host, void *grid_dev,
@@ -386,21 +381,18 @@ int fvgp_hip_nn_grid_build(fvgp_handle *h, const double *xr, int64_t nr, int d, 
     double scale[NG_MAX_DIM], is[NG_MAX_DIM];
     if (!nn_scales("nn_grid_build", scales_host, d, NG_MAX_DIM, is, scale)) return -5;
     if (!grid_dev || ((uintptr_t)grid_dev & 7)) return -6;
-    if (grid_bytes < fvgp_hip_nn_grid_bytes(nr, d)) { fvgp_set_error("nn_grid_build: grid buffer smaller than fvgp_hip_nn_grid_bytes(nr, d)"); return -7; }
+    Carve gc(grid_dev), wc(work); const NgGridBuf gl = ng_grid_layout(gc, nr, d);
+    NbArgs a;
+    ng_work_layout(wc, nr, a);
+    if (grid_bytes < gc.bytes()) { fvgp_set_error("nn_grid_build: grid buffer smaller than fvgp_hip_nn_grid_bytes(nr, d)"); return -7; }
     if (!work || ((uintptr_t)work & 7)) return -8;
-    if (work_bytes < fvgp_hip_nn_grid_workspace_bytes(nr, d)) {
+    if (work_bytes < wc.bytes()) {
         fvgp_set_error("nn_grid_build: work smaller than fvgp_hip_nn_grid_workspace_bytes(nr, d)"); return -9;
     }
     if (!info_host) return -10;
     HIPCHK(hipSetDevice(h->device));
-    const NgGridLayout gl = ng_grid_layout(nr, d);
-    const NgWorkLayout wl = ng_work_layout(nr);
-    char *gb = static_cast<char *>(grid_dev), *wb = static_cast<char *>(work);
-    NbArgs a;
     a.x = xr; a.nr = nr;
-    a.box = reinterpret_cast<double *>(wb + wl.box);
-    a.cid = reinterpret_cast<int *>(wb + wl.cid); a.rank = reinterpret_cast<int *>(wb + wl.rank); a.bsum = reinterpret_cast<int *>(wb + wl.bsum);
-    a.bx = reinterpret_cast<double *>(gb + gl.bx); a.start = reinterpret_cast<int *>(gb + gl.start); a.bidx = reinterpret_cast<int *>(gb + gl.bidx);
+    a.bx = gl.bx; a.start = gl.start; a.bidx = gl.bidx;
     a.nwg = (int)std::min<int64_t>(NG_BOX_WGS, (nr + NG_THREADS - 1) / NG_THREADS);
     a.len = 0; a.g = NgGrid{};
     // 1. the box
@@ -478,10 +470,9 @@ int fvgp_hip_nn_grid_search(fvgp_handle *h, const double *xq, int64_t nq, const 
         if (rc) return rc;
         if (early == nq) return 0;
     }
-    const NgGridLayout gl = ng_grid_layout(nr, d);
-    const char *gb = static_cast<const char *>(grid_dev);
-    a.bx = reinterpret_cast<const double *>(gb + gl.bx); a.start = reinterpret_cast<const int *>(gb + gl.start);
-    a.bidx = reinterpret_cast<const int *>(gb + gl.bidx);
+    Carve gc(const_cast<void *>(grid_dev));                       // (the search only reads the grid)
+    const NgGridBuf gl = ng_grid_layout(gc, nr, d);
+    a.bx = gl.bx; a.start = gl.start; a.bidx = gl.bidx;
     a.xq = xq + early * d; a.out = idx_out + early * ld;
     a.nq = nq - early; a.nr = nr; a.ld = ld; a.c0 = c0 < 0 ? -1 : c0 + early; a.m = m;
     a.shells = std::max(a.g.nc[0], std::max(a.g.nc[1], a.g.nc[2]));

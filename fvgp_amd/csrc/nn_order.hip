@@ -86,9 +86,11 @@ __global__ __launch_bounds__(NO_THREADS) void nn_maxmin_step_kernel(NoArgs a) {
     if (tid == 0) a.part[(long)(a.t & 1) * NO_MAX_WGS + blockIdx.x] = b;
 }
 
-// work, in doubles: the n distances, then the two rows of partials (a Best is two doubles wide)
-inline int64_t no_part_offset(int64_t n) { return even_up(n); }
-inline int64_t no_work_doubles(int64_t n) { return no_part_offset(n) + 2 * NO_MAX_WGS * (int64_t)(sizeof(Best) / sizeof(double)); }
+// the workspace: the n distances, then the two rows of partials; the pointers go into the steps' arguments
+inline void no_layout(Carve &c, int64_t n, NoArgs &a) {
+    a.mind = c.take<double>(n);
+    a.part = c.take<Best>(2 * NO_MAX_WGS);
+}
 
 }  // namespace
 
@@ -96,7 +98,7 @@ extern "C" {
 
 int64_t fvgp_hip_nn_maxmin_workspace_bytes(int64_t n) {
     if (n < 1) return -1;
-    return no_work_doubles(n) * (int64_t)sizeof(double);
+    return carve_bytes_for<NoArgs>(no_layout, n);
 }
 
 int fvgp_hip_nn_maxmin_order(fvgp_handle *h, const double *x, int64_t n, int d, const double *scales_host, int64_t first, int64_t q,
@@ -112,7 +114,8 @@ int fvgp_hip_nn_maxmin_order(fvgp_handle *h, const double *x, int64_t n, int d, 
     if (q < 1 || q > n) { fvgp_set_error("nn_maxmin_order: 1 .. n points to order"); return -7; }
     if (!perm_out) return -8;
     if (!work || ((uintptr_t)work & 7)) return -10;
-    if (work_bytes < fvgp_hip_nn_maxmin_workspace_bytes(n)) {
+    Carve c(work); no_layout(c, n, a);
+    if (work_bytes < c.bytes()) {
         fvgp_set_error("nn_maxmin_order: work smaller than fvgp_hip_nn_maxmin_workspace_bytes(n)"); return -11;
     }
     HIPCHK(hipSetDevice(h->device));
@@ -120,7 +123,7 @@ int fvgp_hip_nn_maxmin_order(fvgp_handle *h, const double *x, int64_t n, int d, 
     const int64_t per = (n + NO_MAX_WGS - 1) / NO_MAX_WGS;
     a.strip = (per + NO_THREADS - 1) / NO_THREADS * NO_THREADS;
     a.nwg = (int)((n + a.strip - 1) / a.strip);
-    a.x = x; a.mind = work; a.part = reinterpret_cast<Best *>(work + no_part_offset(n));
+    a.x = x;
     a.perm = reinterpret_cast<long long *>(perm_out); a.dist = dist_out;
     a.n = n; a.first = first; a.d = d;
     for (int64_t t = 0; t < q; ++t) {

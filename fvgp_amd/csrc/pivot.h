@@ -148,16 +148,15 @@ __global__ __launch_bounds__(256) void pivot_downdate_kernel(PivotArgs a, long s
     }
 }
 
-// the workspace every run needs, from offset o on (in doubles, each piece a multiple of 2); `words` per partial: 3 with the maxima
-struct PivotLayout { int64_t slot, state, best, taken, end; };
-inline PivotLayout pivot_layout(int64_t o, int64_t P, int words) {
-    PivotLayout l;
-    l.slot = o; o += even_up(FVGP_MAX_DIM);
-    l.state = o; o += even_up((int64_t)(sizeof(PivotState) / sizeof(double)));
-    l.best = o; o += even_up(words * ((P + PIVOT_PART - 1) / PIVOT_PART));
-    l.taken = o; o += even_up((P + 7) / 8);
-    l.end = o;
-    return l;
+// the workspace every run needs, each piece a multiple of 16 bytes; `words` per partial: 3 with the maxima, which then lie behind the
+// (score, index) pairs inside `best` as dmaxp.  The pointers go into the run's arguments
+inline void pivot_layout(Carve &c, int64_t P, int words, PivotArgs &a) {
+    const int64_t parts = (P + PIVOT_PART - 1) / PIVOT_PART;
+    a.slot = c.take<double>(FVGP_MAX_DIM);
+    a.st = c.take<PivotState>(1);
+    a.best = c.take<double>(words * parts);
+    a.dmaxp = words > 2 ? c.view<double>(a.best, 2 * parts) : nullptr;
+    a.taken = c.take<unsigned char>(P);
 }
 
 }  // namespace

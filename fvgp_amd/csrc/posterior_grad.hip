@@ -133,11 +133,14 @@ __global__ __launch_bounds__(256) void posterior_grad_reduce_kernel(const double
 
 int64_t pg_slices(int64_t n) { return slice_count(n); }
 
+// fvgp_hip_posterior_grad's scratch: every slice's partial sums, 2 + 2 n_dirs per prediction point
+double *pg_layout(Carve &c, int64_t n, int64_t P, int n_dirs) { return c.take<double>(pg_slices(n) * (2 + 2 * (int64_t)n_dirs) * P, sizeof(double)); }
+
 }  // namespace
 
 int64_t fvgp_hip_posterior_grad_workspace_bytes(int64_t n, int64_t P, int n_dirs) {
     if (n < 1 || P < 1 || n_dirs < 1 || n_dirs > FVGP_MAX_DIM) return -1;
-    return pg_slices(n) * (2 + 2 * (int64_t)n_dirs) * P * (int64_t)sizeof(double);
+    return carve_bytes(pg_layout, n, P, n_dirs);
 }
 
 int fvgp_hip_posterior_grad(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
@@ -158,7 +161,8 @@ int fvgp_hip_posterior_grad(fvgp_handle *h, int kernel_id, const double *x, int6
     int rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
     if (n_dirs < 1 || n_dirs > d) { fvgp_set_error("posterior_grad: 1 <= n_dirs <= d"); return -15; }
     if (!work) return -16;
-    if (work_bytes < fvgp_hip_posterior_grad_workspace_bytes(n, P, n_dirs)) {
+    Carve c(work); double *part = pg_layout(c, n, P, n_dirs);
+    if (work_bytes < c.bytes()) {
         fvgp_set_error("posterior_grad: work smaller than fvgp_hip_posterior_grad_workspace_bytes(n, P, n_dirs)"); return -17;
     }
     if (!A_out) return -18;
@@ -167,7 +171,7 @@ int fvgp_hip_posterior_grad(fvgp_handle *h, int kernel_id, const double *x, int6
     if (W && !dv_out) return -21;
     HIPCHK(hipSetDevice(h->device));
     PGArgs a;
-    a.x = x; a.xp = xpred; a.alpha = alpha; a.W = W; a.part = work;
+    a.x = x; a.xp = xpred; a.alpha = alpha; a.W = W; a.part = part;
     a.n = n; a.P = P; a.ldw = ldw; a.d = d; a.nd = n_dirs; a.ncol = ncol; a.comp = component;
     a.sig = k.sig;
     for (int i = 0; i < FVGP_MAX_DIM; ++i) a.il[i] = k.invl[i];
@@ -182,7 +186,7 @@ int fvgp_hip_posterior_grad(fvgp_handle *h, int kernel_id, const double *x, int6
     HIPCHK(hipGetLastError());
     const int64_t total = (2 + 2 * (int64_t)n_dirs) * P;
     hipLaunchKernelGGL(posterior_grad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,
-                       (const double *)work, (long)S, (long)P, n_dirs, W ? 1 : 0, A_out, q_out, dm_out, dv_out);
+                       (const double *)part, (long)S, (long)P, n_dirs, W ? 1 : 0, A_out, q_out, dm_out, dv_out);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -124,10 +124,16 @@ int fvgp_hip_normal_fill(fvgp_handle *h, uint64_t seed, uint64_t stream, int64_t
     return launch_normal_fill(h, seed, stream, row0, col0, Z, ldz, rows, cols, rows, cols, nullptr, 0);
 }
 
+// fvgp_hip_mvn_sample's scratch: Z and C = L Z (padded n by padded nsamp each), the masked diagonal tiles D
+struct SampleWs { double *Z, *C, *D; };
+static SampleWs sample_layout(Carve &c, int64_t n, int64_t nsamp) {
+    const int64_t np = pad128(n), sp = pad128(nsamp);
+    return {c.take<double>(np * sp), c.take<double>(np * sp), c.take<double>(np * TILE)};
+}
+
 int64_t fvgp_hip_mvn_sample_workspace_bytes(int64_t n, int64_t nsamp) {
     if (n < 1 || nsamp < 1) return -1;
-    const int64_t np = pad128(n), sp = pad128(nsamp);
-    return (2 * np * sp + np * TILE) * (int64_t)sizeof(double);        // Z, L Z, the masked diagonal tiles
+    return carve_bytes(sample_layout, n, nsamp);
 }
 
 int fvgp_hip_mvn_sample(fvgp_handle *h, const double *L, int64_t n, int64_t ldl, const double *mean,
@@ -146,12 +152,13 @@ int fvgp_hip_mvn_sample(fvgp_handle *h, const double *L, int64_t n, int64_t ldl,
     if (Z_out && ((uintptr_t)Z_out & 7)) return -12;
     if (Z_out && ldz < nsamp) return -13;
     if (!work || ((uintptr_t)work & 15)) { fvgp_set_error("mvn_sample: work must be 16-byte aligned"); return -14; }
-    if (work_bytes < fvgp_hip_mvn_sample_workspace_bytes(n, nsamp)) {
+    Carve c(work); const SampleWs l = sample_layout(c, n, nsamp);
+    if (work_bytes < c.bytes()) {
         fvgp_set_error("mvn_sample: work smaller than fvgp_hip_mvn_sample_workspace_bytes(n, nsamp)"); return -15;
     }
     HIPCHK(hipSetDevice(h->device));
     const int64_t np = pad128(n), sp = pad128(nsamp), nb = np / TILE;
-    double *Z = work, *C = work + np * sp, *D = work + 2 * np * sp;
+    double *Z = l.Z, *C = l.C, *D = l.D;
 
     rc = launch_normal_fill(h, seed, stream, 0, samp0, Z, sp, n, nsamp, np, sp, Z_out, ldz); if (rc) return rc;
     hipLaunchKernelGGL(diag_tiles_lower_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, L, (long)ldl, (long)n, D);

@@ -56,16 +56,16 @@ __global__ __launch_bounds__(256) void select_cross_kernel(PivotArgs a) {
     a.part[(long)blockIdx.y * a.pcap + loc] = s;
 }
 
-// offsets in doubles (each a multiple of 2): the solves' padded n-vector at 0, the core's pieces, G (q, P), the slice partials
-struct SelLayout { PivotLayout piv; int64_t G, part, total; };
-SelLayout sel_layout(int64_t n, int64_t P, int q) {
-    SelLayout l;
-    const int64_t pcap = P < SEL_BLOCK_MAX ? P : SEL_BLOCK_MAX;
-    l.piv = pivot_layout(pad128(n), P, 3);
-    l.G = l.piv.end;
-    l.part = l.G + even_up((int64_t)q * P);
-    l.total = l.part + slice_count(n) * pcap;
-    return l;
+// the workspace of a selection, every piece but the last a multiple of 16 bytes: the solves' padded n-vector, the core's pieces, G (q, P),
+// the slice partials.  The pointers go into the run's arguments; the solves' vector comes back writable
+double *sel_layout(Carve &c, int64_t n, int64_t P, int q, PivotArgs &a) {
+    a.pcap = P < SEL_BLOCK_MAX ? P : SEL_BLOCK_MAX;
+    double *kvec = c.take<double>(pad128(n));
+    a.w = kvec;
+    pivot_layout(c, P, 3, a);
+    a.G = c.take<double>((int64_t)q * P);
+    a.part = c.take<double>(slice_count(n) * a.pcap, sizeof(double));
+    return kvec;
 }
 
 }  // namespace
@@ -74,7 +74,7 @@ extern "C" {
 
 int64_t fvgp_hip_select_workspace_bytes(int64_t n, int64_t P, int q) {
     if (n < 1 || P < 1 || q < 1) return -1;
-    return sel_layout(n, P, q).total * (int64_t)sizeof(double);
+    return carve_bytes_for<PivotArgs>(sel_layout, n, P, q);
 }
 
 int fvgp_hip_select_batch(fvgp_handle *h, int kernel_id, const double *x, int64_t n, int d,
@@ -97,7 +97,9 @@ int fvgp_hip_select_batch(fvgp_handle *h, int kernel_id, const double *x, int64_
     if (criterion != 0 && criterion != 1) return -15;
     if (!(tol >= 0.0)) return -17;
     if (!work || ((uintptr_t)work & 15)) { fvgp_set_error("select_batch: work must be 16-byte aligned"); return -18; }
-    if (work_bytes < fvgp_hip_select_workspace_bytes(n, P, q)) {
+    Carve c(work); PivotArgs a;
+    double *kvec = sel_layout(c, n, P, q, a);
+    if (work_bytes < c.bytes()) {
         fvgp_set_error("select_batch: work smaller than fvgp_hip_select_workspace_bytes(n, P, q)"); return -19;
     }
     if (!idx_out) return -20;
@@ -110,26 +112,19 @@ int fvgp_hip_select_batch(fvgp_handle *h, int kernel_id, const double *x, int64_
     // (its own codes, numbered by fvgp_hip_kmat's arguments, cannot come back: kernel_id, d and ntheta were checked above)
     rc = kmat_desc_from_theta(kernel_id, d, theta, ntheta, &k); if (rc) return rc;
     const int64_t np = pad128(n);
-    const SelLayout lay = sel_layout(n, P, q);
     const int64_t block = h->select_block < SEL_BLOCK_MAX ? h->select_block : SEL_BLOCK_MAX;
     // the handle's own buffers (block inverses of the factor, the sweeps' vector): allocated on the first call that needs them
     rc = ensure_linv(h, L, n, ldl); if (rc) return rc;
     rc = ensure_scratch(h, np); if (rc) return rc;
 
-    PivotArgs a;
     a.x = x; a.xc = xcand; a.noise = noise; a.var = var;
-    a.G = work + lay.G; a.ldg_in = P; a.Gout = G_out; a.ldg = ldg;
-    a.w = work; a.slot = work + lay.piv.slot; a.part = work + lay.part;
-    a.best = work + lay.piv.best; a.dmaxp = a.best + 2 * ((P + PIVOT_PART - 1) / PIVOT_PART);
-    a.st = reinterpret_cast<PivotState *>(work + lay.piv.state);
-    a.taken = reinterpret_cast<unsigned char *>(work + lay.piv.taken);
+    a.ldg_in = P; a.Gout = G_out; a.ldg = ldg;
     a.idx = reinterpret_cast<long long *>(idx_out); a.pickv = pick_var_out;
-    a.n = n; a.P = P; a.pcap = P < SEL_BLOCK_MAX ? P : SEL_BLOCK_MAX; a.c0 = 0; a.cn = 0;
+    a.n = n; a.P = P; a.c0 = 0; a.cn = 0;
     a.d = d; a.q = q; a.t = 0; a.crit = criterion; a.repeats = allow_repeats ? 1 : 0;
     a.sig = k.sig; a.tol = tol;
     for (int i = 0; i < FVGP_MAX_DIM; ++i) a.il[i] = k.invl[i];
 
-    double *kvec = work;
     HIPCHK(hipMemsetAsync(kvec, 0, (size_t)np * sizeof(double), h->stream));          // the padding rows stay 0 through every step
     hipLaunchKernelGGL(pivot_init_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
